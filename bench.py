@@ -15,17 +15,30 @@ finishing arena on a second stream (include/cilqr.h, CILQR_OPT_FINISH_THRESHOLD)
 the handles, which drift apart by themselves, fill each other's gaps (a backward pass or a rollout is
 one lane per problem: a chain of N dependent steps that leaves most of the chip idle once the active set has
 shrunk, exactly where another handle's cost kernels fit).  Every step is a complete, independent solve of
-the batch; `value` = problems solved / wall time of the K steps.  `one_handle` reports the same steps
-through one handle (half the memory), `single_batch` the strictly sequential call.
+the batch; `value` = problems solved / wall time of the K steps.
 
-Two extra legs on rank 0 at N = 1 (never `value`; `--no-extras` skips them): `pcie_inclusive` -- the same stream of batches with
+A plain run (`--gpus N --steps K --warmup W`) does only what `value` needs: it generates the scenes, sets up the pool,
+warms up, times the K steps, writes the last timed step's results when `--dump-outputs DIR` is given, and prints the
+line; every figure below that is not `value`, `ms_per_step` or the per-rank / host records of the timed region is null
+there.  `--full` adds everything else, each after the timed region: the calibration solve with HIP events around every
+phase (`breakdown_ms_per_step`, `roofline`), `one_handle` (the same steps through one handle, half the memory),
+`single_batch` (the strictly sequential call), the check that every solve in flight returned the same bits, the two
+extra legs, the C-ABI gather comparison of a multi-rank run, the drop-in latency section and the CPU baseline.
+
+`--dump-outputs DIR` (rank 0): DIR/<name>.npy, float64, of a fixed, seeded sample of the problems of the last timed step
+(at most 48 MiB in all): traj [n][K][10], cost_hist [n][max_iter+1][5] (rows >= n_cost zeroed: the library leaves them
+untouched in device memory), n_cost, status, n_iter [n], and problem_index [n], the sampled problems' rows in the batch.
+The inputs depend on the arguments only (cilqr_amd.scenario: one RNG stream per problem), so two builds can be compared
+output for output.
+
+Under `--full`, two extra legs on rank 0 at N = 1 (never `value`; `--no-extras` skips them): `pcie_inclusive` -- the same stream of batches with
 every input and output array in pageable HOST memory (CILQR_MEM_HOST through the pool: the library uploads the queued solve's
 arrays beside the solves and downloads the results ragged), compared bit for bit with the device-resident result -- and
 `end_to_end` -- obstacle points in HBM -> cilqr_build_corridors on a handle and stream of its own -> cilqr_pool_submit.
 Multi-rank runs carry `per_rank`, `host.cores_busy_per_rank` and `gather_verified_ranks` (a checksum check of what rank 0
 gathered); `--gather c_abi` lets cilqr_gather_results carry the per-step gather instead of torch.distributed.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement); with `--full` it fills two extra objects:
   roofline     backward-pass kernel, every launch of the timed region (time-weighted) and the launches
                that cover the whole batch: algorithmic bytes ((N*110+44)*8 B per problem
                per launch) / HIP-event time, against the 8 TB/s HBM peak; `achieved` and `frac` are quoted on the
@@ -113,6 +126,14 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=65536, help="problems per GPU")
     ap.add_argument("--scene", default="mix11")
     ap.add_argument("--seed", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure, after the timed region: calibration solve and "
+                         "per-phase breakdown, roofline (with the rocprofv3 traffic passes), one_handle, single_batch, the identical-results "
+                         "check, the extra legs, the C-ABI gather comparison, the latency section and the CPU baseline (the --no-* "
+                         "options and --cpu-sample / --cpu-configs below select among them); off: only what `value` needs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write a fixed, seeded sample of the last timed step's results to DIR/<name>.npy "
+                         "(float64, at most 48 MiB in all; rank 0)")
     ap.add_argument("--cpu-sample", type=int, default=3072, help="problems timed on the CPU oracle (0 = skip); 3072 scenes = about 15 s on one core")
     ap.add_argument("--cpu-configs", type=int, default=256, help="scenes per BASELINE config for the per-solve CPU statistics (0 = skip)")
     ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events")
@@ -239,7 +260,7 @@ def measure_backward_traffic(args, problem_steps_per_solve):
         solves = None
         for c in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, c)
-            cmd = ["rocprofv3", "--pmc", c, "-d", d, "--", sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "0",
+            cmd = ["rocprofv3", "--pmc", c, "-d", d, "--", sys.executable, os.path.abspath(__file__), "--full", "--steps", "1", "--warmup", "0",
                    "--in-flight", "1", "--pipeline", "1", "--cpu-sample", "0", "--no-latency", "--no-traffic", "--no-extras", "--batch", str(args.batch),
                    "--scene", args.scene, "--seed", str(args.seed), "--coarse", args.coarse]
             for flag, val in (("--compact-percent", args.compact_percent), ("--team-threshold", args.team_threshold),
@@ -277,7 +298,7 @@ def measure_backward_traffic(args, problem_steps_per_solve):
         return {"hbm_bytes_per_problem_step": hbm / (solves * problem_steps_per_solve), "solves_in_capture": int(solves),
                 "fetch_size_kib": sums["FETCH_SIZE"], "write_size_kib": sums["WRITE_SIZE"],
                 "full_batch_launch_hbm_bytes": (full["FETCH_SIZE"] * 2048.0 + full["WRITE_SIZE"] * 1024.0) if len(full) == 2 else None,
-                "method": "rocprofv3 --pmc FETCH_SIZE and, separately, --pmc WRITE_SIZE over `bench.py --steps 1 --warmup 0 --in-flight 1` "
+                "method": "rocprofv3 --pmc FETCH_SIZE and, separately, --pmc WRITE_SIZE over `bench.py --full --steps 1 --warmup 0 --in-flight 1` "
                           "of this workload; KiB; FETCH_SIZE x 2 (gfx950: 64 B tallied per 128 B request); k_backward + k_backward_team + "
                           "k_backward_wave dispatches"}
     except Exception:   # noqa: BLE001
@@ -587,6 +608,25 @@ def dry_run_multi(args, comm):
             "scene_workers_per_rank": scene_workers(world), "cpu_quota_cores": cpu_quota_cores(), "logical_cpus": os.cpu_count()}
 
 
+def dump_outputs(out_dir, sl, B, K, M, budget_bytes=48 << 20):
+    """--dump-outputs: the results of the last timed step (slot `sl`) of a fixed, seeded sample of the batch's problems, as
+    float64 .npy files; the whole batch when it fits in `budget_bytes`."""
+    import torch
+    per_problem = (K * 10 + (M + 1) * 5 + 4) * 8
+    n = min(B, max(1, budget_bytes // per_problem))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(20240611).choice(B, n, replace=False))
+    d_idx = torch.from_numpy(idx).to(sl.traj.device)
+    nc = sl.nc[d_idx].cpu().numpy()
+    hist = sl.hist[d_idx].cpu().numpy()
+    hist[np.arange(M + 1)[None, :] >= nc[:, None]] = 0.0     # rows past n_cost: untouched by the library in device memory
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"traj": sl.traj[d_idx].cpu().numpy(), "cost_hist": hist, "n_cost": nc, "status": sl.st[d_idx].cpu().numpy(),
+              "n_iter": sl.ni[d_idx].cpu().numpy(), "problem_index": idx}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    sys.stderr.write(f"bench.py: outputs of the last timed step, {n} of {B} problems, written to {out_dir}\n")
+
+
 def run(args, rank, local_rank, world, comm, real_stdout):
     """One rank: a process under a launcher (comm is None: torch.distributed over RCCL when world > 1) or a thread of --multi
     (comm: ThreadComm)."""
@@ -648,6 +688,7 @@ def run(args, rank, local_rank, world, comm, real_stdout):
     smax = max(sc["left"].shape[0], sc["right"].shape[0])
     P = max(1, args.pipeline)
     D = args.in_flight
+    profiled = args.full and not args.no_profile     # HIP events feed the breakdown and the roofline only (--full)
 
     d_start = torch.from_numpy(sc["start"]).to(dev)
     d_coarse = torch.from_numpy(sc["coarse"]).to(dev)
@@ -784,9 +825,13 @@ def run(args, rank, local_rank, world, comm, real_stdout):
             raise api.CilqrError(rc, "in bench step")
         if through_pool:
             dealt[1] += 1
-        return sl, ((pool.profile() if through_pool else c.opt.profile()) if not args.no_profile else None)
+        return sl, ((pool.profile() if through_pool else c.opt.profile()) if profiled else None)
+
+    last_timed = [None]   # the slot of the last timed step (steps finish oldest first)
 
     def finish(c, sl, p, timed):
+        if timed:
+            last_timed[0] = sl
         if timed and p is not None:
             prof_acc["bwd_ms"] += p.backward_ms
             prof_acc["bwd_launches"] += p.backward_launches
@@ -836,14 +881,14 @@ def run(args, rank, local_rank, world, comm, real_stdout):
             comm.barrier()
         torch.cuda.synchronize()
 
-    # One step alone on one handle, with HIP events around every phase of every lockstep iteration:
-    # the per-phase breakdown, the single-batch (un-pipelined) time and the un-overlapped duration of
-    # the full-batch backward launch.  Untimed (part of the warm-up).
+    # One untimed solve on one handle (part of the warm-up); with --full a second one with HIP events around every phase of
+    # every lockstep iteration: the per-phase breakdown, the single-batch (un-pipelined) time and the un-overlapped
+    # duration of the full-batch backward launch.
     single = None
-    if not args.no_profile:
-        rc = opt.solve_raw(prob, ctx[0].sol)   # first solve of the process: code objects, scratch and staging get allocated
-        if rc != api.OK:
-            raise api.CilqrError(rc, "in the first solve")
+    rc = opt.solve_raw(prob, ctx[0].sol)   # first solve of the process: code objects, scratch and staging get allocated
+    if rc != api.OK:
+        raise api.CilqrError(rc, "in the first solve")
+    if profiled:
         opt.set_profiling(1)
         rc = opt.solve_raw(prob, ctx[0].sol)
         if rc != api.OK:
@@ -866,6 +911,8 @@ def run(args, rank, local_rank, world, comm, real_stdout):
     run_steps(args.steps, True)
     fence()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_timed[0], B, K, M)
     # host CPU of the timed region: what one rank's threads -- the loop, the handles' solver workers, the
     # gather thread, RCCL's proxy -- burn per step, so that N ranks can be budgeted against the box's CPU quota
     cpu_rank = cpu_seconds() - cpu0
@@ -935,7 +982,7 @@ def run(args, rank, local_rank, world, comm, real_stdout):
     # by a watchdog: a multi-rank send / recv cannot be rehearsed on a 1-GPU box.
     cabi = None
     hung = False
-    if use_rccl and args.gather == "c_abi":
+    if use_rccl and args.full and args.gather == "c_abi":
         # the timed region went through cilqr_gather_results: the torch.distributed gather of the same (last) step beside it
         from cilqr_amd.distributed import gather_results as torch_gather
         sl_ = last_gather[-1]
@@ -951,7 +998,7 @@ def run(args, rank, local_rank, world, comm, real_stdout):
                 and torch.equal(g_["cost_hist"][torch.arange(M + 1, device=dev)[None, :] < g_["n_cost"][:, None].long()], tg["hist_rows"])
                 and bool(torch.allclose(g_["traj"][:, :, 7], tg["traj"][:, :, 7], rtol=1e-15, atol=0.0)))
             cabi["rank0_block_identical_to_local"] = bool(torch.equal(g_["traj"][:B], sl_.traj))
-    elif use_rccl:
+    elif use_rccl and args.full:
         import threading
         res = {}
 
@@ -1005,7 +1052,7 @@ def run(args, rank, local_rank, world, comm, real_stdout):
 
     # the same steps through ONE of the handles (two solves in flight on it): what a caller with one handle's memory gets
     one_handle = None
-    if world == 1 and P > 1:
+    if world == 1 and P > 1 and args.full:
         run_steps(min(args.warmup, 4), False, ctx[0])
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -1016,7 +1063,7 @@ def run(args, rank, local_rank, world, comm, real_stdout):
                       "batches_in_flight": D, "device_bytes": ctx[0].opt.device_bytes()}
     # sequential form: two more steps back to back on one handle, no events
     seq = None
-    if world == 1 and P * D > 1:
+    if world == 1 and P * D > 1 and args.full:
         opt.set_profiling(0)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -1025,14 +1072,15 @@ def run(args, rank, local_rank, world, comm, real_stdout):
                 raise api.CilqrError(-1, "in sequential step")
         torch.cuda.synchronize()
         seq = (time.perf_counter() - t1) / 2
-    same = all(bool(torch.equal(sl.traj, ctx[0].traj)) and bool(torch.equal(sl.nc, ctx[0].nc)) and
-               bool(torch.equal(sl.st, ctx[0].st)) and bool(torch.equal(sl.ni, ctx[0].ni)) for c in ctx for sl in c.slots if sl.used)
+    same = (all(bool(torch.equal(sl.traj, ctx[0].traj)) and bool(torch.equal(sl.nc, ctx[0].nc)) and
+                bool(torch.equal(sl.st, ctx[0].st)) and bool(torch.equal(sl.ni, ctx[0].ni)) for c in ctx for sl in c.slots if sl.used)
+            if args.full else None)
 
     # ---- Extra legs (never `value`): what a caller sees whose arrays are not already in HBM ("report both with
     # and without transfers").  Both run through the same pool as the timed region, with as many solves
     # submitted as it takes (cilqr_pool_depth: two in flight and one queued per handle).
     dev_bytes_timed = sum(c.opt.device_bytes() for c in ctx)      # (before the extra legs grow the host-array staging)
-    extras = world == 1 and not args.no_extras
+    extras = world == 1 and args.full and not args.no_extras
     n_extra = args.extra_steps if args.extra_steps > 0 else min(args.steps, 24)
     depth = pool.depth()
 
@@ -1199,10 +1247,10 @@ def run(args, rank, local_rank, world, comm, real_stdout):
                 pass
 
     traffic = None
-    if world == 1 and not args.no_traffic and not args.no_profile and single and single["bwd_problem_steps"] > 0:
+    if world == 1 and not args.no_traffic and profiled and single and single["bwd_problem_steps"] > 0:
         traffic = measure_backward_traffic(args, single["bwd_problem_steps"])
     latency = None
-    if world == 1 and not args.no_latency:
+    if world == 1 and args.full and not args.no_latency:
         latency = plan_latency(scenario, ("ped6", "mix11", "dyn20"), args.latency_scenes, 100 + args.seed, workers)
 
     # sanity: every problem must have terminated with a valid status
@@ -1214,7 +1262,7 @@ def run(args, rank, local_rank, world, comm, real_stdout):
         ms_per_step = 1e3 * elapsed / args.steps
         value = world * B * args.steps / elapsed
         roof = None
-        if not args.no_profile and prof_acc["bwd_ms"] > 0:
+        if profiled and prof_acc["bwd_ms"] > 0:
             # ALGORITHMIC bytes: a launch over n problems moves n*(N*110+44)*8 B dense.
             # One solve launches the backward kernel once per lockstep iteration, over 65536 problems at
             # first and over a few stragglers at the end.  The top level aggregates ALL launches of the
@@ -1345,7 +1393,7 @@ def run(args, rank, local_rank, world, comm, real_stdout):
                             "region, where other batches' kernels share the GPU",
                 }
         cpu = None
-        if args.cpu_sample > 0 and world == 1:   # rank 0 at N = 1 only
+        if args.full and args.cpu_sample > 0 and world == 1:   # rank 0 at N = 1 only
             from oracle import oracle as orc
 
             def ocfg_for(n_steps):

@@ -312,7 +312,8 @@ def test_bench_distributed_paths_on_one_gpu():
     rank census, the per-step gather through the gather thread and cilqr_gather_results, all with one rank; (b) --multi with
     both "GPUs" mapped onto device 0: two threads, two pools, peer-copy gather.  Each prints one line; (b) reports n_gpus 2."""
     bench = os.path.join(ROOT, "bench.py")
-    common = ["--batch", "2048", "--steps", "6", "--warmup", "2", "--no-traffic", "--no-latency", "--cpu-sample", "0", "--cpu-configs", "0"]
+    common = ["--full", "--batch", "2048", "--steps", "6", "--warmup", "2", "--no-traffic", "--no-latency", "--cpu-sample", "0",
+              "--cpu-configs", "0"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, bench] + common, env=dict(env, CILQR_BENCH_FORCE_DIST="1", MASTER_PORT="29551"),
                        capture_output=True, text=True, timeout=600)
@@ -396,12 +397,12 @@ def build_corridor_adapter_test(tmp_path, types="stand-ins"):
 
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_fields_on_the_gpu():
-    """`python bench.py` (small batch, a few steps) on the GPU box: ONE JSON line with the fields the driver reads -- metric,
+    """`python bench.py --full` (small batch, a few steps) on an MI355X: ONE JSON line with the contract fields -- metric,
     value, n_gpus, steps, ms_per_step, dtype, config.workload -- the roofline object (bound / achieved / peak / unit / frac /
     traffic) and the cpu_baseline object (value / unit / cores / kind / sample); the timed steps went through the pool of two
     handles and every solve in flight returned the same bits."""
     bench = os.path.join(ROOT, "bench.py")
-    r = subprocess.run([sys.executable, bench, "--batch", "2048", "--steps", "7", "--warmup", "2", "--no-traffic", "--no-latency",
+    r = subprocess.run([sys.executable, bench, "--full", "--batch", "2048", "--steps", "7", "--warmup", "2", "--no-traffic", "--no-latency",
                         "--cpu-sample", "64", "--cpu-configs", "0"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     rec = _one_json_line(r.stdout)
@@ -431,6 +432,38 @@ def test_bench_line_has_the_contract_fields_on_the_gpu():
     assert rec["pcie_inclusive"]["value"] > 0 and rec["pcie_inclusive"]["identical_to_device_resident"] is True
     assert rec["end_to_end"]["value"] > 0 and rec["end_to_end"]["identical_across_steps_and_to_the_sequential_call"] is True
     assert rec["end_to_end"]["corridors_failed"] == 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_the_same_outputs(tmp_path):
+    """A plain `python bench.py` times its steps and prints the contract fields, nothing else (every --full figure null);
+    --dump-outputs writes the last timed step's results as float64 .npy files within 64 MiB, and two runs with other step
+    counts dump the same bits (the inputs depend on the arguments only, every step is the same solve)."""
+    import numpy as np
+    bench = os.path.join(ROOT, "bench.py")
+    dumps = []
+    for steps, warmup in ((3, 1), (2, 2)):
+        d = tmp_path / f"out_{steps}"
+        r = subprocess.run([sys.executable, bench, "--batch", "2048", "--steps", str(steps), "--warmup", str(warmup),
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        rec = _one_json_line(r.stdout)
+        assert rec["steps"] == steps and rec["warmup"] == warmup and rec["value"] > 0 and rec["dtype"] == "f64"
+        assert rec["unit"] == "solves/s" and rec["higher_is_better"] is True
+        assert abs(rec["value"] - 2048 * 1e3 / rec["ms_per_step"]) <= 1e-3 * rec["value"]
+        for key in ("roofline", "cpu_baseline", "single_batch", "one_handle", "pcie_inclusive", "end_to_end", "latency",
+                    "breakdown_ms_per_step", "results_identical_across_solves_in_flight", "c_abi_gather"):
+            assert rec[key] is None, key
+        files = sorted(os.listdir(d))
+        assert files == sorted(n + ".npy" for n in ("traj", "cost_hist", "n_cost", "status", "n_iter", "problem_index")), files
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        assert arrs["traj"].shape[0] == arrs["problem_index"].shape[0] == 2048 and arrs["traj"].shape[2] == 10
+        assert ((arrs["status"] >= 1) & (arrs["status"] <= 5)).all() and (arrs["n_cost"] >= 1).all()
+        dumps.append(arrs)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 def test_header_is_plain_c99_and_the_pool_calls_link(built, tmp_path):
