@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "dev_model.hpp"
@@ -207,45 +208,26 @@ __global__ void k_unpack_rows(const double* __restrict__ rows, const int* __rest
   }
 }
 
-int grow_dev(void** p, size_t* have, size_t need) {
-  if (need <= *have) return CILQR_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *have = 0;
-  need += need / 8;
-  HIP_TRY(hipMalloc(p, need));
-  *have = need;
-  return CILQR_OK;
-}
-
 }  // namespace
 
 struct cilqr_comm {
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1;
-  void* send = nullptr;     // this rank's payload
-  size_t send_bytes = 0;
-  void* recv = nullptr;     // root: the payloads of all ranks, back to back
-  size_t recv_bytes = 0;
-  long long* off = nullptr;       // [capacity] row offsets
-  // device: (live rows, batch) of every rank [2 p], of this rank [2 world], the root's verdict [2 world + 2]
-  long long* totals = nullptr;
-  long long* h_totals = nullptr;  // pinned copy
-  size_t off_cap = 0;
-  int agreed_batch = -1;          // the batch every rank was seen to hold (first use, and whenever this rank's changes)
+  dev_mem send;             // this rank's payload
+  dev_mem recv;             // root: the payloads of all ranks, back to back
+  dev_mem off;              // long long [batch * world] row offsets
+  // long long, device: (live rows, batch) of every rank [2 p], of this rank [2 world], the root's verdict [2 world + 2]
+  dev_mem totals;
+  pinned_mem h_totals;      // its host copy
+  int agreed_batch = -1;    // the batch every rank was seen to hold (first use, and whenever this rank's changes)
+  ~cilqr_comm() {           // (the communicator goes before the buffers it may still use)
+    Rccl* R = rccl();
+    if (comm && R) (void)R->CommDestroy(comm);
+  }
 };
 
 void cilqr_comm_release(cilqr_solver* h) {
-  cilqr_comm* c = h->comm;
-  if (c == nullptr) return;
-  Rccl* R = rccl();
-  if (c->comm && R) (void)R->CommDestroy(c->comm);
-  if (c->send) (void)hipFree(c->send);
-  if (c->recv) (void)hipFree(c->recv);
-  if (c->off) (void)hipFree(c->off);
-  if (c->totals) (void)hipFree(c->totals);
-  if (c->h_totals) (void)hipHostFree(c->h_totals);
-  delete c;
+  delete h->comm;
   h->comm = nullptr;
 }
 
@@ -275,22 +257,20 @@ int cilqr_comm_create(cilqr_handle h, const uint8_t* id, int32_t rank, int32_t w
     return CILQR_ERR_DEVICE;
   }
   HIP_TRY(hipSetDevice(h->device));
-  cilqr_comm* c = new (std::nothrow) cilqr_comm();
+  std::unique_ptr<cilqr_comm> c(new (std::nothrow) cilqr_comm());
   if (c == nullptr) return CILQR_ERR_DEVICE;
   c->rank = rank;
   c->world = world;
   ncclUniqueId u;
   std::memcpy(u.internal, id, CILQR_UNIQUE_ID_BYTES);
-  h->comm = c;
   ncclResult_t r_ = R->CommInitRank(&c->comm, world, u, rank);
-  if (r_ != ncclSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&c->totals), (size_t)(4 * world + 8) * sizeof(long long)) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&c->h_totals), (size_t)(4 * world + 8) * sizeof(long long), hipHostMallocDefault) != hipSuccess) {
+  const size_t n_totals = (size_t)(4 * world + 8) * sizeof(long long);
+  if (r_ != ncclSuccess || c->totals.alloc(n_totals) != hipSuccess || c->h_totals.alloc(n_totals) != hipSuccess) {
     std::snprintf(g_last_hip_error, sizeof(g_last_hip_error), "ncclCommInitRank(rank %d of %d) -> %s", rank, world,
                   (r_ != ncclSuccess && R->GetErrorString) ? R->GetErrorString(r_) : "allocation failed");
-    cilqr_comm_release(h);
     return CILQR_ERR_DEVICE;
   }
+  h->comm = c.release();
   return CILQR_OK;
 }
 
@@ -334,22 +314,19 @@ int cilqr_gather_results(cilqr_handle h, int32_t batch, const cilqr_solution_bat
   hipStream_t st = h->stream;
   const int B = batch, K = h->cfg.n_steps + 1, M1 = h->cfg.max_iter + 1, W = c->world;
   const size_t nb = (size_t)(B + 255) / 256;
-  if ((size_t)B * (size_t)W > c->off_cap) {
-    if (c->off) HIP_TRY(hipFree(c->off));
-    c->off = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->off), (size_t)B * W * sizeof(long long)));
-    c->off_cap = (size_t)B * W;
-  }
+  HIP_TRY(c->off.grow((size_t)B * W * sizeof(long long)));
+  long long* off = c->off.as<long long>();
+  long long* h_totals = c->h_totals.as<long long>();
   // device scalars: [0, W) live rows of every rank (root), [W] this rank's, [W + 1] verdict, [W + 2 ...] the agreement exchange
-  long long* rows_of = c->totals;
-  long long* own_total = c->totals + W;
-  long long* verdict = c->totals + W + 1;
+  long long* rows_of = c->totals.as<long long>();
+  long long* own_total = rows_of + W;
+  long long* verdict = rows_of + W + 1;
   // 0. first use (or another batch than last time): every rank tells the root its batch, the root answers with a verdict --
   //    before anything is sized from that number, so that a rank that holds another batch is an error on every rank
   if (W > 1 && c->agreed_batch != B) {
-    long long* said = c->totals + W + 2;         // [W] on the root, [0] elsewhere
-    c->h_totals[0] = B;
-    HIP_TRY(hipMemcpyAsync(said + c->rank % W, c->h_totals, sizeof(long long), hipMemcpyHostToDevice, st));
+    long long* said = rows_of + W + 2;           // [W] on the root, [0] elsewhere
+    h_totals[0] = B;
+    HIP_TRY(hipMemcpyAsync(said + c->rank % W, h_totals, sizeof(long long), hipMemcpyHostToDevice, st));
     NCCL_TRY(R->GroupStart());
     if (is_root) {
       for (int p = 0; p < W; ++p)
@@ -360,12 +337,12 @@ int cilqr_gather_results(cilqr_handle h, int32_t batch, const cilqr_solution_bat
     NCCL_TRY(R->GroupEnd());
     long long ok0 = 1;
     if (is_root) {
-      HIP_TRY(hipMemcpyAsync(c->h_totals, said, (size_t)W * sizeof(long long), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(h_totals, said, (size_t)W * sizeof(long long), hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
       for (int p = 0; p < W; ++p)
-        if (p != root && c->h_totals[p] != B) ok0 = 0;
-      c->h_totals[W] = ok0;
-      HIP_TRY(hipMemcpyAsync(verdict, c->h_totals + W, sizeof(long long), hipMemcpyHostToDevice, st));
+        if (p != root && h_totals[p] != B) ok0 = 0;
+      h_totals[W] = ok0;
+      HIP_TRY(hipMemcpyAsync(verdict, h_totals + W, sizeof(long long), hipMemcpyHostToDevice, st));
     }
     NCCL_TRY(R->GroupStart());
     if (is_root) {
@@ -376,9 +353,9 @@ int cilqr_gather_results(cilqr_handle h, int32_t batch, const cilqr_solution_bat
     }
     NCCL_TRY(R->GroupEnd());
     if (!is_root) {
-      HIP_TRY(hipMemcpyAsync(c->h_totals + W, verdict, sizeof(long long), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(h_totals + W, verdict, sizeof(long long), hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
-      ok0 = c->h_totals[W];
+      ok0 = h_totals[W];
     }
     if (ok0 != 1) {
       std::snprintf(g_last_hip_error, sizeof(g_last_hip_error), "cilqr_gather_results: the ranks do not hold the same batch");
@@ -390,29 +367,28 @@ int cilqr_gather_results(cilqr_handle h, int32_t batch, const cilqr_solution_bat
   const long long cap = std::min<long long>((long long)B * M1, (long long)B * 32);
   const size_t n_traj8 = (size_t)B * K * kTravelCols, n_ints = (size_t)3 * B;
   const size_t block = 4 + n_traj8 + n_ints + (size_t)cap * CILQR_COST_FIELDS;
-  int rc = grow_dev(&c->send, &c->send_bytes, block * sizeof(double));
-  if (rc != CILQR_OK) return rc;
-  double* sp = static_cast<double*>(c->send);
+  // (the message buffers grow with 1/8 of headroom)
+  const size_t send_bytes = block * sizeof(double), recv_bytes = (size_t)(W - 1) * send_bytes;
+  if (send_bytes > c->send.bytes()) HIP_TRY(c->send.grow(send_bytes + send_bytes / 8));
+  double* sp = c->send.as<double>();
   double* s_traj = sp + 4;
   double* s_ints = s_traj + n_traj8;
   double* s_rows = s_ints + n_ints;
-  hipLaunchKernelGGL(k_row_offsets, dim3(1), dim3(1024), 0, st, local->n_cost, B, c->off, own_total);
+  hipLaunchKernelGGL(k_row_offsets, dim3(1), dim3(1024), 0, st, local->n_cost, B, off, own_total);
   hipLaunchKernelGGL(k_pack_header, dim3(1), dim3(64), 0, st, own_total, B, c->rank, M1, sp);
   hipLaunchKernelGGL(k_pack_traj, dim3(((size_t)B * K + 255) / 256), dim3(256), 0, st, local->traj, B, K, s_traj);
   hipLaunchKernelGGL(k_pack_rows, dim3(nb), dim3(256), 0, st, local->cost_hist, local->n_cost, local->status,
-                     local->n_iter, c->off, B, M1, 0LL, cap, s_rows, s_ints);
+                     local->n_iter, off, B, M1, 0LL, cap, s_rows, s_ints);
   HIP_TRY(hipGetLastError());
   // 2. the gather: one message per rank, straight into the root (block p of the receive buffer: rank p, the root's own skipped)
   auto slot_of = [&](int p) { return (size_t)(p - (p > root ? 1 : 0)); };
-  if (is_root && W > 1) {
-    rc = grow_dev(&c->recv, &c->recv_bytes, (size_t)(W - 1) * block * sizeof(double));
-    if (rc != CILQR_OK) return rc;
-  }
+  if (is_root && recv_bytes > c->recv.bytes()) HIP_TRY(c->recv.grow(recv_bytes + recv_bytes / 8));
+  double* recv = c->recv.as<double>();
   if (W > 1) {
     NCCL_TRY(R->GroupStart());
     if (is_root) {
       for (int p = 0; p < W; ++p)
-        if (p != root) NCCL_TRY_G(R->Recv(static_cast<double*>(c->recv) + slot_of(p) * block, block, ncclFloat64, p, c->comm, st));
+        if (p != root) NCCL_TRY_G(R->Recv(recv + slot_of(p) * block, block, ncclFloat64, p, c->comm, st));
     } else {
       NCCL_TRY_G(R->Send(sp, block, ncclFloat64, root, c->comm, st));
     }
@@ -420,10 +396,10 @@ int cilqr_gather_results(cilqr_handle h, int32_t batch, const cilqr_solution_bat
   }
   // 3. unpack on the root, blocks in rank order (everything sized on the device: no host round trip in between)
   auto unpack = [&](int p, const double* rows, long long lo, long long hi, bool all) {
-    const double* src = (p == root) ? sp : static_cast<const double*>(c->recv) + slot_of(p) * block;
+    const double* src = (p == root) ? sp : recv + slot_of(p) * block;
     const size_t b0 = (size_t)p * B;
     int* g_nc = gathered->n_cost + b0;
-    long long* off_p = c->off + b0;
+    long long* off_p = off + b0;
     if (all) {
       hipLaunchKernelGGL(k_unpack_ints, dim3(nb), dim3(256), 0, st, src + 4 + n_traj8, B, g_nc, gathered->status + b0,
                          gathered->n_iter ? gathered->n_iter + b0 : nullptr);
@@ -435,16 +411,16 @@ int cilqr_gather_results(cilqr_handle h, int32_t batch, const cilqr_solution_bat
                        lo, hi, gathered->cost_hist + b0 * M1 * CILQR_COST_FIELDS);
   };
   if (is_root) {
-    hipLaunchKernelGGL(k_check_headers, dim3(1), dim3(64), 0, st, sp, static_cast<const double*>(c->recv), block, W, root, B, M1,
+    hipLaunchKernelGGL(k_check_headers, dim3(1), dim3(64), 0, st, sp, recv, block, W, root, B, M1,
                        rows_of, verdict);
     for (int p = 0; p < W; ++p) unpack(p, nullptr, 0LL, cap, true);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_totals, c->totals, (size_t)(W + 2) * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_totals, rows_of, (size_t)(W + 2) * sizeof(long long), hipMemcpyDeviceToHost, st));
   } else {
-    HIP_TRY(hipMemcpyAsync(c->h_totals + W, own_total, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_totals + W, own_total, sizeof(long long), hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipStreamSynchronize(st));      // the one host synchronisation of a gather
-  if (is_root && c->h_totals[W + 1] != 1) {
+  if (is_root && h_totals[W + 1] != 1) {
     std::snprintf(g_last_hip_error, sizeof(g_last_hip_error), "cilqr_gather_results: a rank's message does not carry this batch");
     return CILQR_ERR_ARG;
   }
@@ -452,22 +428,22 @@ int cilqr_gather_results(cilqr_handle h, int32_t batch, const cilqr_solution_bat
   //    know from the same number (the sender its own total, the root the headers')
   bool more = false;
   if (is_root) {
-    for (int p = 0; p < W; ++p) more = more || c->h_totals[p] > cap;
+    for (int p = 0; p < W; ++p) more = more || h_totals[p] > cap;
   } else {
-    more = c->h_totals[W] > cap;
+    more = h_totals[W] > cap;
   }
   if (more) {
-    const long long own_more = std::max<long long>(0, (is_root ? c->h_totals[root] : c->h_totals[W]) - cap);
+    const long long own_more = std::max<long long>(0, (is_root ? h_totals[root] : h_totals[W]) - cap);
     std::vector<size_t> at(W + 1, 0);
     if (is_root)
-      for (int p = 0; p < W; ++p) at[p + 1] = at[p] + (size_t)std::max<long long>(0, c->h_totals[p] - cap) * CILQR_COST_FIELDS;
-    void* extra = nullptr;      // (a path for unusual batches: allocated and freed here)
+      for (int p = 0; p < W; ++p) at[p + 1] = at[p] + (size_t)std::max<long long>(0, h_totals[p] - cap) * CILQR_COST_FIELDS;
+    dev_mem extra;              // (a path for unusual batches: allocated and freed here)
     const size_t extra_doubles = is_root ? at[W] : (size_t)own_more * CILQR_COST_FIELDS;
-    HIP_TRY(hipMalloc(&extra, (extra_doubles + 1) * sizeof(double)));
-    double* ex = static_cast<double*>(extra);
+    HIP_TRY(extra.alloc((extra_doubles + 1) * sizeof(double)));
+    double* ex = extra.as<double>();
     if (own_more > 0)
       hipLaunchKernelGGL(k_pack_rows, dim3(nb), dim3(256), 0, st, local->cost_hist, local->n_cost, local->status, local->n_iter,
-                         c->off + (is_root ? (size_t)root * B : 0), B, M1, cap, cap + own_more, ex + (is_root ? at[root] : 0),
+                         off + (is_root ? (size_t)root * B : 0), B, M1, cap, cap + own_more, ex + (is_root ? at[root] : 0),
                          static_cast<double*>(nullptr));
     ncclResult_t gr = R->GroupStart();
     if (gr == ncclSuccess) {
@@ -482,9 +458,9 @@ int cilqr_gather_results(cilqr_handle h, int32_t batch, const cilqr_solution_bat
     }
     if (gr == ncclSuccess && is_root)
       for (int p = 0; p < W; ++p)
-        if (at[p + 1] > at[p]) unpack(p, ex + at[p], cap, c->h_totals[p], false);
+        if (at[p + 1] > at[p]) unpack(p, ex + at[p], cap, h_totals[p], false);
     const hipError_t se = hipStreamSynchronize(st);
-    (void)hipFree(extra);
+    extra.reset();
     if (gr != ncclSuccess || se != hipSuccess) {
       std::snprintf(g_last_hip_error, sizeof(g_last_hip_error), "cilqr_gather_results: the exchange of the rows beyond the region failed");
       return CILQR_ERR_DEVICE;

@@ -16,6 +16,7 @@
 #include <thread>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -31,33 +32,18 @@ thread_local char g_last_hip_error[256] = "";
 namespace {
 
 template <typename T>
-int dev_alloc(cilqr_solver* h, T** p, size_t count) {
-  void* q = nullptr;
+hipError_t dev_alloc(cilqr_solver* h, T** p, size_t count) {
   const size_t bytes = count * sizeof(T);
-  HIP_TRY(hipMalloc(&q, bytes ? bytes : 256));
-  h->allocs.push_back(q);
+  dev_mem m;
+  if (const hipError_t e = m.alloc(bytes ? bytes : 256)) return e;
+  *p = m.as<T>();
+  h->allocs.push_back(std::move(m));
   h->bytes += (int64_t)bytes;
-  *p = static_cast<T*>(q);
-  return CILQR_OK;
+  return hipSuccess;
 }
 
 constexpr int64_t kTailMaxProblems = 8192;
 constexpr size_t kSmallTransfer = (size_t)4 << 20;   // host batches up to this many bytes travel as one pinned block each way   // CILQR_OPT_TAIL_THRESHOLD is clamped to this
-
-// the lazily grown blocks of a handle (staging, tail workspaces).  Their sizes are owned by the thread that grows them;
-// what another thread may ask for at any time -- cilqr_device_bytes -- is the atomic sum kept beside them (found by the
-// ThreadSanitizer run of tools/tsan_run.sh: the sizes themselves used to be read there)
-int grow(cilqr_solver* h, void** p, size_t* have, size_t need) {
-  if (need <= *have) return CILQR_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  h->grown_bytes.fetch_sub((int64_t)*have, std::memory_order_relaxed);
-  *have = 0;
-  HIP_TRY(hipMalloc(p, need));
-  *have = need;
-  h->grown_bytes.fetch_add((int64_t)need, std::memory_order_relaxed);
-  return CILQR_OK;
-}
 
 void fill_params(const cilqr_config& c, Params* p) {
   std::memset(p, 0, sizeof(*p));
@@ -114,18 +100,6 @@ DeviceState main_view(const cilqr_solver* h, const cilqr_job_set& js) {
   return v;
 }
 
-// pinned host blocks of a job set, grown like the device blocks (never while a copy into them is in flight: the solve that
-// owns the set is the only user)
-int grow_pinned(void** p, size_t* have, size_t need) {
-  if (need <= *have) return CILQR_OK;
-  if (*p) HIP_TRY(hipHostFree(*p));
-  *p = nullptr;
-  *have = 0;
-  HIP_TRY(hipHostMalloc(p, need, hipHostMallocDefault));
-  *have = need;
-  return CILQR_OK;
-}
-
 // Host arrays travel on two streams of the handle's own, created when the first large host batch shows up: HIP maps streams
 // onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 unless the environment says otherwise) in the order they are created, and a
 // handle that only ever sees device arrays should not spend queues on streams it never uses (round 3 measured what two
@@ -133,8 +107,8 @@ int grow_pinned(void** p, size_t* have, size_t need) {
 // instead of 2.00 M solves/s -- not reproduced once they existed lazily, r06 log 2).
 int io_streams(cilqr_solver* h) {
   std::lock_guard<std::mutex> lk(h->io_mu);
-  if (h->stream_in == nullptr) HIP_TRY(hipStreamCreateWithFlags(&h->stream_in, hipStreamNonBlocking));
-  if (h->stream_out == nullptr) HIP_TRY(hipStreamCreateWithFlags(&h->stream_out, hipStreamNonBlocking));
+  if (h->stream_in.get() == nullptr) HIP_TRY(h->stream_in.create(hipStreamNonBlocking));
+  if (h->stream_out.get() == nullptr) HIP_TRY(h->stream_out.create(hipStreamNonBlocking));
   return CILQR_OK;
 }
 
@@ -149,7 +123,7 @@ int acquire_in_buffer(cilqr_solver* h, bool block) {
       const bool wait_loaded = b.state == 2;
       b.state = 1;
       lk.unlock();
-      if (wait_loaded && hipEventSynchronize(b.loaded) != hipSuccess) return -2;
+      if (wait_loaded && hipEventSynchronize(b.loaded.get()) != hipSuccess) return -2;
       return k;
     }
     if (!block || h->quit) return -1;
@@ -158,7 +132,7 @@ int acquire_in_buffer(cilqr_solver* h, bool block) {
 }
 void release_in_buffer(cilqr_solver* h, int k, hipStream_t st) {   // behind the kernels on `st` that read it
   if (k < 0) return;
-  const bool recorded = hipEventRecord(h->in_bufs[k].loaded, st) == hipSuccess;
+  const bool recorded = hipEventRecord(h->in_bufs[k].loaded.get(), st) == hipSuccess;
   {
     std::lock_guard<std::mutex> lk(h->mu);
     h->in_bufs[k].state = recorded ? 2 : 0;
@@ -190,27 +164,25 @@ int stage_inputs(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_in_buffer
     const size_t payload = (n_start + n_coarse + n_cor + n_sta) * sizeof(double) + n_cnt * sizeof(int);
     // (a small batch lands in a block of its own: it is staged by the solving thread on the solve's stream, so the next
     // small batch's copy is ordered behind this one's load kernels by the stream itself)
-    if (payload > kSmallTransfer && ib == nullptr) return CILQR_ERR_STATE;
-    const int g = payload <= kSmallTransfer ? grow(h, &h->in_small, &h->in_small_bytes, kSmallTransfer + 1024) : grow(h, &ib->p, &ib->bytes, bytes);
-    if (g != CILQR_OK) return g;
-    double* d = static_cast<double*>(payload <= kSmallTransfer ? h->in_small : ib->p);
-    if (payload <= kSmallTransfer) {
+    const bool small = payload <= kSmallTransfer;
+    if (!small && ib == nullptr) return CILQR_ERR_STATE;
+    dev_mem& block = small ? h->in_small : ib->p;
+    HIP_TRY(block.grow(small ? kSmallTransfer + 1024 : bytes, &h->grown_bytes));
+    double* d = block.as<double>();
+    if (small) {
       // a small batch (the drop-in call is a batch of one): the five arrays go through ONE pinned block and ONE copy --
       // five pageable copies cost ~10 us each before the first kernel can start
-      if (h->in_pinned == nullptr) {
-        HIP_TRY(hipHostMalloc(&h->in_pinned, kSmallTransfer, hipHostMallocDefault));
-        HIP_TRY(hipEventCreateWithFlags(&h->in_pinned_ev, hipEventDisableTiming));
-      } else {
-        HIP_TRY(hipEventSynchronize(h->in_pinned_ev));   // the previous load's copy has left the block
-      }
-      char* q = static_cast<char*>(h->in_pinned);
+      if (h->in_pinned.get() == nullptr) HIP_TRY(h->in_pinned.alloc(kSmallTransfer));
+      if (h->in_pinned_ev.get() == nullptr) HIP_TRY(h->in_pinned_ev.create());
+      else HIP_TRY(hipEventSynchronize(h->in_pinned_ev.get()));   // the previous load's copy has left the block
+      char* q = h->in_pinned.as<char>();
       std::memcpy(q, in->start, n_start * 8); q += n_start * 8;
       std::memcpy(q, in->coarse, n_coarse * 8); q += n_coarse * 8;
       std::memcpy(q, in->corridor, n_cor * 8); q += n_cor * 8;
       if (want_station) { std::memcpy(q, in->coarse_station, n_sta * 8); q += n_sta * 8; }
       std::memcpy(q, in->corridor_count, n_cnt * 4);
-      HIP_TRY(hipMemcpyAsync(d, h->in_pinned, payload, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipEventRecord(h->in_pinned_ev, st));
+      HIP_TRY(hipMemcpyAsync(d, h->in_pinned.get(), payload, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipEventRecord(h->in_pinned_ev.get(), st));
       pv.start = d; d += n_start;
       pv.coarse = d; d += n_coarse;
       pv.corridor = d; d += n_cor;
@@ -385,11 +357,11 @@ int wait_stream(hipStream_t st, hipEvent_t scratch, bool relaxed) {
 bool cilqr_timer::on() const { return h->profiling; }
 bool cilqr_timer::wants(int k) const { return h->profiling && (h->profiling_level != 2 || k == 1); }   // level 2: the backward launches only
 int cilqr_timer::reserve() {
-  if (next + 2 > js->ev.size()) {
-    const size_t old = js->ev.size();
-    js->ev.resize(old + 64);
-    for (size_t i = old; i < js->ev.size(); ++i)
-      if (hipEventCreate(&js->ev[i]) != hipSuccess) return -1;
+  if (next + 2 <= js->ev.size()) return 0;
+  for (int k = 0; k < 64; ++k) {   // (an event joins the list once it exists)
+    hip_event e;
+    if (e.create_timed() != hipSuccess) return -1;
+    js->ev.push_back(std::move(e));
   }
   return 0;
 }
@@ -434,7 +406,7 @@ int cilqr_timer::begin(int k) {
   if (!open) return 0;
   if (reserve()) return -1;
   kind.push_back(k);
-  return hipEventRecord(js->ev[next++], stream) == hipSuccess ? 0 : -1;
+  return hipEventRecord(js->ev[next++].get(), stream) == hipSuccess ? 0 : -1;
 }
 // an event pair for a kernel that stamps its own start and end (hipExtLaunchKernelGGL); nullptrs when off
 int cilqr_timer::pair(int k, hipEvent_t* a, hipEvent_t* b) {
@@ -442,22 +414,22 @@ int cilqr_timer::pair(int k, hipEvent_t* a, hipEvent_t* b) {
   if (!wants(k)) return 0;
   if (reserve()) return -1;
   kind.push_back(k);
-  *a = js->ev[next++];
-  *b = js->ev[next++];
+  *a = js->ev[next++].get();
+  *b = js->ev[next++].get();
   return 0;
 }
 int cilqr_timer::end() {
   if (marked) { cilqr_phase_mark_end(); marked = false; }
   if (!open) return 0;
   open = false;
-  return hipEventRecord(js->ev[next++], stream) == hipSuccess ? 0 : -1;
+  return hipEventRecord(js->ev[next++].get(), stream) == hipSuccess ? 0 : -1;
 }
 void cilqr_timer::resolve(cilqr_profile* p) {
   if (!on()) return;
   size_t nb = 0;
   for (size_t i = 0; i < kind.size(); ++i) {
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, js->ev[2 * i], js->ev[2 * i + 1]);
+    (void)hipEventElapsedTime(&ms, js->ev[2 * i].get(), js->ev[2 * i + 1].get());
     switch (kind[i]) {
       case 0: p->quadratize_ms += ms; break;
       case 1:
@@ -473,7 +445,7 @@ void cilqr_timer::resolve(cilqr_profile* p) {
   }
   if (!kind.empty() && h->profiling_level == 1) {
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, js->ev[0], js->ev[next - 1]);
+    (void)hipEventElapsedTime(&ms, js->ev[0].get(), js->ev[next - 1].get());
     p->total_ms = ms;
   }
 }
@@ -539,8 +511,9 @@ int cilqr_create(const cilqr_config* cfg, int32_t device, int32_t batch_capacity
     return CILQR_ERR_DEVICE;
   }
   HIP_TRY(hipSetDevice(device));
-  cilqr_solver* h = new (std::nothrow) cilqr_solver();
-  if (h == nullptr) return CILQR_ERR_DEVICE;
+  std::unique_ptr<cilqr_solver> owner(new (std::nothrow) cilqr_solver());   // (a handle that fails half-built releases itself)
+  if (owner == nullptr) return CILQR_ERR_DEVICE;
+  cilqr_solver* h = owner.get();
   h->cfg = *cfg;
   h->device = device;
   // slots are padded to a multiple of 64 so that every row of every tensor starts 512 B aligned
@@ -563,11 +536,9 @@ int cilqr_create(const cilqr_config* cfg, int32_t device, int32_t batch_capacity
   }
   const size_t N = cfg->n_steps, K = N + 1, B = Bc;
   d.Pcap = Bc;
-  int rc = CILQR_OK;
   // tensors the survivor re-packing moves (k_compact): every arena and every twin has its own
-  auto alloc_moved = [&](DeviceState& t, size_t cap) {
-#define ALLOCM(field, count) \
-  if (rc == CILQR_OK) rc = dev_alloc(h, &t.field, (size_t)(count))
+  auto alloc_moved = [&](DeviceState& t, size_t cap) -> int {
+#define ALLOCM(field, count) HIP_TRY(dev_alloc(h, &t.field, (size_t)(count)))
     ALLOCM(X, 2 * K * 3 * cap);
     ALLOCM(U, 2 * N * cap);
     ALLOCM(cur, cap);
@@ -578,11 +549,11 @@ int cilqr_create(const cilqr_config* cfg, int32_t device, int32_t batch_capacity
     ALLOCM(upd, cap); ALLOCM(acc_idx, cap); ALLOCM(emit, cap); ALLOCM(pid, cap); ALLOCM(done_now, cap);
     ALLOCM(act, cap); ALLOCM(act_next, cap); ALLOCM(posn, cap);
 #undef ALLOCM
+    return CILQR_OK;
   };
   // per-iteration scratch of an arena (shared with its twin)
-  auto alloc_scratch = [&](DeviceState& t, size_t cap) {
-#define ALLOCS(field, count) \
-  if (rc == CILQR_OK) rc = dev_alloc(h, &t.field, (size_t)(count))
+  auto alloc_scratch = [&](DeviceState& t, size_t cap) -> int {
+#define ALLOCS(field, count) HIP_TRY(dev_alloc(h, &t.field, (size_t)(count)))
     ALLOCS(lin, N * kLinPairs * cap);
     ALLOCS(term, (size_t)kTermPairs * cap);
     ALLOCS(gains, N * kGainPairs * cap);
@@ -603,14 +574,15 @@ int cilqr_create(const cilqr_config* cfg, int32_t device, int32_t batch_capacity
     ALLOCS(pend, (size_t)(kNumAlpha + 1) * cap);
     ALLOCS(counters, 64);
 #undef ALLOCS
+    return CILQR_OK;
   };
-  alloc_moved(d, B);
-  alloc_scratch(d, B);
-  if (rc == CILQR_OK) rc = dev_alloc(h, &d.coarse0, 2 * B);
-  if (rc == CILQR_OK) rc = dev_alloc(h, &d.cstation, K * B);
+  if (const int rc = alloc_moved(d, B)) return rc;
+  if (const int rc = alloc_scratch(d, B)) return rc;
+  HIP_TRY(dev_alloc(h, &d.coarse0, 2 * B));
+  HIP_TRY(dev_alloc(h, &d.cstation, K * B));
   // twin arena for re-packing the survivors (k_compact)
   h->twin = d;
-  alloc_moved(h->twin, B);
+  if (const int rc = alloc_moved(h->twin, B)) return rc;
   // finishing arena + twin: a solve moves here once at most fin_cap problems are left (job_iterate)
   size_t fin_want = 8192;
   if (const char* fe = std::getenv("CILQR_FIN_CAP")) fin_want = (size_t)std::max(64, std::atoi(fe)) / 64 * 64;   // tuning experiments
@@ -618,58 +590,46 @@ int cilqr_create(const cilqr_config* cfg, int32_t device, int32_t batch_capacity
   h->fin_threshold = h->fin_cap;
   h->fin = d;
   h->fin.Bcap = h->fin_cap;
-  alloc_moved(h->fin, (size_t)h->fin_cap);
-  alloc_scratch(h->fin, (size_t)h->fin_cap);
+  if (const int rc = alloc_moved(h->fin, (size_t)h->fin_cap)) return rc;
+  if (const int rc = alloc_scratch(h->fin, (size_t)h->fin_cap)) return rc;
   h->fin_twin = h->fin;
-  alloc_moved(h->fin_twin, (size_t)h->fin_cap);
+  if (const int rc = alloc_moved(h->fin_twin, (size_t)h->fin_cap)) return rc;
   // what a solve in flight owns (two sets: see cilqr_job_set)
-  for (int k = 0; k < 2 && rc == CILQR_OK; ++k) {
-    cilqr_job_set& js = h->sets[k];
-    if (rc == CILQR_OK) rc = dev_alloc(h, &js.hist, (size_t)(cfg->max_iter + 1) * 5 * B);
-    if (rc == CILQR_OK) rc = dev_alloc(h, &js.iter, B);
-    if (rc == CILQR_OK) rc = dev_alloc(h, &js.status, B);
-    if (rc == CILQR_OK) rc = dev_alloc(h, &js.n_cost, B);
-    if (rc == CILQR_OK) rc = dev_alloc(h, &js.n_iter_trajs, B);
-    if (rc == CILQR_OK) rc = dev_alloc(h, &js.atrace, (size_t)cfg->max_iter * B);
-    if (rc == CILQR_OK) rc = dev_alloc(h, &js.lanes, (size_t)2 * max_lane_segments * kLaneFields);
-    if (rc == CILQR_OK) rc = dev_alloc(h, &js.lgrid, (size_t)2 * kGridMaxCells * kGridCellBytes);
-    if (rc == CILQR_OK) rc = dev_alloc(h, &js.lanes_raw, (size_t)2 * max_lane_segments * 7);
-    if (rc == CILQR_OK) rc = dev_alloc(h, &js.tail_iter_dev, 4);
-    if (rc == CILQR_OK && hipHostMalloc(reinterpret_cast<void**>(&js.h_count), (size_t)(cfg->max_iter + 64) * sizeof(int),
-                                        hipHostMallocMapped) != hipSuccess)
-      rc = CILQR_ERR_DEVICE;
-    if (rc == CILQR_OK && hipHostGetDevicePointer(reinterpret_cast<void**>(&js.h_count_dev), js.h_count, 0) != hipSuccess)
-      rc = CILQR_ERR_DEVICE;
-    if (rc == CILQR_OK && hipEventCreateWithFlags(&js.handoff, hipEventDisableTiming) != hipSuccess) rc = CILQR_ERR_DEVICE;
-    if (rc == CILQR_OK && hipEventCreateWithFlags(&js.sync_ev, hipEventDisableTiming) != hipSuccess) rc = CILQR_ERR_DEVICE;
-    if (rc == CILQR_OK && hipEventCreateWithFlags(&js.exported, hipEventDisableTiming) != hipSuccess) rc = CILQR_ERR_DEVICE;
+  for (cilqr_job_set& js : h->sets) {
+    HIP_TRY(dev_alloc(h, &js.hist, (size_t)(cfg->max_iter + 1) * 5 * B));
+    HIP_TRY(dev_alloc(h, &js.iter, B));
+    HIP_TRY(dev_alloc(h, &js.status, B));
+    HIP_TRY(dev_alloc(h, &js.n_cost, B));
+    HIP_TRY(dev_alloc(h, &js.n_iter_trajs, B));
+    HIP_TRY(dev_alloc(h, &js.atrace, (size_t)cfg->max_iter * B));
+    HIP_TRY(dev_alloc(h, &js.lanes, (size_t)2 * max_lane_segments * kLaneFields));
+    HIP_TRY(dev_alloc(h, &js.lgrid, (size_t)2 * kGridMaxCells * kGridCellBytes));
+    HIP_TRY(dev_alloc(h, &js.lanes_raw, (size_t)2 * max_lane_segments * 7));
+    HIP_TRY(dev_alloc(h, &js.tail_iter_dev, 4));
+    HIP_TRY(js.h_count.alloc((size_t)(cfg->max_iter + 64) * sizeof(int), hipHostMallocMapped));
+    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&js.h_count_dev), js.h_count.get(), 0));
+    HIP_TRY(js.handoff.create());
+    HIP_TRY(js.sync_ev.create());
+    HIP_TRY(js.exported.create());
   }
   for (cilqr_in_buffer& b : h->in_bufs) {
-    if (rc == CILQR_OK && (hipEventCreateWithFlags(&b.ready, hipEventDisableTiming) != hipSuccess ||
-                           hipEventCreateWithFlags(&b.loaded, hipEventDisableTiming) != hipSuccess))
-      rc = CILQR_ERR_DEVICE;
+    HIP_TRY(b.ready.create());
+    HIP_TRY(b.loaded.create());
   }
-  if (rc == CILQR_OK) {   // the stage API works on the main arena with the first set
+  {   // the stage API works on the main arena with the first set
     const DeviceState v = main_view(h, h->sets[0]);
     d.hist = v.hist; d.iter = v.iter; d.status = v.status; d.n_cost = v.n_cost; d.n_iter_trajs = v.n_iter_trajs;
     d.atrace = v.atrace; d.lanes = v.lanes; d.lgrid = v.lgrid;
   }
-  if (rc == CILQR_OK) rc = dev_alloc(h, &h->lambda_stage, B);
-  if (rc == CILQR_OK && hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess)
-    rc = CILQR_ERR_DEVICE;
-  if (rc == CILQR_OK) {
-    int lo = 0, hi = 0;   // numerically lower = higher priority
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    const char* pe = std::getenv("CILQR_FIN_PRIORITY");   // tuning experiments: 0 = same priority as the first stage
-    const int prio = (pe && pe[0] == '0') ? lo : hi;
-    if (hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, prio) != hipSuccess) rc = CILQR_ERR_DEVICE;
-  }
-  if (rc != CILQR_OK) {
-    cilqr_destroy(h);
-    return rc;
-  }
-  h->stream = h->own_stream;
-  *out = h;
+  HIP_TRY(dev_alloc(h, &h->lambda_stage, B));
+  HIP_TRY(h->own_stream.create(hipStreamNonBlocking));
+  int lo = 0, hi = 0;   // numerically lower = higher priority
+  (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+  const char* pe = std::getenv("CILQR_FIN_PRIORITY");   // tuning experiments: 0 = same priority as the first stage
+  const int prio = (pe && pe[0] == '0') ? lo : hi;
+  HIP_TRY(h->stream2.create(hipStreamNonBlocking, prio));
+  h->stream = h->own_stream.get();
+  *out = owner.release();
   return CILQR_OK;
 }
 
@@ -692,49 +652,16 @@ int cilqr_destroy(cilqr_handle h) {
     h->worker_io.join();
   }
   (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->stream2) (void)hipStreamSynchronize(h->stream2);
-  if (h->stream_in) (void)hipStreamSynchronize(h->stream_in);
-  if (h->stream_out) (void)hipStreamSynchronize(h->stream_out);
+  for (hipStream_t st : {h->stream, h->stream2.get(), h->stream_in.get(), h->stream_out.get()})
+    if (st) (void)hipStreamSynchronize(st);
   cilqr_comm_release(h);
-  for (void* p : h->allocs) (void)hipFree(p);
-  for (cilqr_in_buffer& b : h->in_bufs) {
-    if (b.p) (void)hipFree(b.p);
-    if (b.ready) (void)hipEventDestroy(b.ready);
-    if (b.loaded) (void)hipEventDestroy(b.loaded);
-  }
-  if (h->in_small) (void)hipFree(h->in_small);
-  if (h->in_pinned) (void)hipHostFree(h->in_pinned);
-  if (h->in_pinned_ev) (void)hipEventDestroy(h->in_pinned_ev);
-  if (h->cor_fail) (void)hipFree(h->cor_fail);
-  if (h->cor_fail_host) (void)hipHostFree(h->cor_fail_host);
-  if (h->cor_done) (void)hipEventDestroy(h->cor_done);
-  if (h->tail_ws) (void)hipFree(h->tail_ws);
-  if (h->tail_ws1) (void)hipFree(h->tail_ws1);
-  for (cilqr_job_set& js : h->sets) {
-    if (js.out_stage) (void)hipFree(js.out_stage);
-    if (js.row_off) (void)hipFree(js.row_off);
-    if (js.out_pinned) (void)hipHostFree(js.out_pinned);
-    if (js.host_counts) (void)hipHostFree(js.host_counts);
-    if (js.host_rows) (void)hipHostFree(js.host_rows);
-    if (js.exported) (void)hipEventDestroy(js.exported);
-    if (js.h_count) (void)hipHostFree(js.h_count);
-    for (hipEvent_t e : js.ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : js.iter_ev) (void)hipEventDestroy(e);
-    if (js.handoff) (void)hipEventDestroy(js.handoff);
-    if (js.sync_ev) (void)hipEventDestroy(js.sync_ev);
-  }
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  if (h->stream2) (void)hipStreamDestroy(h->stream2);
-  if (h->stream_in) (void)hipStreamDestroy(h->stream_in);
-  if (h->stream_out) (void)hipStreamDestroy(h->stream_out);
-  delete h;
+  delete h;   // its owners release the memory and the events, then the streams (solver_priv.hpp: cilqr_solver)
   return CILQR_OK;
 }
 
 int cilqr_set_stream(cilqr_handle h, void* hip_stream) {
   if (h == nullptr) return CILQR_ERR_NULL;
-  h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
+  h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream.get();
   return CILQR_OK;
 }
 
@@ -1019,7 +946,7 @@ int job_begin(cilqr_solver* h, cilqr_job& j) {
       h->cv.notify_all();
       return j.upload_rc;
     }
-    HIP_TRY(hipStreamWaitEvent(st, h->in_bufs[j.in_buf].ready, 0));
+    HIP_TRY(hipStreamWaitEvent(st, h->in_bufs[j.in_buf].ready.get(), 0));
     rc = do_load(h, in, js, &j.gmain, st, &j.pv, j.in_buf);
     j.in_buf = -1;   // (given back behind the load kernels, whatever happened)
   } else {
@@ -1053,15 +980,14 @@ int job_begin(cilqr_solver* h, cilqr_job& j) {
     // the iterates last, so that a small batch can fetch everything else (and the first few iterates) in one short copy
     j.n_head = out_head_bytes(h, B, out);
     const size_t bytes = j.n_head + j.n_itr * 8 + 1024;
-    rc = grow(h, &js.out_stage, &js.out_stage_bytes, bytes);
-    if (rc != CILQR_OK) return rc;
-    double* p = static_cast<double*>(js.out_stage);
+    HIP_TRY(js.out_stage.grow(bytes, &h->grown_bytes));
+    double* p = js.out_stage.as<double>();
     j.o_traj = p; p += j.n_traj;
     j.o_hist = p; p += j.n_hist;
     int* q = reinterpret_cast<int*>(p);
     j.o_nc = q; j.o_st = q + B; j.o_ni = q + 2 * B; j.o_nit = q + 3 * B;
     j.o_at = out->alpha_trace ? reinterpret_cast<signed char*>(q + 4 * B) : nullptr;
-    j.o_it = out->iter_trajs ? reinterpret_cast<double*>(static_cast<char*>(js.out_stage) + j.n_head) : nullptr;
+    j.o_it = out->iter_trajs ? reinterpret_cast<double*>(js.out_stage.as<char>() + j.n_head) : nullptr;
     j.big_out = host_out_is_big(h, B, out);
     j.small_out = !j.big_out;
     // The staging buffer is reused between solves.  Its Cost rows reach the caller through the live rows only, on either
@@ -1069,9 +995,8 @@ int job_begin(cilqr_solver* h, cilqr_job& j) {
     // batch travel as the dense block they are, so the entries the kernels do not write (>= n_iter_trajs) are cleared here
     if (j.big_out && j.n_itr) HIP_TRY(hipMemsetAsync(j.o_it, 0, j.n_itr * 8, st));
     if (j.big_out) {
-      rc = grow(h, reinterpret_cast<void**>(&js.row_off), &js.row_off_bytes, ((size_t)B + 1) * sizeof(long long));
-      if (rc == CILQR_OK) rc = grow_pinned(&js.host_counts, &js.host_counts_bytes, (size_t)4 * B * sizeof(int));
-      if (rc != CILQR_OK) return rc;
+      HIP_TRY(js.row_off.grow(((size_t)B + 1) * sizeof(long long), &h->grown_bytes));
+      HIP_TRY(js.host_counts.grow((size_t)4 * B * sizeof(int)));
     }
   }
 
@@ -1082,25 +1007,22 @@ int job_begin(cilqr_solver* h, cilqr_job& j) {
   if (j.o_it) launch_export_iter_traj(j.d, nullptr, B, j.o_it, out->max_iter_trajs, st);
   if (j.tm.end()) return CILQR_ERR_DEVICE;
 
-  if ((int)js.iter_ev.size() < M) {
-    const size_t old = js.iter_ev.size();
-    js.iter_ev.resize(M);
-    for (size_t i = old; i < js.iter_ev.size(); ++i)
-      HIP_TRY(hipEventCreateWithFlags(&js.iter_ev[i], hipEventDisableTiming));
+  while ((int)js.iter_ev.size() < M) {   // (an event joins the list once it exists)
+    hip_event e;
+    HIP_TRY(e.create());
+    js.iter_ev.push_back(std::move(e));
   }
   // The tail of the batch (kernels_tail.hip) needs a private arena per problem; sized before the first kernel so
   // that no allocation falls into the solve.  (Grown only while no other solve is finishing: see cilqr_submit.)
   if (j.tail_threshold > 0) {
     const size_t need = (size_t)std::min(B, j.tail_threshold) * tail_workspace_bytes(j.d);
-    if (need > h->tail_ws_bytes) {
+    if (need > h->tail_ws.bytes()) {
       std::unique_lock<std::mutex> lk(h->mu);
       h->cv.wait(lk, [h] { return !h->fin_busy || h->quit; });
       if (h->quit) return CILQR_ERR_STATE;   // the handle is being destroyed
-      rc = grow(h, &h->tail_ws, &h->tail_ws_bytes, need);
-      if (rc != CILQR_OK) return rc;
+      HIP_TRY(h->tail_ws.grow(need, &h->grown_bytes));
     }
-    rc = grow(h, &h->tail_ws1, &h->tail_ws1_bytes, need);   // only ever used by the first stage (this thread)
-    if (rc != CILQR_OK) return rc;
+    HIP_TRY(h->tail_ws1.grow(need, &h->grown_bytes));   // only ever used by the first stage (this thread)
   }
   launch_init_counters(j.d, B, st);
   // rows >= n_cost of the caller's cost_hist are zero on every host path (include/cilqr.h).  A large batch receives its live
@@ -1123,11 +1045,12 @@ int job_iterate(cilqr_solver* h, cilqr_job& j, int stage) {
   HIP_TRY(hipSetDevice(h->device));
   cilqr_job_set& js = h->sets[j.set];
   const int M = h->cfg.max_iter, B = j.B;
+  int* h_count = js.h_count.as<int>();
   hipStream_t st = (stage == 1) ? j.st1 : j.st2;
   DeviceState& d = j.d;
   DeviceState& o = j.o;
   if (stage == 2) {
-    if (j.st2 != j.st1) HIP_TRY(hipStreamWaitEvent(j.st2, js.handoff, 0));
+    if (j.st2 != j.st1) HIP_TRY(hipStreamWaitEvent(j.st2, js.handoff.get(), 0));
     j.tm.stream = st;
   }
   // The host runs kLead iterations ahead of the GPU: before enqueueing iteration `it` it waits only
@@ -1145,8 +1068,8 @@ int job_iterate(cilqr_solver* h, cilqr_job& j, int stage) {
   for (; it < M; ++it) {                               // cc:201
     if (it >= kLead) {
       // (few problems left: an iteration is ~100 us, and a nap that ends late costs a whole one -- spin longer before napping)
-      if (int wrc = wait_event(js.iter_ev[it - kLead], j.relaxed_wait, n_hint < kShortIterationProblems ? kWaitSpinShortUs : kWaitSpinUs)) return wrc;
-      n_hint = js.h_count[it - kLead];
+      if (int wrc = wait_event(js.iter_ev[it - kLead].get(), j.relaxed_wait, n_hint < kShortIterationProblems ? kWaitSpinShortUs : kWaitSpinUs)) return wrc;
+      n_hint = h_count[it - kLead];
       if (n_hint == 0) break;                          // iterations it-kLead+1 .. it-1 were no-ops
     }
     bool hand_over = false;
@@ -1176,7 +1099,7 @@ int job_iterate(cilqr_solver* h, cilqr_job& j, int stage) {
       hipLaunchKernelGGL(k_seed_counters, dim3(1), dim3(64), 0, st, f.counters, a.n_next, kCntActive + it % 3);
       HIP_TRY(hipGetLastError());
       if (j.tm.end()) return CILQR_ERR_DEVICE;
-      HIP_TRY(hipEventRecord(js.handoff, st));
+      HIP_TRY(hipEventRecord(js.handoff.get(), st));
       d = f;
       o = twin_of(f, h->fin_twin);
       j.span = n_hint;
@@ -1194,11 +1117,11 @@ int job_iterate(cilqr_solver* h, cilqr_job& j, int stage) {
     if (n_hint <= tail_threshold) {
       // few problems left: each gets a workgroup that runs all its remaining iterations (cc:201-319) in one launch
       // a solve that was never handed over has the tail workspace of the first stage to itself
-      void* ws = (stage == 1 && !j.handed) ? h->tail_ws1 : h->tail_ws;
+      void* ws = (stage == 1 && !j.handed) ? h->tail_ws1.get() : h->tail_ws.get();
       if (j.tm.begin(4)) return CILQR_ERR_DEVICE;
       HIP_TRY(hipMemsetAsync(js.tail_iter_dev, 0, sizeof(int), st));
       launch_tail(d, ws, n_hint, j.o_traj, j.o_it, j.out.max_iter_trajs, js.tail_iter_dev, st);
-      HIP_TRY(hipMemcpyAsync(js.h_count + M + 32, js.tail_iter_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(h_count + M + 32, js.tail_iter_dev, sizeof(int), hipMemcpyDeviceToHost, st));
       if (j.tm.end()) return CILQR_ERR_DEVICE;
       j.tail_used = true;
       j.tail_n = n_hint;
@@ -1221,7 +1144,7 @@ int job_iterate(cilqr_solver* h, cilqr_job& j, int stage) {
     launch_export_done(d, n_hint, j.o_traj, st);       // cc:238,285,303,319
     if (j.o_it) launch_export_iter_traj(d, d.act, n_hint, j.o_it, j.out.max_iter_trajs, st);
     if (j.tm.end()) return CILQR_ERR_DEVICE;
-    HIP_TRY(hipEventRecord(js.iter_ev[it], st));
+    HIP_TRY(hipEventRecord(js.iter_ev[it].get(), st));
     if (h->compaction && (int64_t)100 * n_hint <= (int64_t)h->compact_percent * j.span) {
       // the survivors have thinned out: re-pack them densely (k_compact reads the exact count)
       if (j.tm.begin(3)) return CILQR_ERR_DEVICE;
@@ -1248,7 +1171,7 @@ int job_finish(cilqr_solver* h, cilqr_job& j) {
   if (j.tm.begin(3)) return CILQR_ERR_DEVICE;
   const bool big_out = out->memory == CILQR_MEM_HOST && j.big_out;
   launch_export_hist(j.gmain, B, big_out ? nullptr : j.o_hist, j.o_nc, j.o_st, j.o_ni, j.o_nit, j.o_at, st);
-  if (big_out) launch_export_hist_rows(j.gmain, B, js.row_off, j.o_hist, st);   // the live rows, packed, where the dense block used to go
+  if (big_out) launch_export_hist_rows(j.gmain, B, js.row_off.as<long long>(), j.o_hist, st);   // the live rows, packed, where the dense block used to go
   if (j.tm.end()) return CILQR_ERR_DEVICE;
   HIP_TRY(hipGetLastError());
   const bool small_out = out->memory == CILQR_MEM_HOST && j.small_out;
@@ -1261,41 +1184,42 @@ int job_finish(cilqr_solver* h, cilqr_job& j) {
   if (small_out) {
     // a small batch: the head of the staging block in one copy into pinned memory, handed out on the host below (seven
     // pageable copies cost ~25 us each after the last kernel); the iterates that exist follow once their counts are known
-    if (js.out_pinned == nullptr) HIP_TRY(hipHostMalloc(&js.out_pinned, kSmallTransfer, hipHostMallocDefault));
-    HIP_TRY(hipMemcpyAsync(js.out_pinned, js.out_stage, j.n_head + first, hipMemcpyDeviceToHost, st));
+    if (js.out_pinned.get() == nullptr) HIP_TRY(js.out_pinned.alloc(kSmallTransfer));
+    HIP_TRY(hipMemcpyAsync(js.out_pinned.get(), js.out_stage.get(), j.n_head + first, hipMemcpyDeviceToHost, st));
   } else if (big_out) {
     // A large batch: everything is downloaded on the handle's download stream, so that the kernels of the NEXT solve's
     // finishing stage do not queue behind 0.3 GB of copies.  First the counts (they size the packed rows), then the
     // trajectories straight into the caller's array; the finishing arena goes back as soon as the last kernel is known to
     // be done, i.e. before the copies are
     if (int src = io_streams(h)) return src;
-    hipStream_t so = h->stream_out;
-    HIP_TRY(hipEventRecord(js.exported, st));
-    HIP_TRY(hipStreamWaitEvent(so, js.exported, 0));
-    HIP_TRY(hipMemcpyAsync(js.host_counts, j.o_nc, (size_t)4 * B * 4, hipMemcpyDeviceToHost, so));   // n_cost | status | n_iter | n_iter_trajs
-    HIP_TRY(hipEventRecord(js.sync_ev, so));
-    if (int wrc = wait_event(js.sync_ev, j.relaxed_wait)) return wrc;
+    hipStream_t so = h->stream_out.get();
+    HIP_TRY(hipEventRecord(js.exported.get(), st));
+    HIP_TRY(hipStreamWaitEvent(so, js.exported.get(), 0));
+    HIP_TRY(hipMemcpyAsync(js.host_counts.get(), j.o_nc, (size_t)4 * B * 4, hipMemcpyDeviceToHost, so));   // n_cost | status | n_iter | n_iter_trajs
+    HIP_TRY(hipEventRecord(js.sync_ev.get(), so));
+    if (int wrc = wait_event(js.sync_ev.get(), j.relaxed_wait)) return wrc;
     release_fin(h, j);
-    const int32_t* nc = static_cast<const int32_t*>(js.host_counts);
+    const int32_t* nc = js.host_counts.as<const int32_t>();
     size_t rows = 0;
     for (int b = 0; b < B; ++b) rows += (size_t)std::min(std::max(nc[b], 0), M + 1);
-    if (int grc = grow_pinned(&js.host_rows, &js.host_rows_bytes, std::max(rows + rows / 2, (size_t)B * 16) * 5 * 8)) return grc;
-    HIP_TRY(hipMemcpyAsync(js.host_rows, j.o_hist, rows * 5 * 8, hipMemcpyDeviceToHost, so));
+    HIP_TRY(js.host_rows.grow(std::max(rows + rows / 2, (size_t)B * 16) * 5 * 8));
+    HIP_TRY(hipMemcpyAsync(js.host_rows.get(), j.o_hist, rows * 5 * 8, hipMemcpyDeviceToHost, so));
     HIP_TRY(hipMemcpyAsync(out->traj, j.o_traj, j.n_traj * 8, hipMemcpyDeviceToHost, so));
     if (out->iter_trajs) HIP_TRY(hipMemcpyAsync(out->iter_trajs, j.o_it, j.n_itr * 8, hipMemcpyDeviceToHost, so));
     if (out->alpha_trace) HIP_TRY(hipMemcpyAsync(out->alpha_trace, j.o_at, j.n_at, hipMemcpyDeviceToHost, so));
     st = so;
   }
-  if (int wrc = wait_stream(st, js.sync_ev, j.relaxed_wait)) return wrc;
+  if (int wrc = wait_stream(st, js.sync_ev.get(), j.relaxed_wait)) return wrc;
   int it = j.it;
   {  // lockstep iterations that had work, and the problem-steps each backward launch covered
+    const int* h_count = js.h_count.as<int>();
     int used = 0;
     for (int i = 0; i < it; ++i) {
-      const int n_in = (i == 0) ? B : js.h_count[i - 1];
+      const int n_in = (i == 0) ? B : h_count[i - 1];
       if (n_in > 0) used = i + 1;
     }
     for (int i : j.bwd_iter) {
-      const int n_in = (i == 0) ? B : js.h_count[i - 1];
+      const int n_in = (i == 0) ? B : h_count[i - 1];
       if (n_in <= 0) continue;
       j.prof.backward_launches += 1;
       j.prof.backward_problem_steps += (int64_t)n_in * h->cfg.n_steps;
@@ -1303,13 +1227,13 @@ int job_finish(cilqr_solver* h, cilqr_job& j) {
     j.tm.full_flags.assign(j.bwd_iter.size(), 0);
     j.tm.live_flags.assign(j.bwd_iter.size(), 0);
     for (size_t k = 0; k < j.bwd_iter.size(); ++k) {
-      const int n_in = (j.bwd_iter[k] == 0) ? B : js.h_count[j.bwd_iter[k] - 1];
+      const int n_in = (j.bwd_iter[k] == 0) ? B : h_count[j.bwd_iter[k] - 1];
       j.tm.full_flags[k] = (n_in == B);
       j.tm.live_flags[k] = (n_in > 0);
     }
     it = used;
     if (j.tail_used) {
-      it = std::max(it, js.h_count[M + 32]);
+      it = std::max(it, h_count[M + 32]);
       j.prof.tail_problems = j.tail_n;   // upper bound (the count the host knew when it enqueued the tail)
     }
   }
@@ -1319,10 +1243,10 @@ int job_finish(cilqr_solver* h, cilqr_job& j) {
       std::unique_lock<std::mutex> lk(h->mu);
       h->cv.wait(lk, [&] { return !j.io_busy; });
     }
-    const char* q = static_cast<const char*>(js.host_counts);
+    const char* q = js.host_counts.as<const char>();
     const int32_t* nc = reinterpret_cast<const int32_t*>(q);
     const size_t row = 5 * 8, block = (size_t)(M + 1) * row;
-    const char* src = static_cast<const char*>(js.host_rows);
+    const char* src = js.host_rows.as<const char>();
     for (int b = 0; b < B; ++b) {   // live rows into the caller's dense array; the rest of it is zero already
       const size_t live = (size_t)std::min(std::max(nc[b], 0), M + 1) * row;
       std::memcpy(reinterpret_cast<char*>(out->cost_hist) + (size_t)b * block, src, live);
@@ -1334,7 +1258,7 @@ int job_finish(cilqr_solver* h, cilqr_job& j) {
     if (out->iter_trajs) std::memcpy(out->n_iter_trajs, q + (size_t)3 * B * 4, (size_t)B * 4);
   }
   if (small_out) {   // same layout as the staging block (job_begin)
-    char* pin = static_cast<char*>(js.out_pinned);
+    char* pin = js.out_pinned.as<char>();
     const char* q = pin + (j.n_traj + j.n_hist) * 8;
     const int32_t* nc = reinterpret_cast<const int32_t*>(q);
     const int32_t* nit = reinterpret_cast<const int32_t*>(q + (size_t)3 * B * 4);
@@ -1350,7 +1274,7 @@ int job_finish(cilqr_solver* h, cilqr_job& j) {
           more = true;
         }
       }
-      if (more) { if (int wrc = wait_stream(st, js.sync_ev, j.relaxed_wait)) return wrc; }
+      if (more) { if (int wrc = wait_stream(st, js.sync_ev.get(), j.relaxed_wait)) return wrc; }
     }
     std::memcpy(out->traj, pin, j.n_traj * 8);
     {  // cost rows: the live ones; the rest of the caller's array is zero, as on every host path
@@ -1532,11 +1456,12 @@ void worker_io_main(cilqr_solver* h) {
         buf = acquire_in_buffer(h, true);
         if (buf < 0) rc = CILQR_ERR_DEVICE;
       }
-      if (rc == CILQR_OK) rc = stage_inputs(h, &j.in, &h->in_bufs[buf], h->stream_in, &j.pv);
-      if (rc == CILQR_OK && hipEventRecord(h->in_bufs[buf].ready, h->stream_in) != hipSuccess) rc = CILQR_ERR_DEVICE;
+      hipStream_t si = h->stream_in.get();
+      if (rc == CILQR_OK) rc = stage_inputs(h, &j.in, &h->in_bufs[buf], si, &j.pv);
+      if (rc == CILQR_OK && hipEventRecord(h->in_bufs[buf].ready.get(), si) != hipSuccess) rc = CILQR_ERR_DEVICE;
       if (rc != CILQR_OK && buf >= 0) {   // nothing will read it
-        (void)hipStreamSynchronize(h->stream_in);
-        release_in_buffer(h, buf, h->stream_in);
+        (void)hipStreamSynchronize(si);
+        release_in_buffer(h, buf, si);
         buf = -1;
       }
       lk.lock();
@@ -1579,7 +1504,7 @@ int cilqr_submit(cilqr_handle h, const cilqr_problem_batch* in, cilqr_solution_b
   j.spec_threshold = h->alone_on_device ? h->spec_threshold : h->spec_threshold_submit;
   j.tail_threshold = h->alone_on_device ? h->tail_threshold : h->tail_threshold_submit;
   j.st1 = h->stream;
-  j.st2 = h->stream2;
+  j.st2 = h->stream2.get();
   j.relaxed_wait = true;     // a worker thread waits for this solve, and other solves want the cores (wait_event)
   // host arrays of a large batch: the transfer thread starts on them now (worker_io_main)
   const bool plain = in->n_lane_groups <= 1 && in->batch > 0 && in->batch <= h->capacity;
@@ -1643,12 +1568,12 @@ int cilqr_stage_init_guess(cilqr_handle h) {
   return CILQR_OK;
 }
 
-static int to_device(cilqr_solver* h, const void* src, size_t bytes, int memory, void** tmp, const void** dev) {
-  *tmp = nullptr;
+// the caller's input on the device: its own array, or a copy in `tmp` (host memory)
+static int to_device(cilqr_solver* h, const void* src, size_t bytes, int memory, dev_mem& tmp, const void** dev) {
   if (memory == CILQR_MEM_DEVICE) { *dev = src; return CILQR_OK; }
-  HIP_TRY(hipMalloc(tmp, bytes ? bytes : 256));
-  HIP_TRY(hipMemcpyAsync(*tmp, src, bytes, hipMemcpyHostToDevice, h->stream));
-  *dev = *tmp;
+  HIP_TRY(tmp.alloc(bytes ? bytes : 256));
+  HIP_TRY(hipMemcpyAsync(tmp.get(), src, bytes, hipMemcpyHostToDevice, h->stream));
+  *dev = tmp.get();
   return CILQR_OK;
 }
 
@@ -1657,35 +1582,28 @@ int cilqr_stage_set_trajectory(cilqr_handle h, const double* X, const double* U,
   if (!(h->stage & 1)) return CILQR_ERR_STATE;
   HIP_TRY(hipSetDevice(h->device));
   const int B = h->B, K = h->cfg.n_steps + 1, N = h->cfg.n_steps;
-  void *tx = nullptr, *tu = nullptr;
+  dev_mem tx, tu;
   const void *dx = nullptr, *du = nullptr;
-  int rc = to_device(h, X, (size_t)B * K * 6 * 8, memory, &tx, &dx);
-  if (rc == CILQR_OK) rc = to_device(h, U, (size_t)B * N * 2 * 8, memory, &tu, &du);
-  if (rc == CILQR_OK) {
-    launch_set_trajectory(h->ds, B, static_cast<const double*>(dx), static_cast<const double*>(du), h->stream);
-    if (hipStreamSynchronize(h->stream) != hipSuccess) rc = CILQR_ERR_DEVICE;
-  }
-  if (tx) (void)hipFree(tx);
-  if (tu) (void)hipFree(tu);
-  if (rc == CILQR_OK) h->stage = 1 | 2;
-  return rc;
-}
-
-static int from_device(cilqr_solver* h, double* dst, size_t count, int memory, double** dev, void** tmp) {
-  *tmp = nullptr;
-  if (memory == CILQR_MEM_DEVICE) { *dev = dst; return CILQR_OK; }
-  HIP_TRY(hipMalloc(tmp, count ? count * 8 : 256));
-  *dev = static_cast<double*>(*tmp);
-  (void)h;
+  if (int rc = to_device(h, X, (size_t)B * K * 6 * 8, memory, tx, &dx)) return rc;
+  if (int rc = to_device(h, U, (size_t)B * N * 2 * 8, memory, tu, &du)) return rc;
+  launch_set_trajectory(h->ds, B, static_cast<const double*>(dx), static_cast<const double*>(du), h->stream);
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return CILQR_ERR_DEVICE;
+  h->stage = 1 | 2;
   return CILQR_OK;
 }
-static int finish_from_device(cilqr_solver* h, double* dst, size_t count, int memory, void* tmp) {
+
+// where the kernels write a result for the caller: its own array, or `tmp` (host memory), copied over by finish_from_device
+static int from_device(double* dst, size_t count, int memory, dev_mem& tmp, double** dev) {
+  if (memory == CILQR_MEM_DEVICE) { *dev = dst; return CILQR_OK; }
+  HIP_TRY(tmp.alloc(count ? count * 8 : 256));
+  *dev = tmp.as<double>();
+  return CILQR_OK;
+}
+static int finish_from_device(cilqr_solver* h, double* dst, size_t count, int memory, const dev_mem& tmp) {
   int rc = CILQR_OK;
-  if (memory == CILQR_MEM_HOST && tmp) {
-    if (hipMemcpyAsync(dst, tmp, count * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = CILQR_ERR_DEVICE;
-  }
+  if (memory == CILQR_MEM_HOST && hipMemcpyAsync(dst, tmp.get(), count * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+    rc = CILQR_ERR_DEVICE;
   if (hipStreamSynchronize(h->stream) != hipSuccess) rc = CILQR_ERR_DEVICE;
-  if (tmp) (void)hipFree(tmp);
   if (rc == CILQR_OK && hipGetLastError() != hipSuccess) rc = CILQR_ERR_DEVICE;
   return rc;
 }
@@ -1696,9 +1614,8 @@ int cilqr_stage_total_cost(cilqr_handle h, double* cost5, int32_t memory) {
   HIP_TRY(hipSetDevice(h->device));
   const int B = h->B;
   double* dev = nullptr;
-  void* tmp = nullptr;
-  int rc = from_device(h, cost5, (size_t)B * 5, memory, &dev, &tmp);
-  if (rc != CILQR_OK) return rc;
+  dev_mem tmp;
+  if (int rc = from_device(cost5, (size_t)B * 5, memory, tmp, &dev)) return rc;
   launch_cost_only(h->ds, nullptr, B, 0, h->stream);
   launch_gather_scalar(h->ds.trial, 5, h->ds.Bcap, B, dev, 5, 0, h->stream);
   return finish_from_device(h, cost5, (size_t)B * 5, memory, tmp);
@@ -1781,9 +1698,8 @@ int cilqr_stage_read(cilqr_handle h, int32_t tensor, double* dst, int32_t memory
     return CILQR_OK;
   }
   double* dev = nullptr;
-  void* tmp = nullptr;
-  int rc = from_device(h, dst, count, memory, &dev, &tmp);
-  if (rc != CILQR_OK) return rc;
+  dev_mem tmp;
+  if (int rc = from_device(dst, count, memory, tmp, &dev)) return rc;
   hipStream_t st = h->stream;
   switch (tensor) {
     case CILQR_T_GOALS: launch_gather_pairs(d.goals, K * 3, Bc, B, dev, K * 6, 0, st); break;
@@ -1805,25 +1721,22 @@ int cilqr_stage_nearest_lane(cilqr_handle h, int32_t n, const double* xy, int32_
   if (n <= 0) return CILQR_ERR_ARG;
   if (!(h->stage & 1)) return CILQR_ERR_STATE;
   HIP_TRY(hipSetDevice(h->device));
-  void *t0 = nullptr, *tl = nullptr;
+  dev_mem t0, tl;
   const void* dxy = nullptr;
-  int rc = to_device(h, xy, (size_t)n * 2 * 8, memory, &t0, &dxy);
+  if (int rc = to_device(h, xy, (size_t)n * 2 * 8, memory, t0, &dxy)) return rc;
   int* dl = left; int* dr = right;
-  if (rc == CILQR_OK && memory == CILQR_MEM_HOST) {
-    if (hipMalloc(&tl, (size_t)n * 2 * sizeof(int)) != hipSuccess) rc = CILQR_ERR_DEVICE;
-    dl = static_cast<int*>(tl); dr = dl + n;
+  if (memory == CILQR_MEM_HOST) {
+    if (tl.alloc((size_t)n * 2 * sizeof(int)) != hipSuccess) return CILQR_ERR_DEVICE;
+    dl = tl.as<int>(); dr = dl + n;
   }
-  if (rc == CILQR_OK) {
-    launch_nearest_lane(h->ds, n, static_cast<const double*>(dxy), dl, dr, use_grid, h->stream);
-    if (memory == CILQR_MEM_HOST) {
-      if (hipMemcpyAsync(left, dl, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-          hipMemcpyAsync(right, dr, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
-        rc = CILQR_ERR_DEVICE;
-    }
-    if (hipStreamSynchronize(h->stream) != hipSuccess) rc = CILQR_ERR_DEVICE;
+  launch_nearest_lane(h->ds, n, static_cast<const double*>(dxy), dl, dr, use_grid, h->stream);
+  int rc = CILQR_OK;
+  if (memory == CILQR_MEM_HOST) {
+    if (hipMemcpyAsync(left, dl, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        hipMemcpyAsync(right, dr, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+      rc = CILQR_ERR_DEVICE;
   }
-  if (t0) (void)hipFree(t0);
-  if (tl) (void)hipFree(tl);
+  if (hipStreamSynchronize(h->stream) != hipSuccess) rc = CILQR_ERR_DEVICE;
   return rc;
 }
 
@@ -1856,17 +1769,15 @@ int cilqr_build_corridors(cilqr_handle h, const cilqr_corridor_config* cfg, int3
   const size_t b_cor = n * (size_t)cmax * 3 * 8, b_poly = polygons ? n * (size_t)cmax * 2 * 8 : 0;
   CorridorParams cp{cfg->max_diff_x, cfg->max_diff_y, cfg->radius, cfg->max_axis_x, cfg->max_axis_y,
                     cfg->is_multiple_sample ? 6 : 2};
-  void *t_in = nullptr, *t_out = nullptr;
+  dev_mem t_in, t_out;
   int rc = CILQR_OK;
   // the failure counter and its landing place on the host belong to the handle: a hipMalloc / hipFree per call is a
   // device-wide synchronisation, i.e. a producer that runs beside solves in flight (other handles, a pool) would wait for
   // all of them
-  if (h->cor_fail == nullptr) {
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->cor_fail), 256));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->cor_fail_host), 64, hipHostMallocDefault));
-    HIP_TRY(hipEventCreateWithFlags(&h->cor_done, hipEventDisableTiming));
-  }
-  int* t_fail = h->cor_fail;
+  if (h->cor_fail.get() == nullptr) HIP_TRY(h->cor_fail.alloc(256));
+  if (h->cor_fail_host.get() == nullptr) HIP_TRY(h->cor_fail_host.alloc(64));
+  if (h->cor_done.get() == nullptr) HIP_TRY(h->cor_done.create());
+  int* t_fail = h->cor_fail.as<int>();
   // (a producer beside solves in flight -- bench.py: end_to_end -- runs on the handle's own stream at normal priority: on a
   // low-priority stream the call took 25 ms instead of 16.5 and the pipeline lost 1.5 %, r06 log 7)
   hipStream_t cst = h->stream;
@@ -1878,11 +1789,11 @@ int cilqr_build_corridors(cilqr_handle h, const cilqr_corridor_config* cfg, int3
   if (hipMemsetAsync(t_fail, 0, 4, cst) != hipSuccess) rc = CILQR_ERR_DEVICE;
   if (rc == CILQR_OK && memory == CILQR_MEM_HOST) {
     const size_t o_pts = (b_knots + 255) / 256 * 256, o_cnt = o_pts + (b_pts + 255) / 256 * 256;
-    if (hipMalloc(&t_in, o_cnt + b_cnt + 256) != hipSuccess || hipMalloc(&t_out, b_cor + 512 + b_cnt + b_poly) != hipSuccess) {
+    if (t_in.alloc(o_cnt + b_cnt + 256) != hipSuccess || t_out.alloc(b_cor + 512 + b_cnt + b_poly) != hipSuccess) {
       rc = CILQR_ERR_DEVICE;
     } else {
-      char* bi = static_cast<char*>(t_in);
-      char* bo = static_cast<char*>(t_out);
+      char* bi = t_in.as<char>();
+      char* bo = t_out.as<char>();
       if (hipMemcpyAsync(bi, knots, b_knots, hipMemcpyHostToDevice, cst) != hipSuccess ||
           (b_pts && hipMemcpyAsync(bi + o_pts, points, b_pts, hipMemcpyHostToDevice, cst) != hipSuccess) ||
           hipMemcpyAsync(bi + o_cnt, point_count, b_cnt, hipMemcpyHostToDevice, cst) != hipSuccess)
@@ -1906,19 +1817,17 @@ int cilqr_build_corridors(cilqr_handle h, const cilqr_corridor_config* cfg, int3
         rc = CILQR_ERR_DEVICE;
     }
     if (rc == CILQR_OK &&
-        hipMemcpyAsync(h->cor_fail_host, t_fail, 4, hipMemcpyDeviceToHost, cst) != hipSuccess)
+        hipMemcpyAsync(h->cor_fail_host.get(), t_fail, 4, hipMemcpyDeviceToHost, cst) != hipSuccess)
       rc = CILQR_ERR_DEVICE;
     // a large batch is milliseconds of kernel time: the caller's thread naps through it instead of spinning (it usually has
     // solves in flight whose worker threads want the cores); a small one is waited for the short way
     if (rc == CILQR_OK && n >= (size_t)1 << 18) {
-      if (hipEventRecord(h->cor_done, cst) != hipSuccess || wait_event(h->cor_done, true) != CILQR_OK) rc = CILQR_ERR_DEVICE;
+      if (hipEventRecord(h->cor_done.get(), cst) != hipSuccess || wait_event(h->cor_done.get(), true) != CILQR_OK) rc = CILQR_ERR_DEVICE;
     } else if (hipStreamSynchronize(cst) != hipSuccess) {
       rc = CILQR_ERR_DEVICE;
     }
-    if (rc == CILQR_OK) failed = *h->cor_fail_host;
+    if (rc == CILQR_OK) failed = *h->cor_fail_host.as<int>();
   }
-  if (t_in) (void)hipFree(t_in);
-  if (t_out) (void)hipFree(t_out);
   if (n_failed) *n_failed = failed;
   return rc;
 }
@@ -1954,18 +1863,15 @@ int cilqr_device_math(cilqr_handle h, int32_t fn, int32_t n, const double* in, d
   if (h == nullptr || in == nullptr || out == nullptr) return CILQR_ERR_NULL;
   if (n <= 0 || fn < 0 || fn > 10) return CILQR_ERR_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  double* d = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&d), (size_t)n * 16) != hipSuccess) return CILQR_ERR_DEVICE;
-  int rc = CILQR_OK;
-  if (hipMemcpyAsync(d, in, (size_t)n * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = CILQR_ERR_DEVICE;
-  if (rc == CILQR_OK) {
-    launch_device_math(fn, n, d, d + n, h->stream);
-    if (hipMemcpyAsync(out, d + n, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess)
-      rc = CILQR_ERR_DEVICE;
-  }
-  (void)hipFree(d);
-  return rc;
+  dev_mem tmp;
+  if (tmp.alloc((size_t)n * 16) != hipSuccess) return CILQR_ERR_DEVICE;
+  double* d = tmp.as<double>();
+  if (hipMemcpyAsync(d, in, (size_t)n * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) return CILQR_ERR_DEVICE;
+  launch_device_math(fn, n, d, d + n, h->stream);
+  if (hipMemcpyAsync(out, d + n, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+      hipStreamSynchronize(h->stream) != hipSuccess)
+    return CILQR_ERR_DEVICE;
+  return CILQR_OK;
 }
 
 int cilqr_open_loop_rollout(cilqr_handle h, int32_t batch, const double* x0, const double* U, double* X,
@@ -1974,21 +1880,14 @@ int cilqr_open_loop_rollout(cilqr_handle h, int32_t batch, const double* x0, con
   if (batch <= 0) return CILQR_ERR_ARG;
   HIP_TRY(hipSetDevice(h->device));
   const int N = h->cfg.n_steps, K = N + 1;
-  void *t0 = nullptr, *tu = nullptr, *tx = nullptr;
+  dev_mem t0, tu, tx;
   const void *d0 = nullptr, *du = nullptr;
   double* dx = nullptr;
-  int rc = to_device(h, x0, (size_t)batch * 6 * 8, memory, &t0, &d0);
-  if (rc == CILQR_OK) rc = to_device(h, U, (size_t)batch * N * 2 * 8, memory, &tu, &du);
-  if (rc == CILQR_OK) rc = from_device(h, X, (size_t)batch * K * 6, memory, &dx, &tx);
-  if (rc == CILQR_OK) {
-    launch_rollout(h->ds.p, batch, static_cast<const double*>(d0), static_cast<const double*>(du), dx, h->stream);
-    rc = finish_from_device(h, X, (size_t)batch * K * 6, memory, tx);
-    tx = nullptr;
-  }
-  if (t0) (void)hipFree(t0);
-  if (tu) (void)hipFree(tu);
-  if (tx) (void)hipFree(tx);
-  return rc;
+  if (int rc = to_device(h, x0, (size_t)batch * 6 * 8, memory, t0, &d0)) return rc;
+  if (int rc = to_device(h, U, (size_t)batch * N * 2 * 8, memory, tu, &du)) return rc;
+  if (int rc = from_device(X, (size_t)batch * K * 6, memory, tx, &dx)) return rc;
+  launch_rollout(h->ds.p, batch, static_cast<const double*>(d0), static_cast<const double*>(du), dx, h->stream);
+  return finish_from_device(h, X, (size_t)batch * K * 6, memory, tx);
 }
 
 }  // extern "C"

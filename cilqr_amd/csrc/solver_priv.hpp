@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/cilqr.h"
+#include "hip_owned.hpp"
 #include "state.hpp"
 
 extern thread_local char g_last_hip_error[256];
@@ -51,24 +52,20 @@ struct cilqr_job_set {
   double* lanes_raw = nullptr;      // device [2*smax][7]
   std::vector<double> lane_cache;   // the lane tables whose device image and grid are current (left rows, then right rows)
   int lane_cache_nl = -1, lane_cache_nr = -1;
-  int* h_count = nullptr;           // pinned, written by k_update through h_count_dev
+  cilqr::pinned_mem h_count;        // int, mapped: written by k_update through h_count_dev
   int* h_count_dev = nullptr;
   int* tail_iter_dev = nullptr;     // largest iteration count reached inside the tail kernel
   // host arrays (CILQR_MEM_HOST) on the way out: the staging of ONE solve in flight (the way in: cilqr_in_buffer)
-  void* out_stage = nullptr;        // problem-major results on the device when the caller's buffers are host memory
-  size_t out_stage_bytes = 0;
-  void* out_pinned = nullptr;       // small host batches: the staging block lands here in one copy
-  long long* row_off = nullptr;     // device [B + 1]: first packed Cost row of every problem, total (large host batches)
-  size_t row_off_bytes = 0;
-  void* host_counts = nullptr;      // pinned: n_cost | status | n_iter | n_iter_trajs of a large host batch
-  size_t host_counts_bytes = 0;
-  void* host_rows = nullptr;        // pinned: its LIVE Cost rows, packed (scattered into the caller's dense array on the host)
-  size_t host_rows_bytes = 0;
-  hipEvent_t exported = nullptr;    // recorded on the solve's stream behind its last kernel (what the download stream waits for)
-  std::vector<hipEvent_t> iter_ev;  // one per lockstep iteration (count read-back)
-  std::vector<hipEvent_t> ev;       // profiling
-  hipEvent_t handoff = nullptr;     // survivors copied into the finishing arena (recorded on the first stage's stream)
-  hipEvent_t sync_ev = nullptr;     // what a relaxed host wait for a whole stream polls (solver.hip: wait_stream)
+  cilqr::dev_mem out_stage;         // problem-major results on the device when the caller's buffers are host memory
+  cilqr::pinned_mem out_pinned;     // small host batches: the staging block lands here in one copy
+  cilqr::dev_mem row_off;           // long long [B + 1]: first packed Cost row of every problem, total (large host batches)
+  cilqr::pinned_mem host_counts;    // n_cost | status | n_iter | n_iter_trajs of a large host batch
+  cilqr::pinned_mem host_rows;      // its LIVE Cost rows, packed (scattered into the caller's dense array on the host)
+  cilqr::hip_event exported;        // recorded on the solve's stream behind its last kernel (what the download stream waits for)
+  std::vector<cilqr::hip_event> iter_ev;  // one per lockstep iteration (count read-back)
+  std::vector<cilqr::hip_event> ev;       // profiling
+  cilqr::hip_event handoff;         // survivors copied into the finishing arena (recorded on the first stage's stream)
+  cilqr::hip_event sync_ev;         // what a relaxed host wait for a whole stream polls (solver.hip: wait_stream)
 };
 
 struct cilqr_timer {  // event pairs around kernels / phases, resolved after the final sync
@@ -93,10 +90,9 @@ struct cilqr_timer {  // event pairs around kernels / phases, resolved after the
 // start of its upload until its load kernels are enqueued; two of them, so that the arrays of the NEXT solve travel while this
 // one iterates (solver.hip: worker_io_main).
 struct cilqr_in_buffer {
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipEvent_t ready = nullptr;    // recorded on the upload stream behind the last input copy
-  hipEvent_t loaded = nullptr;   // recorded on the solve's stream behind the load kernels that read the buffer
+  cilqr::dev_mem p;
+  cilqr::hip_event ready;        // recorded on the upload stream behind the last input copy
+  cilqr::hip_event loaded;       // recorded on the solve's stream behind the load kernels that read the buffer
   int state = 0;                 // 0 free; 1 owned by a solve; 2 given back: free once `loaded` has happened
 };
 
@@ -167,18 +163,21 @@ struct cilqr_solver {
   int fin_threshold = 0;     // hand the survivors over at this active count (CILQR_OPT_FINISH_THRESHOLD); 0 = never
   bool compaction = true;
   int compact_percent = 75;  // re-pack when the survivors fill at most this share of the occupied slots
-  hipStream_t own_stream = nullptr;
+  // (the streams are declared before every other owner: the handle's memory and events are released first)
+  cilqr::hip_stream own_stream;
   hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;   // finishing stage of asynchronous solves (high priority: short, latency-bound kernels)
-  hipStream_t stream_in = nullptr;   // host arrays: uploads of submitted solves (the transfer thread), beside the solves' kernels
-  hipStream_t stream_out = nullptr;  // host arrays: downloads of finished solves, so that the next solve's kernels need not queue behind them
-  std::vector<void*> allocs;
+  cilqr::hip_stream stream2;     // finishing stage of asynchronous solves (high priority: short, latency-bound kernels)
+  cilqr::hip_stream stream_in;   // host arrays: uploads of submitted solves (the transfer thread), beside the solves' kernels
+  cilqr::hip_stream stream_out;  // host arrays: downloads of finished solves, so that the next solve's kernels need not queue behind them
+  std::vector<cilqr::dev_mem> allocs;   // the arenas and the job sets' tensors (cilqr_create)
   int64_t bytes = 0;
-  std::atomic<int64_t> grown_bytes{0};   // staging blocks + tail workspaces, grown by the solving threads (solver.hip: grow)
-  void* in_small = nullptr;         // small host batches: their device block (the large ones: in_bufs)
-  size_t in_small_bytes = 0;
-  void* in_pinned = nullptr;        // small host batches: the input arrays leave from here in one copy
-  hipEvent_t in_pinned_ev = nullptr;
+  // the lazily grown device blocks (staging, tail workspaces): their sizes belong to the thread that grows them; what another
+  // thread may ask for at any time -- cilqr_device_bytes -- is this sum, kept by hip_mem::grow (found by the ThreadSanitizer
+  // run of tools/tsan_run.sh: the sizes themselves used to be read there)
+  std::atomic<int64_t> grown_bytes{0};
+  cilqr::dev_mem in_small;          // small host batches: their device block (the large ones: in_bufs)
+  cilqr::pinned_mem in_pinned;      // small host batches: the input arrays leave from here in one copy
+  cilqr::hip_event in_pinned_ev;
   cilqr_job_set sets[2];
   bool set_busy[2] = {false, false};   // (under mu) a submitted solve runs on the set
   cilqr_in_buffer in_bufs[2];
@@ -204,10 +203,8 @@ struct cilqr_solver {
   // fewer: 256 until round 5, 128 since (profiles/r05_cost_kernel_experiments.txt 6)
   int tail_threshold = 1024;
   int tail_threshold_submit = 128;
-  void* tail_ws = nullptr;    // private arenas of the tail's problems (lazily grown)
-  size_t tail_ws_bytes = 0;
-  void* tail_ws1 = nullptr;   // the same for a solve that reaches the tail without having been handed over (first stage)
-  size_t tail_ws1_bytes = 0;
+  cilqr::dev_mem tail_ws;     // private arenas of the tail's problems (lazily grown)
+  cilqr::dev_mem tail_ws1;    // the same for a solve that reaches the tail without having been handed over (first stage)
   // asynchronous submit / wait: two jobs in flight, one worker thread per stage
   std::thread worker1, worker2, worker_io;
   std::mutex io_mu;           // creation of stream_in / stream_out (solver.hip: io_streams)
@@ -223,8 +220,8 @@ struct cilqr_solver {
   int profiling_level = 1;
   cilqr_profile prof;         // of the last solve that completed
   cilqr_comm* comm = nullptr;   // multi-GPU results gather (cilqr_comm_create)
-  int* cor_fail = nullptr;        // cilqr_build_corridors: failure counter on the device, where it lands on the host, its event
-  int* cor_fail_host = nullptr;
-  hipEvent_t cor_done = nullptr;
+  cilqr::dev_mem cor_fail;        // cilqr_build_corridors: failure counter on the device, where it lands on the host, its event
+  cilqr::pinned_mem cor_fail_host;
+  cilqr::hip_event cor_done;
   cilqr::TrackerParams tracker;   // CILQR_INIT_TRACKER
 };
