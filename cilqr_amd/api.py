@@ -28,7 +28,7 @@ OPT_ROUND_GROUP = 7
 OPT_FINISH_THRESHOLD = 8
 OPT_EXACT_LANE_TIES = 9
 ST_RUNNING, ST_CONVERGED_ABS, ST_CONVERGED_REL, ST_GNORM, ST_UNSOLVED, ST_MAX_ITER, ST_NO_CORRIDOR = range(7)
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 T_GOALS, T_CORRIDOR, T_LANES, T_X, T_U, T_XCAND, T_UCAND, T_A, T_B, T_LX, T_LU, T_LXX, T_LUU, \
     T_KFB, T_KFF, T_DV, T_GNORM = range(17)
@@ -96,7 +96,19 @@ class SceneStruct(C.Structure):
                 ("dynamic_trajectories", C.c_void_p), ("dynamic_trajectory_counts", C.c_void_p)]
 
 
+class SceneBatchStruct(C.Structure):
+    """cilqr_scene_batch (include/cilqr.h): one centre line, per scene a fixed number of padded obstacle slots."""
+    _fields_ = [("batch", C.c_int32), ("memory", C.c_int32), ("center", C.c_void_p), ("n_center", C.c_int32),
+                ("max_static", C.c_int32), ("max_dynamic", C.c_int32), ("max_vertices", C.c_int32),
+                ("max_samples", C.c_int32), ("reserved0", C.c_int32),
+                ("static_points", C.c_void_p), ("static_counts", C.c_void_p),
+                ("dynamic_polygon_points", C.c_void_p), ("dynamic_polygon_counts", C.c_void_p),
+                ("dynamic_trajectories", C.c_void_p), ("dynamic_trajectory_counts", C.c_void_p)]
+
+
 COARSE_FIELDS = 9   # time, s, x, y, theta, kappa, velocity, a, delta
+# limits of cilqr_dp_plan_batch's fixed-size storage (CILQR_DP_MAX_* of include/cilqr.h)
+DP_MAX_VERTICES, DP_MAX_STATIC, DP_MAX_DYNAMIC, DP_MAX_SAMPLES, DP_MAX_KNOTS = 8, 32, 32, 1024, 256
 
 
 class TrackerConfig(C.Structure):
@@ -126,7 +138,7 @@ EXPORTS = [
     "cilqr_stage_total_cost", "cilqr_stage_quadratize", "cilqr_stage_backward", "cilqr_stage_forward",
     "cilqr_stage_read", "cilqr_stage_nearest_lane", "cilqr_open_loop_rollout", "cilqr_error_string",
     "cilqr_default_corridor_config", "cilqr_build_corridors", "cilqr_lane_constraints",
-    "cilqr_default_dp_config", "cilqr_dp_plan", "cilqr_road_barriers", "cilqr_default_tracker_config",
+    "cilqr_default_dp_config", "cilqr_dp_plan", "cilqr_dp_plan_batch", "cilqr_road_barriers", "cilqr_default_tracker_config",
     "cilqr_set_tracker_config",
     "cilqr_multi_create", "cilqr_multi_destroy", "cilqr_multi_solve", "cilqr_multi_set_option", "cilqr_multi_shards",
     "cilqr_multi_device_bytes",
@@ -191,6 +203,8 @@ def lib():
         L.cilqr_default_dp_config.argtypes = [C.POINTER(DpConfig)]
         L.cilqr_default_dp_config.restype = None
         L.cilqr_dp_plan.argtypes = [C.POINTER(DpConfig), C.POINTER(SceneStruct), C.c_void_p, C.c_void_p, C.c_int32]
+        L.cilqr_dp_plan_batch.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(SceneBatchStruct), C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.cilqr_default_tracker_config.argtypes = [C.POINTER(TrackerConfig)]
         L.cilqr_default_tracker_config.restype = None
         L.cilqr_set_tracker_config.argtypes = [C.c_void_p, C.POINTER(TrackerConfig)]
@@ -504,6 +518,34 @@ class BatchIlqrOptimizer:
                                           polygons_ptr)
         return rc, int(nf.value)
 
+    def dp_plan_batch(self, packed: dict, start3, cfg: "DpConfig | None" = None):
+        """DpPlanner::Plan for a batch of scenes on the GPU (cilqr_dp_plan_batch), host arrays.  `packed` =
+        cilqr_amd.scene_io.pack_scene_batch(center, scenes), start3 [B,3] = x, y, theta.  Returns dict(dp [B,K,9] = time s x
+        y theta kappa velocity a delta, coarse [B,K,6], knots [B,K,3], station [B,K], found [B] bool, n_not_found); a
+        scene with found = False is the reference's "DP failed", its rows are filled all the same."""
+        cfg = cfg or default_dp_config()
+        B = int(packed["batch"])
+        K = max(1, int(cfg.tf / cfg.delta_t + 1)) if cfg.delta_t > 0 else 1
+        keep = {k: np.ascontiguousarray(v) for k, v in packed.items() if isinstance(v, np.ndarray)}
+        sb = scene_batch_struct(packed, MEM_HOST, **{k: _ptr(keep[k]) for k in _SCENE_BATCH_ARRAYS})
+        start = _f64(np.asarray(start3)[:, :3])
+        if start.shape != (B, 3):
+            raise ValueError(f"start3 must be [{B}, 3]")
+        dp, coarse, knots = np.zeros((B, K, COARSE_FIELDS)), np.zeros((B, K, 6)), np.zeros((B, K, 3))
+        station, found = np.zeros((B, K)), np.zeros(B, dtype=np.int32)
+        rc, nnf = self.dp_plan_batch_raw(cfg, sb, _ptr(start), K, _ptr(dp), _ptr(coarse), _ptr(knots), _ptr(station),
+                                         _ptr(found))
+        self._chk(rc, "dp_plan_batch")
+        return dict(dp=dp, coarse=coarse, knots=knots, station=station, found=found.astype(bool), n_not_found=nnf)
+
+    def dp_plan_batch_raw(self, cfg, scene_batch, start_ptr, n_knots, coarse9_ptr, coarse6_ptr, knots3_ptr, station_ptr,
+                          found_ptr):
+        """Pointer-level form (device or host memory as scene_batch.memory says); returns (rc, n_not_found)."""
+        nnf = C.c_int32(0)
+        rc = self.L.cilqr_dp_plan_batch(self.h, C.byref(cfg), C.byref(scene_batch), start_ptr, n_knots, coarse9_ptr,
+                                        coarse6_ptr, knots3_ptr, station_ptr, found_ptr, C.byref(nnf))
+        return rc, int(nnf.value)
+
     def open_loop_rollout(self, x0, U):
         x0, U = _f64(x0), _f64(U)
         B = x0.shape[0]
@@ -538,6 +580,22 @@ def dp_plan(flat: dict, start3, cfg: "DpConfig | None" = None):
     if rc not in (OK, ERR_NO_PATH):
         raise CilqrError(rc, "in cilqr_dp_plan")
     return rc == OK, coarse
+
+
+_SCENE_BATCH_ARRAYS = ("static_points", "static_counts", "dynamic_polygon_points", "dynamic_polygon_counts",
+                       "dynamic_trajectories", "dynamic_trajectory_counts")
+
+
+def scene_batch_struct(packed: dict, memory: int, **pointers) -> SceneBatchStruct:
+    """cilqr_scene_batch for the sizes of `packed` (scene_io.pack_scene_batch) with the per-problem arrays at `pointers`
+    (one per name of _SCENE_BATCH_ARRAYS: host or device addresses, as `memory` says); the centre line is always the
+    host array of `packed`, which must stay alive as long as the struct is used."""
+    center = packed["center"]
+    if not (center.dtype == np.float64 and center.flags.c_contiguous):
+        raise ValueError("packed['center'] must be a C-contiguous float64 array")
+    return SceneBatchStruct(int(packed["batch"]), memory, center.ctypes.data, center.shape[0], int(packed["max_static"]),
+                            int(packed["max_dynamic"]), int(packed["max_vertices"]), int(packed["max_samples"]), 0,
+                            *[pointers[k] for k in _SCENE_BATCH_ARRAYS])
 
 
 def road_barriers(center):

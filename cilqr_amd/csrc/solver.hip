@@ -462,7 +462,7 @@ const char* cilqr_error_string(int code) {
     case CILQR_ERR_NULL: return "null pointer";
     case CILQR_ERR_CONSTRAINTS: return "ilqr input constraints error";
     case CILQR_ERR_KNOTS: return "ilqr input coarse_traj error";
-    case CILQR_ERR_CAPACITY: return "batch / cmax / lane segments exceed the capacity given to cilqr_create";
+    case CILQR_ERR_CAPACITY: return "batch / cmax / lane segments exceed the capacity given to cilqr_create, or a size exceeds a fixed limit of the entry point";
     case CILQR_ERR_DEVICE: return g_last_hip_error[0] ? g_last_hip_error : "HIP runtime error";
     case CILQR_ERR_ARG: return "invalid argument";
     case CILQR_ERR_STATE: return "stage called out of order";

@@ -224,4 +224,10 @@ struct cilqr_solver {
   cilqr::pinned_mem cor_fail_host;
   cilqr::hip_event cor_done;
   cilqr::TrackerParams tracker;   // CILQR_INIT_TRACKER
+  // cilqr_dp_plan_batch (planner_batch.hip): blocks that grow to the largest call -- the road's tables on their way to the
+  // device, the placed dynamic polygons of a chunk of scenes, the staging of HOST arrays -- and the count's way back
+  cilqr::pinned_mem dp_tab_host;
+  cilqr::dev_mem dp_tab, dp_placed, dp_in, dp_out;
+  cilqr::dev_mem dp_fail;
+  cilqr::pinned_mem dp_fail_host;
 };

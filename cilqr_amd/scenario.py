@@ -420,7 +420,7 @@ def _generate_chunk(spec: SceneSpec, B: int, seed: int, first: int, road: Road, 
 
 
 def generate_dp(spec: SceneSpec | str, batch: int, seed: int = 0, first_problem: int = 0, workers: int = 8,
-                dp_config=None):
+                dp_config=None, planner: str = "host", device: int = 0):
     """Scenes whose coarse trajectory comes from the DP coarse planner (the reference's own producer,
     algorithm/planner/dp_planner.cpp, through the C-ABI's cilqr_dp_plan) instead of this module's smooth
     best-clearance pick: every obstacle stays in the scene (the planner avoids them itself), the start state is the
@@ -429,7 +429,10 @@ def generate_dp(spec: SceneSpec | str, batch: int, seed: int = 0, first_problem:
     Returns dict(start[B,4], coarse[B,K,6] (x, y, theta, v, a, delta), dp[B,K,9] (the planner's full rows), found[B]
     bool ("DP failed" where False), obstacle_points[B,K,P,2], obstacle_count[B,K], left, right, n_steps, dt, cmax,
     scene_file).  There is no `corridor`: it is built from the obstacle points by cilqr_build_corridors
-    (BatchIlqrOptimizer.build_corridors), as Corridor::Plan does behind the reference's DP."""
+    (BatchIlqrOptimizer.build_corridors), as Corridor::Plan does behind the reference's DP.
+
+    planner = "host": one cilqr_dp_plan per scene on a pool of `workers` threads; "device": the whole batch in one
+    cilqr_dp_plan_batch on GPU `device` (the same lattice path; x, y and the headings agree to rounding)."""
     from concurrent.futures import ThreadPoolExecutor
     from . import api, scene_io
     if isinstance(spec, str):
@@ -440,14 +443,21 @@ def generate_dp(spec: SceneSpec | str, batch: int, seed: int = 0, first_problem:
     sf = scene_io.from_generator(sc)
     cfg = dp_config or api.default_dp_config(tf=spec.n_steps * spec.dt, delta_t=spec.dt)
 
-    def one(b):
-        flat = scene_io.flatten_scene(sf.center, sf.scenes[b])
-        return api.dp_plan(flat, sc["start"][b, :3], cfg)
+    if planner == "device":
+        with api.BatchIlqrOptimizer(n_steps=spec.n_steps, device=device, batch_capacity=1, cmax=spec.cmax) as opt:
+            r = opt.dp_plan_batch(scene_io.pack_scene_batch(sf.center, sf.scenes), sc["start"][:, :3], cfg)
+        dp, found = r["dp"], r["found"].copy()
+    elif planner == "host":
+        def one(b):
+            flat = scene_io.flatten_scene(sf.center, sf.scenes[b])
+            return api.dp_plan(flat, sc["start"][b, :3], cfg)
 
-    with ThreadPoolExecutor(max(1, workers)) as pool:
-        outs = list(pool.map(one, range(batch)))
-    dp = np.stack([o[1] for o in outs])
-    found = np.array([o[0] for o in outs], dtype=bool)
+        with ThreadPoolExecutor(max(1, workers)) as pool:
+            outs = list(pool.map(one, range(batch)))
+        dp = np.stack([o[1] for o in outs])
+        found = np.array([o[0] for o in outs], dtype=bool)
+    else:
+        raise ValueError(f"planner must be 'host' or 'device', not {planner!r}")
     # a plan that stands still for a whole layer has 0 / 0 curvature (ComputePathProfile divides by the station
     # difference of neighbouring points): as unusable as a failed plan
     found &= np.isfinite(dp).all(axis=(1, 2))

@@ -219,6 +219,73 @@ def flatten_scene(center: np.ndarray, scene: Scene) -> dict:
         dynamic_trajectory_counts=np.asarray([len(d.trajectory) for d in scene.dynamic], dtype=np.int32))
 
 
+def pack_scene_batch(center: np.ndarray, scenes: list, max_static: "int | None" = None, max_dynamic: "int | None" = None,
+                     max_vertices: "int | None" = None, max_samples: "int | None" = None) -> dict:
+    """A list of scenes on one road as the C-ABI's `cilqr_scene_batch` takes it (include/cilqr.h): a fixed number of
+    obstacle slots per scene, every polygon padded to max_vertices vertices and every trajectory to max_samples samples
+    (zeros), a count per slot -- 0 vertices = slot unused.  The max_* default to the largest the scenes need (at least 1);
+    a scene that needs more than a given max_* is refused.  Returns dict(batch, max_static, max_dynamic, max_vertices,
+    max_samples, center [n,7], static_points [B,S,V,2], static_counts [B,S], dynamic_polygon_points [B,D,V,2],
+    dynamic_polygon_counts [B,D], dynamic_trajectories [B,D,T,4], dynamic_trajectory_counts [B,D])."""
+    B = len(scenes)
+    statics = [[np.asarray(p, float).reshape(-1, 2) for p in sc.static] for sc in scenes]
+    dyns = [[(np.asarray(d.polygon, float).reshape(-1, 2), np.asarray(d.trajectory, float).reshape(-1, 4)) for d in sc.dynamic]
+            for sc in scenes]
+    need = dict(
+        max_static=max((len(s) for s in statics), default=0),
+        max_dynamic=max((len(d) for d in dyns), default=0),
+        max_vertices=max([len(p) for s in statics for p in s] + [len(p) for d in dyns for p, _ in d], default=0),
+        max_samples=max((len(t) for d in dyns for _, t in d), default=0))
+    given = dict(max_static=max_static, max_dynamic=max_dynamic, max_vertices=max_vertices, max_samples=max_samples)
+    size = {}
+    for k, n in need.items():
+        if given[k] is None:
+            size[k] = max(1, n)
+        elif n > given[k]:
+            worst = {"max_static": lambda b: len(statics[b]), "max_dynamic": lambda b: len(dyns[b]),
+                     "max_vertices": lambda b: max([len(p) for p in statics[b]] + [len(p) for p, _ in dyns[b]], default=0),
+                     "max_samples": lambda b: max((len(t) for _, t in dyns[b]), default=0)}[k]
+            b = max(range(B), key=worst)
+            raise ValueError(f"scene {b} needs {k} = {n}, the batch is packed with {k} = {given[k]}")
+        else:
+            size[k] = int(given[k])
+    for b in range(B):
+        for p in statics[b] + [p for p, _ in dyns[b]]:
+            if len(p) < 1:
+                raise ValueError(f"scene {b} holds a polygon without vertices (0 vertices marks an unused slot)")
+    S, D, V, T = size["max_static"], size["max_dynamic"], size["max_vertices"], size["max_samples"]
+    out = dict(batch=B, center=np.ascontiguousarray(center, dtype=np.float64), **size,
+               static_points=np.zeros((B, S, V, 2)), static_counts=np.zeros((B, S), dtype=np.int32),
+               dynamic_polygon_points=np.zeros((B, D, V, 2)), dynamic_polygon_counts=np.zeros((B, D), dtype=np.int32),
+               dynamic_trajectories=np.zeros((B, D, T, 4)), dynamic_trajectory_counts=np.zeros((B, D), dtype=np.int32))
+    for b in range(B):
+        for o, p in enumerate(statics[b]):
+            out["static_points"][b, o, :len(p)] = p
+            out["static_counts"][b, o] = len(p)
+        for o, (p, t) in enumerate(dyns[b]):
+            out["dynamic_polygon_points"][b, o, :len(p)] = p
+            out["dynamic_polygon_counts"][b, o] = len(p)
+            out["dynamic_trajectories"][b, o, :len(t)] = t
+            out["dynamic_trajectory_counts"][b, o] = len(t)
+    return out
+
+
+def unpack_scene(packed: dict, b: int) -> dict:
+    """Scene b of pack_scene_batch's arrays in the form of flatten_scene (the used slots, back to back)."""
+    def cat(arrs, width):
+        return np.ascontiguousarray(np.concatenate(arrs, axis=0) if arrs else np.zeros((0, width)), dtype=np.float64)
+    sc, dc, tc = packed["static_counts"][b], packed["dynamic_polygon_counts"][b], packed["dynamic_trajectory_counts"][b]
+    so, do = np.flatnonzero(sc > 0), np.flatnonzero(dc > 0)
+    return dict(
+        center=packed["center"],
+        static_points=cat([packed["static_points"][b, o, :sc[o]] for o in so], 2),
+        static_counts=sc[so].astype(np.int32),
+        dynamic_polygon_points=cat([packed["dynamic_polygon_points"][b, o, :dc[o]] for o in do], 2),
+        dynamic_polygon_counts=dc[do].astype(np.int32),
+        dynamic_trajectories=cat([packed["dynamic_trajectories"][b, o, :tc[o]] for o in do], 4),
+        dynamic_trajectory_counts=tc[do].astype(np.int32))
+
+
 # ---------------------------------------------------------------------------------------------
 # the reference's own scene artefact: reference.pickle
 # ---------------------------------------------------------------------------------------------

@@ -23,6 +23,8 @@
  *       nearest_lane    FindNeastLaneSegment cc:605-618 + LineSegment2d::DistanceTo (algorithm/math/line_segment2d.cpp:61-75)
  *   cilqr_open_loop_rollout ilqr::iLQR::OpenLoopRollout (algorithm/slover/ilqr.h:363-370) on
  *                           VehicleModel::Dynamics (vehicle_model.cc:88-121)
+ *   cilqr_dp_plan           DpPlanner::Plan + ComputePathProfile (algorithm/planner/dp_planner.cpp:135-281), one scene
+ *                           on the host; cilqr_dp_plan_batch: B scenes per call on the GPU
  *
  * Layout convention: every per-problem array is problem-major ("[B][...]"), IEEE fp64,
  * in host or device memory as flagged by `memory`.
@@ -36,7 +38,7 @@
 extern "C" {
 #endif
 
-#define CILQR_ABI_VERSION 6
+#define CILQR_ABI_VERSION 7
 
 #define CILQR_NX 6  /* state  (x, y, theta, v, a, delta)   vehicle_model.h:11 */
 #define CILQR_NU 2  /* control (jerk, delta_rate)           vehicle_model.h:12 */
@@ -367,7 +369,7 @@ int cilqr_device_math(cilqr_handle h, int32_t fn, int32_t n, const double* in, d
 int cilqr_open_loop_rollout(cilqr_handle h, int32_t batch, const double* x0, const double* U,
                             double* X, int32_t memory);
 
-/* ---- coarse trajectory: the producer of `coarse` / `start`, host only ----
+/* ---- coarse trajectory: the producer of `coarse` / `start`; one scene on the host ----
  * DpPlanner::Plan (algorithm/planner/dp_planner.cpp:135-281): 5 x 7 x 10 (time, station, lateral) sampling DP in
  * the Frenet frame of the centre line with collision checks against the scene, then ComputePathProfile
  * (algorithm/utils/discrete_points_math.cc:27-176).  C++ callers use include/cilqr/dp_planner.hpp directly;
@@ -405,6 +407,53 @@ int cilqr_road_barriers(const double* center, int32_t n_center, double* left, do
  * the reference, whose caller then stops: trajectory_planner.cpp:32-35). */
 int cilqr_dp_plan(const cilqr_dp_config* cfg, const cilqr_scene* scene, const double* start3, double* coarse,
                   int32_t n_knots);
+
+/* ---- the same planner for B scenes per call, on the GPU (ABI 7) ----
+ * One road (centre line) for the whole batch, as the lane tables of cilqr_problem_batch are; per scene a fixed number of
+ * obstacle slots, every polygon stored with max_vertices vertices and every trajectory with max_samples samples
+ * (cilqr_amd.scene_io.pack_scene_batch pads a list of scenes into this form).  A slot whose vertex count is 0 is unused.
+ * Limits of the kernel's fixed-size storage (CILQR_ERR_CAPACITY beyond them): */
+#define CILQR_DP_MAX_VERTICES 8      /* vertices per polygon */
+#define CILQR_DP_MAX_STATIC 32       /* static obstacle slots per scene */
+#define CILQR_DP_MAX_DYNAMIC 32      /* dynamic obstacle slots per scene */
+#define CILQR_DP_MAX_SAMPLES 1024    /* trajectory samples per dynamic obstacle */
+#define CILQR_DP_MAX_KNOTS 256       /* n_knots, and the path samples of the five layers together */
+typedef struct cilqr_scene_batch {
+  int32_t batch, memory;            /* CILQR_MEM_* of every per-problem array below */
+  const double* center;             /* [n_center][7], HOST memory, ONE centre line for the batch */
+  int32_t n_center;
+  int32_t max_static, max_dynamic;  /* obstacle slots per scene (0: none, the arrays of that kind may be NULL) */
+  int32_t max_vertices;             /* vertices stored per polygon */
+  int32_t max_samples;              /* trajectory samples stored per dynamic obstacle */
+  int32_t reserved0;
+  const double*  static_points;     /* [B][max_static][max_vertices][2] world frame */
+  const int32_t* static_counts;     /* [B][max_static] vertices; 0 = slot unused */
+  const double*  dynamic_polygon_points;    /* [B][max_dynamic][max_vertices][2] body frame */
+  const int32_t* dynamic_polygon_counts;    /* [B][max_dynamic]; 0 = slot unused */
+  const double*  dynamic_trajectories;      /* [B][max_dynamic][max_samples][4] time x y theta */
+  const int32_t* dynamic_trajectory_counts; /* [B][max_dynamic]; 0 samples: the obstacle is never there (as in cilqr_dp_plan) */
+} cilqr_scene_batch;
+/* cilqr_dp_plan for every scene of the batch, one workgroup per scene (kernels_dp.hip).  Per scene the semantics are
+ * those of cilqr_dp_plan: the trajectory is filled whether or not a collision-free path exists (found[b] = 0 is its
+ * CILQR_ERR_NO_PATH), a plan that stands still for a layer carries the same 0 / 0 = NaN curvature.  The lattice path,
+ * every cost, the station and the time column are the host planner's bit for bit; x, y, the headings and what is
+ * differenced from them go through the device's sin / cos / atan and agree to rounding.
+ *   start3  [B][3] x y theta                         (memory as scenes->memory, like every array below)
+ *   coarse9 [B][K][CILQR_COARSE_FIELDS]              optional (NULL to skip)
+ *   coarse6 [B][K][6] x y theta velocity a delta     optional: cilqr_problem_batch::coarse
+ *   knots3  [B][K][3] x y theta                      optional: the `knots` input of cilqr_build_corridors
+ *   station [B][K]                                   optional: cilqr_problem_batch::coarse_station
+ *   found   [B] 1 / 0;  *n_not_found (HOST, optional): how many are 0
+ * Runs on the handle's stream and waits for that stream only (the count has to come back); its work space belongs to
+ * the handle and grows to the largest call, nothing is allocated in steady state.  CILQR_ERR_STATE while solves are
+ * submitted on the handle.  Checked before anything is launched: CILQR_ERR_NULL; CILQR_ERR_ARG for batch < 1,
+ * n_center < 2, non-positive tf / delta_t, negative sizes, max_vertices < 1 with slots to fill and -- HOST arrays -- a
+ * count that is negative or above its max_*; CILQR_ERR_KNOTS; CILQR_ERR_CAPACITY beyond the limits above.  With DEVICE arrays
+ * the counts are checked in the kernel: such a scene is reported as not found, its rows are zero, the others are
+ * unaffected.  Non-finite coordinates are no error: the arithmetic is the host planner's, the result deterministic. */
+int cilqr_dp_plan_batch(cilqr_handle h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes,
+                        const double* start3, int32_t n_knots, double* coarse9, double* coarse6, double* knots3,
+                        double* station, int32_t* found, int32_t* n_not_found);
 
 /* ---- several GPUs from ONE host process (the reference's caller is one process:
  * algorithm/planning_node.cc:9-31) ----

@@ -223,6 +223,11 @@ class DpEnvironment {
   }
 
   const ReferenceLine& reference() const { return ref_; }
+  // what the batched device planner (cilqr_dp_plan_batch) takes over as tables, built here once per call
+  const std::vector<DpPoint2>& barrier() const { return barrier_; }
+  double disc_radius() const { return radius_; }
+  double rear_disc_x() const { return r2x_; }
+  double front_disc_x() const { return f2x_; }
 
   void AddStatic(const std::vector<DpPoint2>& world_polygon) { statics_.push_back(MakePoly(world_polygon)); }
 
@@ -439,6 +444,12 @@ class DpPlanner {
   }
 
   int segment_points(int layer) const { return nseg_[layer]; }
+  // the lattice as the constructor laid it out (the tables of cilqr_dp_plan_batch)
+  double unit_time() const { return unit_time_; }
+  double safe_margin() const { return safe_margin_; }
+  double layer_time(int layer) const { return time_[layer]; }
+  double station_step(int si) const { return station_[si]; }
+  double lateral_fraction(int li) const { return lateral_[li]; }
 
  private:
   struct Cell {
