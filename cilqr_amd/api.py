@@ -27,6 +27,7 @@ OPT_WAVE_THRESHOLD = 6
 OPT_ROUND_GROUP = 7
 OPT_FINISH_THRESHOLD = 8
 OPT_EXACT_LANE_TIES = 9
+OPT_SCENE_CHUNK = 10
 ST_RUNNING, ST_CONVERGED_ABS, ST_CONVERGED_REL, ST_GNORM, ST_UNSOLVED, ST_MAX_ITER, ST_NO_CORRIDOR = range(7)
 ABI_VERSION = 7
 
@@ -109,6 +110,8 @@ class SceneBatchStruct(C.Structure):
 COARSE_FIELDS = 9   # time, s, x, y, theta, kappa, velocity, a, delta
 # limits of cilqr_dp_plan_batch's fixed-size storage (CILQR_DP_MAX_* of include/cilqr.h)
 DP_MAX_VERTICES, DP_MAX_STATIC, DP_MAX_DYNAMIC, DP_MAX_SAMPLES, DP_MAX_KNOTS = 8, 32, 32, 1024, 256
+PLAN_FIELDS = 11    # time, s, x, y, theta, kappa, velocity, a, delta, jerk, delta_rate (cilqr_plan_scenes_batch)
+PLAN_OK, PLAN_DP_FAILED, PLAN_CORRIDOR_FAILED = 0, 1, 2
 
 
 class TrackerConfig(C.Structure):
@@ -138,7 +141,8 @@ EXPORTS = [
     "cilqr_stage_total_cost", "cilqr_stage_quadratize", "cilqr_stage_backward", "cilqr_stage_forward",
     "cilqr_stage_read", "cilqr_stage_nearest_lane", "cilqr_open_loop_rollout", "cilqr_error_string",
     "cilqr_default_corridor_config", "cilqr_build_corridors", "cilqr_lane_constraints",
-    "cilqr_default_dp_config", "cilqr_dp_plan", "cilqr_dp_plan_batch", "cilqr_road_barriers", "cilqr_default_tracker_config",
+    "cilqr_default_dp_config", "cilqr_dp_plan", "cilqr_dp_plan_batch", "cilqr_scene_points_batch", "cilqr_plan_scenes_batch",
+    "cilqr_road_barriers", "cilqr_default_tracker_config",
     "cilqr_set_tracker_config",
     "cilqr_multi_create", "cilqr_multi_destroy", "cilqr_multi_solve", "cilqr_multi_set_option", "cilqr_multi_shards",
     "cilqr_multi_device_bytes",
@@ -205,6 +209,11 @@ def lib():
         L.cilqr_dp_plan.argtypes = [C.POINTER(DpConfig), C.POINTER(SceneStruct), C.c_void_p, C.c_void_p, C.c_int32]
         L.cilqr_dp_plan_batch.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(SceneBatchStruct), C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+        L.cilqr_scene_points_batch.argtypes = [C.c_void_p, C.POINTER(SceneBatchStruct), C.c_int32, C.c_void_p, C.c_int32,
+                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cilqr_plan_scenes_batch.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(CorridorConfig),
+                                              C.POINTER(SceneBatchStruct), C.c_void_p, C.c_int32, C.POINTER(SolutionBatch),
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.cilqr_default_tracker_config.argtypes = [C.POINTER(TrackerConfig)]
         L.cilqr_default_tracker_config.restype = None
         L.cilqr_set_tracker_config.argtypes = [C.c_void_p, C.POINTER(TrackerConfig)]
@@ -545,6 +554,68 @@ class BatchIlqrOptimizer:
         rc = self.L.cilqr_dp_plan_batch(self.h, C.byref(cfg), C.byref(scene_batch), start_ptr, n_knots, coarse9_ptr,
                                         coarse6_ptr, knots3_ptr, station_ptr, found_ptr, C.byref(nnf))
         return rc, int(nnf.value)
+
+    def scene_points(self, packed: dict, times, multiple_sample: bool = False, max_points: "int | None" = None):
+        """Environment::QueryStaticObstaclesPoints + QueryDynamicObstaclesPoints at every knot time for a batch of scenes on
+        the GPU (cilqr_scene_points_batch), host arrays.  `packed` = scene_io.pack_scene_batch(center, scenes), times [K]
+        one time axis for the batch.  Returns (points [B,K,max_points,2] -- the rows padded with zeros --, point_count
+        [B,K] int32, scene_ok [B] bool); max_points defaults to the worst case of the packed sizes."""
+        B = int(packed["batch"])
+        times = _f64(times).ravel()
+        K = times.size
+        if max_points is None:
+            max_points = (int(packed["max_static"]) + int(packed["max_dynamic"])) * int(packed["max_vertices"]) * \
+                (6 if multiple_sample else 1)
+        keep = {k: np.ascontiguousarray(v) for k, v in packed.items() if isinstance(v, np.ndarray)}
+        sb = scene_batch_struct(packed, MEM_HOST, **{k: _ptr(keep[k]) for k in _SCENE_BATCH_ARRAYS})
+        points = np.zeros((B, K, max_points, 2))
+        count, ok = np.zeros((B, K), dtype=np.int32), np.zeros(B, dtype=np.int32)
+        self._chk(self.scene_points_raw(sb, K, times, multiple_sample, max_points, _ptr(points) if max_points else None,
+                                        _ptr(count), _ptr(ok)), "scene_points")
+        return points, count, ok.astype(bool)
+
+    def scene_points_raw(self, scene_batch, n_knots, times, multiple_sample, max_points, points_ptr, count_ptr, ok_ptr=None):
+        """Pointer-level form (the outputs in device or host memory as scene_batch.memory says; `times` a host array)."""
+        times = _f64(times).ravel()
+        return self.L.cilqr_scene_points_batch(self.h, C.byref(scene_batch), n_knots, _ptr(times), int(bool(multiple_sample)),
+                                               max_points, points_ptr, count_ptr, ok_ptr)
+
+    def plan_scenes(self, packed: dict, start, dp_cfg: "DpConfig | None" = None, corridor_cfg: "CorridorConfig | None" = None,
+                    alpha_trace: bool = False):
+        """TrajectoryPlanner::Plan for a batch of scenes on the GPU (cilqr_plan_scenes_batch), host arrays: DP -> obstacle
+        points -> corridors (the handle's cmax) -> lane constraints -> solve -> result rows.  `packed` =
+        scene_io.pack_scene_batch(center, scenes), start [B,4] = x, y, theta, v.  Returns the dict of plan() plus plan
+        [B,K,11] = time s x y theta kappa velocity a delta jerk delta_rate, dp [B,K,9], outcome [B] int32 (PLAN_OK /
+        PLAN_DP_FAILED / PLAN_CORRIDOR_FAILED), n_dp_failed, n_corridor_failed."""
+        dp_cfg = dp_cfg or default_dp_config(tf=self.N * self.cfg.dt, delta_t=self.cfg.dt)
+        corridor_cfg = corridor_cfg or default_corridor_config()
+        B, K, M = int(packed["batch"]), self.K, self.cfg.max_iter
+        start = _f64(start)
+        if start.shape != (B, 4):
+            raise ValueError(f"start must be [{B}, 4]")
+        keep = {k: np.ascontiguousarray(v) for k, v in packed.items() if isinstance(v, np.ndarray)}
+        sb = scene_batch_struct(packed, MEM_HOST, **{k: _ptr(keep[k]) for k in _SCENE_BATCH_ARRAYS})
+        traj, hist = np.zeros((B, K, 10)), np.zeros((B, M + 1, 5))
+        n_cost, status, n_iter = (np.zeros(B, np.int32) for _ in range(3))
+        at = np.full((B, M), -3, np.int8) if alpha_trace else None
+        sol = SolutionBatch(MEM_HOST, 0, _ptr(traj), _ptr(hist), _ptr(n_cost), _ptr(status), _ptr(n_iter), None, None, _ptr(at))
+        plan, dp, outcome = np.zeros((B, K, PLAN_FIELDS)), np.zeros((B, K, COARSE_FIELDS)), np.zeros(B, np.int32)
+        rc, n_dp, n_cor = self.plan_scenes_raw(dp_cfg, corridor_cfg, sb, _ptr(start), K, sol, _ptr(plan), _ptr(dp), _ptr(outcome))
+        self._chk(rc, "plan_scenes")
+        self.B = B
+        return dict(rc=rc, traj=traj, cost_hist=hist, n_cost=n_cost, status=status, n_iter=n_iter, alpha_trace=at, plan=plan,
+                    dp=dp, outcome=outcome, n_dp_failed=n_dp, n_corridor_failed=n_cor)
+
+    def plan_scenes_raw(self, dp_cfg, corridor_cfg, scene_batch, start_ptr, n_knots, sol: SolutionBatch, plan_ptr=None,
+                        coarse9_ptr=None, outcome_ptr=None):
+        """Pointer-level form (start / plan / coarse9 / outcome in device or host memory as scene_batch.memory says, the
+        solver's outputs as sol.memory says); returns (rc, n_dp_failed, n_corridor_failed)."""
+        n_dp, n_cor = C.c_int32(0), C.c_int32(0)
+        rc = self.L.cilqr_plan_scenes_batch(self.h, C.byref(dp_cfg) if dp_cfg is not None else None,
+                                            C.byref(corridor_cfg) if corridor_cfg is not None else None, C.byref(scene_batch),
+                                            start_ptr, n_knots, C.byref(sol), plan_ptr, coarse9_ptr, outcome_ptr,
+                                            C.byref(n_dp), C.byref(n_cor))
+        return rc, int(n_dp.value), int(n_cor.value)
 
     def open_loop_rollout(self, x0, U):
         x0, U = _f64(x0), _f64(U)

@@ -36,6 +36,13 @@ bool host_counts_valid(const cilqr_scene_batch& sb) {
 extern "C" int cilqr_dp_plan_batch(cilqr_handle h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes,
                                    const double* start3, int32_t n_knots, double* coarse9, double* coarse6,
                                    double* knots3, double* station, int32_t* found, int32_t* n_not_found) {
+  return cilqr_dp_plan_batch_impl(h, cfg, scenes, start3, n_knots, coarse9, coarse6, knots3, station, found, n_not_found,
+                                  nullptr);
+}
+
+int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes, const double* start3,
+                             int32_t n_knots, double* coarse9, double* coarse6, double* knots3, double* station,
+                             int32_t* found, int32_t* n_not_found, double* times_out) {
   if (h == nullptr || cfg == nullptr || scenes == nullptr || start3 == nullptr || found == nullptr ||
       scenes->center == nullptr)
     return CILQR_ERR_NULL;
@@ -189,5 +196,7 @@ extern "C" int cilqr_dp_plan_batch(cilqr_handle h, const cilqr_dp_config* cfg, c
   HIP_TRY(hipMemcpyAsync(h->dp_fail_host.get(), d_fail, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));   // this stream alone: solves on other handles go on
   if (n_not_found) *n_not_found = *h->dp_fail_host.as<int>();
+  if (times_out)   // k_dp_plan's time column: knots past the path's samples stay zero
+    for (int k = 0; k < n_knots; ++k) times_out[k] = k < P.nq ? P.delta_t * k : 0.0;
   return CILQR_OK;
 }

@@ -707,6 +707,10 @@ int cilqr_set_option(cilqr_handle h, int32_t option, int64_t value) {
       if (value < 0) return CILQR_ERR_ARG;
       h->fin_threshold = (int)(value > h->fin_cap ? h->fin_cap : value);
       return CILQR_OK;
+    case CILQR_OPT_SCENE_CHUNK:
+      if (value < 0) return CILQR_ERR_ARG;
+      h->scene_chunk = (int)(value > 0x7fffffff ? 0x7fffffff : value);
+      return CILQR_OK;
     default:
       return CILQR_ERR_ARG;
   }
@@ -725,6 +729,7 @@ int cilqr_get_option(cilqr_handle h, int32_t option, int64_t* value, int64_t* va
     case CILQR_OPT_TAIL_THRESHOLD: v = h->tail_threshold; vs = h->tail_threshold_submit; break;
     case CILQR_OPT_EXACT_LANE_TIES: v = vs = h->ds.exact_ties; break;
     case CILQR_OPT_FINISH_THRESHOLD: v = vs = h->fin_threshold; break;
+    case CILQR_OPT_SCENE_CHUNK: v = vs = h->scene_chunk; break;
     default: return CILQR_ERR_ARG;
   }
   *value = v;

@@ -230,4 +230,15 @@ struct cilqr_solver {
   cilqr::dev_mem dp_tab, dp_placed, dp_in, dp_out;
   cilqr::dev_mem dp_fail;
   cilqr::pinned_mem dp_fail_host;
+  // cilqr_scene_points_batch / cilqr_plan_scenes_batch (scene_pipeline.hip), grown likewise: the knot times on their way to
+  // the device and the outcome counts' way back, the staging of HOST scenes and HOST outputs, the intermediates of the
+  // pipeline (coarse trajectory, corridors, ...) and the obstacle points of the chunk of scenes in flight
+  cilqr::pinned_mem sp_host;
+  cilqr::dev_mem sp_tab, sp_in, sp_out, ps_work, ps_points;
+  int scene_chunk = 0;            // CILQR_OPT_SCENE_CHUNK
 };
+
+// cilqr_dp_plan_batch (planner_batch.hip); times_out (HOST, [n_knots], optional): the time column every planned scene gets
+int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes, const double* start3,
+                             int32_t n_knots, double* coarse9, double* coarse6, double* knots3, double* station,
+                             int32_t* found, int32_t* n_not_found, double* times_out);

@@ -420,7 +420,7 @@ def _generate_chunk(spec: SceneSpec, B: int, seed: int, first: int, road: Road, 
 
 
 def generate_dp(spec: SceneSpec | str, batch: int, seed: int = 0, first_problem: int = 0, workers: int = 8,
-                dp_config=None, planner: str = "host", device: int = 0):
+                dp_config=None, planner: str = "host", device: int = 0, points: str = "host"):
     """Scenes whose coarse trajectory comes from the DP coarse planner (the reference's own producer,
     algorithm/planner/dp_planner.cpp, through the C-ABI's cilqr_dp_plan) instead of this module's smooth
     best-clearance pick: every obstacle stays in the scene (the planner avoids them itself), the start state is the
@@ -432,9 +432,14 @@ def generate_dp(spec: SceneSpec | str, batch: int, seed: int = 0, first_problem:
     (BatchIlqrOptimizer.build_corridors), as Corridor::Plan does behind the reference's DP.
 
     planner = "host": one cilqr_dp_plan per scene on a pool of `workers` threads; "device": the whole batch in one
-    cilqr_dp_plan_batch on GPU `device` (the same lattice path; x, y and the headings agree to rounding)."""
+    cilqr_dp_plan_batch on GPU `device` (the same lattice path; x, y and the headings agree to rounding).
+    points = "host": obstacle_points / obstacle_count as the generator computes them; "device": from the packed scenes by
+    cilqr_scene_points_batch on GPU `device` at the knot times k * dt (P is then the worst case of the packed batch, the
+    rows are padded with zeros; the same counts and, to rounding, the same points per knot, static polygons first)."""
     from concurrent.futures import ThreadPoolExecutor
     from . import api, scene_io
+    if points not in ("host", "device"):
+        raise ValueError(f"points must be 'host' or 'device', not {points!r}")
     if isinstance(spec, str):
         spec = SPECS[spec]
     spec = dataclasses.replace(spec, min_clearance=-1.0)
@@ -464,6 +469,11 @@ def generate_dp(spec: SceneSpec | str, batch: int, seed: int = 0, first_problem:
     coarse = np.ascontiguousarray(dp[:, :, [2, 3, 4, 6, 7, 8]])        # x, y, theta, velocity, a, delta (cc:148)
     for b in range(batch):                                              # the scene file replays what was solved
         sf.scenes[b].coarse = coarse[b].copy()
-    return dict(start=sc["start"], coarse=coarse, dp=dp, found=found, obstacle_points=sc["obstacle_points"],
-                obstacle_count=sc["obstacle_count"], left=sc["left"], right=sc["right"], n_steps=spec.n_steps,
+    obstacle_points, obstacle_count = sc["obstacle_points"], sc["obstacle_count"]
+    if points == "device":
+        with api.BatchIlqrOptimizer(n_steps=spec.n_steps, device=device, batch_capacity=1, cmax=spec.cmax) as opt:
+            obstacle_points, obstacle_count, _ = opt.scene_points(scene_io.pack_scene_batch(sf.center, sf.scenes),
+                                                                  np.arange(spec.n_steps + 1) * spec.dt)
+    return dict(start=sc["start"], coarse=coarse, dp=dp, found=found, obstacle_points=obstacle_points,
+                obstacle_count=obstacle_count, left=sc["left"], right=sc["right"], n_steps=spec.n_steps,
                 dt=spec.dt, cmax=spec.cmax, scene_file=sf)

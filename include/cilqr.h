@@ -25,6 +25,10 @@
  *                           VehicleModel::Dynamics (vehicle_model.cc:88-121)
  *   cilqr_dp_plan           DpPlanner::Plan + ComputePathProfile (algorithm/planner/dp_planner.cpp:135-281), one scene
  *                           on the host; cilqr_dp_plan_batch: B scenes per call on the GPU
+ *   cilqr_scene_points_batch  Environment::QueryStaticObstaclesPoints + QueryDynamicObstaclesPoints
+ *                           (algorithm/utils/environment.cpp:133-182) at every knot's time, B scenes per call on the GPU
+ *   cilqr_plan_scenes_batch   TrajectoryPlanner::Plan (algorithm/planner/trajectory_planner.cpp:28-162) for B scenes:
+ *                           DP -> obstacle points -> corridors -> lane constraints -> solve -> result rows
  *
  * Layout convention: every per-problem array is problem-major ("[B][...]"), IEEE fp64,
  * in host or device memory as flagged by `memory`.
@@ -67,7 +71,8 @@ extern "C" {
 #define CILQR_ST_UNSOLVED 4      /* lambda > 1e11                        cc:302     */
 #define CILQR_ST_MAX_ITER 5      /* iter == max_iter_num                 cc:312     */
 #define CILQR_ST_NO_CORRIDOR 6   /* corridor_count < 0 at some knot: the corridor producer failed there
-                                    (cilqr_build_corridors codes); the reference aborts the whole Plan
+                                    (cilqr_build_corridors codes -2 ... -4), or the DP planner found no path for the
+                                    scene (-5 at knot 0, written by cilqr_plan_scenes_batch); the reference aborts the whole Plan
                                     (corridor.cc:78-81, trajectory_planner.cpp:49-57).  The problem is not
                                     optimised: traj = the init guess, n_cost = 1, n_iter = 1 */
 
@@ -225,6 +230,10 @@ int cilqr_set_stream(cilqr_handle h, void* hip_stream);
  * 3 % more throughput on a pool of two handles, 6 % on a single solve; the step-replay tests then need the `lane_tie`
  * excuse (tests/parity_util.py). */
 #define CILQR_OPT_EXACT_LANE_TIES 9
+/* CILQR_OPT_SCENE_CHUNK (default 0): scenes whose obstacle points cilqr_plan_scenes_batch holds at a time.  0 = as many
+ * as fit into 1 GiB of points; a positive value = that many (a test hook: a scene's result does not depend on the chunk
+ * it falls into).  Bit-identical results. */
+#define CILQR_OPT_SCENE_CHUNK 10
 int cilqr_set_option(cilqr_handle h, int32_t option, int64_t value);
 /* the value in force (for the options with two defaults -- CILQR_OPT_SPEC_THRESHOLD, CILQR_OPT_TAIL_THRESHOLD -- the one of
  * cilqr_solve_batch in *value and, if value_submitted is not NULL, the one of submitted solves there) */
@@ -454,6 +463,61 @@ typedef struct cilqr_scene_batch {
 int cilqr_dp_plan_batch(cilqr_handle h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes,
                         const double* start3, int32_t n_knots, double* coarse9, double* coarse6, double* knots3,
                         double* station, int32_t* found, int32_t* n_not_found);
+
+/* ---- obstacle points per knot for B scenes, on the GPU ----
+ * What Corridor::BuildCorridorConstraints asks the Environment for once per knot (environment.cpp:133-182), for every
+ * scene of a batch and every knot time of ONE time axis: the `points` / `point_count` inputs of cilqr_build_corridors,
+ * in exactly that layout.  Per knot: the static polygons in slot order (slots with a count > 0; vertices copied bit for
+ * bit), then the dynamic obstacles present at the knot's time t, in slot order.  An obstacle with T samples and m
+ * vertices is absent when m < 1, T < 1, time[0] > t + 1e-10 or time[T-1] < t - 1e-10; otherwise its pose is sample k =
+ * the first with t < time[k] + 1e-10 (std::upper_bound; past the end: the last) and its vertices are
+ * x + rx c - ry s, y + rx s + ry c in that order, c / s the device library's cos / sin of the sample's heading
+ * (cilqr_device_math fn 7 / 8).  is_multiple_sample = 1: every polygon contributes Polygon2d::sample_points
+ * (polygon2d.cpp:259-271) instead of its corners -- reversed first if its signed area is negative, then six points per
+ * edge at the accumulated ratios 0, 0.2, ..., each p (1 - ratio) + q ratio.
+ *   knot_times  [n_knots], HOST memory
+ *   points      [B][n_knots][max_points][2]   live points packed at the front of a knot's row; the rest of the row is
+ *                                             left untouched (memory as scenes->memory, like the two arrays below)
+ *   point_count [B][n_knots]
+ *   scene_ok    [B] 1 / 0, optional (NULL to skip)
+ * Checked before anything is launched: CILQR_ERR_NULL; CILQR_ERR_ARG for a bad batch, sizes or memory flag, HOST counts
+ * that are negative or above their max_*, n_knots < 1 and max_points < (max_static + max_dynamic) * max_vertices * (6
+ * with is_multiple_sample, else 1); CILQR_ERR_CAPACITY beyond the CILQR_DP_MAX_* limits; CILQR_ERR_STATE while solves
+ * are submitted on the handle.  With DEVICE arrays the counts are checked in the kernel: such a scene gets point_count 0
+ * at every knot and scene_ok 0, the others are unaffected.  Runs on the handle's stream and waits for that stream only;
+ * its work space belongs to the handle and grows to the largest call. */
+int cilqr_scene_points_batch(cilqr_handle h, const cilqr_scene_batch* scenes, int32_t n_knots, const double* knot_times,
+                             int32_t is_multiple_sample, int32_t max_points, double* points, int32_t* point_count,
+                             int32_t* scene_ok);
+
+/* ---- TrajectoryPlanner::Plan for B scenes per call (trajectory_planner.cpp:28-162) ----
+ * scene batch -> cilqr_dp_plan_batch -> cilqr_scene_points_batch (at the time column the planner produced, with
+ * corridor_cfg->is_multiple_sample and the worst-case max_points) -> cilqr_build_corridors (the cmax of the handle's
+ * create call) -> cilqr_solve_batch with the lane tables of cilqr_road_barriers + cilqr_lane_constraints (built once per
+ * call on the host from the batch's centre line and corridor_cfg->lane_segment_length) -> the rows of
+ * trajectory_planner.cpp:101-125.  Only the scenes and the start states cross to the device: every intermediate lives in
+ * the handle's work space (grown to the largest call), points and corridors are produced for CILQR_OPT_SCENE_CHUNK scenes at a
+ * time, the corridors of the whole batch go into one solve.  The results are, bit for bit, those of the four calls made
+ * one after the other (the solve is given the planner's station column as coarse_station).
+ *   start4  [B][4] x y theta v       (memory as scenes->memory, like plan / coarse9 / outcome)
+ *   out     the solver's own outputs, as for cilqr_solve_batch (its own `memory`)
+ *   plan    [B][n_knots][CILQR_PLAN_FIELDS], optional: time s x y theta kappa velocity a delta jerk delta_rate; s is the
+ *           running sum of hypot over the optimised x / y, every other column the bits of the trajectory's column
+ *   coarse9 [B][n_knots][CILQR_COARSE_FIELDS], optional: the DP planner's trajectory
+ *   outcome [B], optional: 0 planned; CILQR_PLAN_DP_FAILED ("DP failed", cpp:32-35); CILQR_PLAN_CORRIDOR_FAILED ("Corridor
+ *           failed", cpp:49-57: a knot with corridor_count -2 ... -4).  Such a scene is not optimised: it ends with
+ *           CILQR_ST_NO_CORRIDOR.  *n_dp_failed / *n_corridor_failed (HOST, optional): how many there are of each.
+ * CILQR_ERR_CAPACITY when (max_static + max_dynamic) * max_vertices * (6 or 1) + 8 (24 with is_multiple_sample) exceeds
+ * the corridor kernel's 320 points, when the batch exceeds the handle's capacity or the lane tables its
+ * max_lane_segments; CILQR_ERR_KNOTS unless n_knots = tf / delta_t + 1 = the handle's n_steps + 1; the other checks are
+ * those of the calls above, all made before anything is launched. */
+#define CILQR_PLAN_FIELDS 11
+#define CILQR_PLAN_DP_FAILED 1
+#define CILQR_PLAN_CORRIDOR_FAILED 2
+int cilqr_plan_scenes_batch(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilqr_corridor_config* corridor_cfg,
+                            const cilqr_scene_batch* scenes, const double* start4, int32_t n_knots,
+                            cilqr_solution_batch* out, double* plan, double* coarse9, int32_t* outcome,
+                            int32_t* n_dp_failed, int32_t* n_corridor_failed);
 
 /* ---- several GPUs from ONE host process (the reference's caller is one process:
  * algorithm/planning_node.cc:9-31) ----
