@@ -3,35 +3,16 @@
 // are its bits), the handle's work space, the launches of kernels_dp.hip.
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 #include "../../include/cilqr/dp_planner.hpp"
 #include "dp_core.hpp"
-#include "solver_priv.hpp"
-
-namespace {
+#include "scene_batch.hpp"
 
 using cilqr::DpParams;
 
 // the placed dynamic polygons of the scenes in flight: the batch is planned in chunks of as many scenes as fit
 constexpr size_t kPlacedBytesCap = (size_t)1 << 30;
-
-size_t round256(size_t n) { return (n + 255) / 256 * 256; }
-
-// counts of HOST arrays: negative, or above what the arrays store
-bool host_counts_valid(const cilqr_scene_batch& sb) {
-  const size_t B = (size_t)sb.batch;
-  for (size_t i = 0; i < B * sb.max_static; ++i)
-    if (sb.static_counts[i] < 0 || sb.static_counts[i] > sb.max_vertices) return false;
-  for (size_t i = 0; i < B * sb.max_dynamic; ++i)
-    if (sb.dynamic_polygon_counts[i] < 0 || sb.dynamic_polygon_counts[i] > sb.max_vertices ||
-        sb.dynamic_trajectory_counts[i] < 0 || sb.dynamic_trajectory_counts[i] > sb.max_samples)
-      return false;
-  return true;
-}
-
-}  // namespace
 
 extern "C" int cilqr_dp_plan_batch(cilqr_handle h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes,
                                    const double* start3, int32_t n_knots, double* coarse9, double* coarse6,
@@ -47,26 +28,13 @@ int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const 
       scenes->center == nullptr)
     return CILQR_ERR_NULL;
   const cilqr_scene_batch& sb = *scenes;
-  if (sb.batch < 1 || sb.n_center < 2 || sb.max_static < 0 || sb.max_dynamic < 0 || sb.max_vertices < 0 ||
-      sb.max_samples < 0 || !(cfg->delta_t > 0.0) || !(cfg->tf > 0.0))
-    return CILQR_ERR_ARG;
-  if (sb.memory != CILQR_MEM_HOST && sb.memory != CILQR_MEM_DEVICE) return CILQR_ERR_ARG;
-  if ((sb.max_static > 0 && (sb.static_points == nullptr || sb.static_counts == nullptr)) ||
-      (sb.max_dynamic > 0 && (sb.dynamic_polygon_points == nullptr || sb.dynamic_polygon_counts == nullptr ||
-                              sb.dynamic_trajectories == nullptr || sb.dynamic_trajectory_counts == nullptr)))
-    return CILQR_ERR_NULL;
-  if ((sb.max_static > 0 || sb.max_dynamic > 0) && sb.max_vertices < 1) return CILQR_ERR_ARG;
-  if (sb.max_dynamic > 0 && sb.max_samples < 1) return CILQR_ERR_ARG;
+  if (int rc = cilqr::check_scene_batch(sb)) return rc;
+  if (!(cfg->delta_t > 0.0) || !(cfg->tf > 0.0)) return CILQR_ERR_ARG;
   if ((int32_t)(cfg->tf / cfg->delta_t + 1) != n_knots) return CILQR_ERR_KNOTS;
-  if (sb.max_vertices > CILQR_DP_MAX_VERTICES || sb.max_static > CILQR_DP_MAX_STATIC ||
-      sb.max_dynamic > CILQR_DP_MAX_DYNAMIC || sb.max_samples > CILQR_DP_MAX_SAMPLES || n_knots > CILQR_DP_MAX_KNOTS)
-    return CILQR_ERR_CAPACITY;
-  {
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->job_count != 0) return CILQR_ERR_STATE;   // submitted solves not collected yet (cilqr_wait)
-  }
+  if (cilqr::beyond_limits(sb, n_knots)) return CILQR_ERR_CAPACITY;
+  if (cilqr::solves_in_flight(h)) return CILQR_ERR_STATE;
   const bool on_host = sb.memory == CILQR_MEM_HOST;
-  if (on_host && !host_counts_valid(sb)) return CILQR_ERR_ARG;
+  if (on_host && !cilqr::host_counts_valid(sb)) return CILQR_ERR_ARG;
 
   // ---- the lattice and the road, by the host planner's own constructors
   cilqr::DpConfig d;
@@ -108,90 +76,75 @@ int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const 
   hipStream_t st = h->stream;
   const size_t B = (size_t)sb.batch, K = (size_t)n_knots;
   // ---- work space of the handle (grown, never shrunk: nothing is allocated once the largest call has been seen)
-  const size_t b_center = (size_t)sb.n_center * 7 * 8, b_barrier = barrier.size() * 2 * 8;
-  const size_t o_barrier = round256(b_center), b_tab = o_barrier + round256(b_barrier) + 256;
-  HIP_TRY(h->dp_tab_host.grow(b_tab));
-  HIP_TRY(h->dp_tab.grow(b_tab, &h->grown_bytes));
+  cilqr::block_layout l_tab, l_placed, l_in, l_out;
+  const cilqr::slot s_center = l_tab.add((size_t)sb.n_center * 7 * 8), s_barrier = l_tab.add(barrier.size() * 2 * 8);
+  HIP_TRY(h->dp_tab_host.grow(l_tab.bytes() + 256));
+  HIP_TRY(h->dp_tab.grow(l_tab.bytes() + 256, &h->grown_bytes));
   if (h->dp_fail.get() == nullptr) HIP_TRY(h->dp_fail.alloc(256));
   if (h->dp_fail_host.get() == nullptr) HIP_TRY(h->dp_fail_host.alloc(64));
   const size_t rec = 4 + 2 * (size_t)sb.max_vertices;
   const size_t per_scene = (size_t)P.nq * sb.max_dynamic * (rec * 8 + 4);
   size_t chunk = B;
   if (per_scene > 0) chunk = std::min(B, std::max<size_t>(1, kPlacedBytesCap / per_scene));
-  const size_t o_placed_n = round256(chunk * (size_t)P.nq * sb.max_dynamic * rec * 8);
-  HIP_TRY(h->dp_placed.grow(o_placed_n + round256(chunk * (size_t)P.nq * sb.max_dynamic * 4) + 256, &h->grown_bytes));
+  const cilqr::slot s_placed = l_placed.add(chunk * (size_t)P.nq * sb.max_dynamic * rec * 8);
+  const cilqr::slot s_placed_n = l_placed.add(chunk * (size_t)P.nq * sb.max_dynamic * 4);
+  HIP_TRY(h->dp_placed.grow(l_placed.bytes() + 256, &h->grown_bytes));
   // HOST arrays: one block in, one block out
-  const size_t b_start = B * 3 * 8, b_sp = B * sb.max_static * sb.max_vertices * 2 * 8, b_sc = B * sb.max_static * 4;
-  const size_t b_dp = B * sb.max_dynamic * sb.max_vertices * 2 * 8, b_dc = B * sb.max_dynamic * 4;
-  const size_t b_dt = B * sb.max_dynamic * sb.max_samples * 4 * 8;
-  const size_t i_sp = round256(b_start), i_sc = i_sp + round256(b_sp), i_dp = i_sc + round256(b_sc), i_dpc = i_dp + round256(b_dp);
-  const size_t i_dt = i_dpc + round256(b_dc), i_dtc = i_dt + round256(b_dt), b_in = i_dtc + round256(b_dc) + 256;
-  const size_t b_c9 = coarse9 ? B * K * CILQR_COARSE_FIELDS * 8 : 0, b_c6 = coarse6 ? B * K * 6 * 8 : 0;
-  const size_t b_k3 = knots3 ? B * K * 3 * 8 : 0, b_stn = station ? B * K * 8 : 0, b_found = B * 4;
-  const size_t o_c6 = round256(b_c9), o_k3 = o_c6 + round256(b_c6), o_stn = o_k3 + round256(b_k3);
-  const size_t o_found = o_stn + round256(b_stn), b_out = o_found + round256(b_found) + 256;
+  const cilqr::slot s_start = l_in.add(B * 3 * 8);
+  const cilqr::SceneImage im(l_in, sb);
+  const cilqr::slot s_c9 = l_out.add(coarse9 ? B * K * CILQR_COARSE_FIELDS * 8 : 0), s_c6 = l_out.add(coarse6 ? B * K * 6 * 8 : 0);
+  const cilqr::slot s_k3 = l_out.add(knots3 ? B * K * 3 * 8 : 0), s_stn = l_out.add(station ? B * K * 8 : 0);
+  const cilqr::slot s_found = l_out.add(B * 4);
   if (on_host) {
-    HIP_TRY(h->dp_in.grow(b_in, &h->grown_bytes));
-    HIP_TRY(h->dp_out.grow(b_out, &h->grown_bytes));
+    HIP_TRY(h->dp_in.grow(l_in.bytes() + 256, &h->grown_bytes));
+    HIP_TRY(h->dp_out.grow(l_out.bytes() + 256, &h->grown_bytes));
   }
 
   // ---- tables: pinned block -> device (the stream is waited for at the end of every call, so the block is free again)
   char* th = h->dp_tab_host.as<char>();
   char* td = h->dp_tab.as<char>();
-  std::memcpy(th, sb.center, b_center);
-  if (b_barrier) std::memcpy(th + o_barrier, barrier.data(), b_barrier);
+  std::memcpy(th, sb.center, s_center.bytes);
+  if (s_barrier.bytes) std::memcpy(th + s_barrier.off, barrier.data(), s_barrier.bytes);
   static_assert(sizeof(cilqr::DpPoint2) == 16, "the barrier table travels as [n][2] doubles");
-  HIP_TRY(hipMemcpyAsync(td, th, o_barrier + b_barrier, hipMemcpyHostToDevice, st));
-  P.center = reinterpret_cast<const double*>(td);
-  P.barrier = reinterpret_cast<const double*>(td + o_barrier);
+  HIP_TRY(hipMemcpyAsync(td, th, s_barrier.off + s_barrier.bytes, hipMemcpyHostToDevice, st));
+  P.center = s_center.in<const double>(td);
+  P.barrier = s_barrier.in<const double>(td);
   int* d_fail = h->dp_fail.as<int>();
   HIP_TRY(hipMemsetAsync(d_fail, 0, 4, st));
 
-  const double *d_start = start3, *d_sp = sb.static_points, *d_dp = sb.dynamic_polygon_points, *d_dt = sb.dynamic_trajectories;
-  const int *d_sc = sb.static_counts, *d_dpc = sb.dynamic_polygon_counts, *d_dtc = sb.dynamic_trajectory_counts;
+  cilqr_scene_batch dv = sb;
+  const double* d_start = start3;
   double *d_c9 = coarse9, *d_c6 = coarse6, *d_k3 = knots3, *d_stn = station;
   int* d_found = found;
+  char* bo = h->dp_out.as<char>();
   if (on_host) {
     char* bi = h->dp_in.as<char>();
-    char* bo = h->dp_out.as<char>();
-    HIP_TRY(hipMemcpyAsync(bi, start3, b_start, hipMemcpyHostToDevice, st));
-    if (b_sp) {
-      HIP_TRY(hipMemcpyAsync(bi + i_sp, sb.static_points, b_sp, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(bi + i_sc, sb.static_counts, b_sc, hipMemcpyHostToDevice, st));
-    }
-    if (b_dp) {
-      HIP_TRY(hipMemcpyAsync(bi + i_dp, sb.dynamic_polygon_points, b_dp, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(bi + i_dpc, sb.dynamic_polygon_counts, b_dc, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(bi + i_dt, sb.dynamic_trajectories, b_dt, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(bi + i_dtc, sb.dynamic_trajectory_counts, b_dc, hipMemcpyHostToDevice, st));
-    }
-    d_start = reinterpret_cast<const double*>(bi);
-    d_sp = reinterpret_cast<const double*>(bi + i_sp); d_sc = reinterpret_cast<const int*>(bi + i_sc);
-    d_dp = reinterpret_cast<const double*>(bi + i_dp); d_dpc = reinterpret_cast<const int*>(bi + i_dpc);
-    d_dt = reinterpret_cast<const double*>(bi + i_dt); d_dtc = reinterpret_cast<const int*>(bi + i_dtc);
-    if (coarse9) d_c9 = reinterpret_cast<double*>(bo);
-    if (coarse6) d_c6 = reinterpret_cast<double*>(bo + o_c6);
-    if (knots3) d_k3 = reinterpret_cast<double*>(bo + o_k3);
-    if (station) d_stn = reinterpret_cast<double*>(bo + o_stn);
-    d_found = reinterpret_cast<int*>(bo + o_found);
+    if (int rc = cilqr::copy_in(bi, s_start, start3, st)) return rc;
+    if (int rc = im.upload(sb, bi, st, &dv)) return rc;
+    d_start = s_start.in<const double>(bi);
+    if (coarse9) d_c9 = s_c9.in<double>(bo);
+    if (coarse6) d_c6 = s_c6.in<double>(bo);
+    if (knots3) d_k3 = s_k3.in<double>(bo);
+    if (station) d_stn = s_stn.in<double>(bo);
+    d_found = s_found.in<int>(bo);
   }
 
-  double* placed = h->dp_placed.as<double>();
-  int* placed_n = reinterpret_cast<int*>(h->dp_placed.as<char>() + o_placed_n);
+  double* placed = s_placed.in<double>(h->dp_placed.get());
+  int* placed_n = s_placed_n.in<int>(h->dp_placed.get());
   for (size_t first = 0; first < B; first += chunk) {
     const int n = (int)std::min(chunk, B - first);
-    cilqr::launch_dp_place(P, (int)first, n, d_dp, d_dpc, d_dt, d_dtc, placed, placed_n, st);
-    cilqr::launch_dp_plan(P, (int)first, n, d_start, d_sp, d_sc, d_dpc, d_dtc, placed, placed_n, d_c9, d_c6, d_k3, d_stn,
-                          d_found, d_fail, st);
+    cilqr::launch_dp_place(P, (int)first, n, dv.dynamic_polygon_points, dv.dynamic_polygon_counts, dv.dynamic_trajectories,
+                           dv.dynamic_trajectory_counts, placed, placed_n, st);
+    cilqr::launch_dp_plan(P, (int)first, n, d_start, dv.static_points, dv.static_counts, dv.dynamic_polygon_counts,
+                          dv.dynamic_trajectory_counts, placed, placed_n, d_c9, d_c6, d_k3, d_stn, d_found, d_fail, st);
   }
   HIP_TRY(hipGetLastError());
   if (on_host) {
-    char* bo = h->dp_out.as<char>();
-    if (coarse9) HIP_TRY(hipMemcpyAsync(coarse9, bo, b_c9, hipMemcpyDeviceToHost, st));
-    if (coarse6) HIP_TRY(hipMemcpyAsync(coarse6, bo + o_c6, b_c6, hipMemcpyDeviceToHost, st));
-    if (knots3) HIP_TRY(hipMemcpyAsync(knots3, bo + o_k3, b_k3, hipMemcpyDeviceToHost, st));
-    if (station) HIP_TRY(hipMemcpyAsync(station, bo + o_stn, b_stn, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(found, bo + o_found, b_found, hipMemcpyDeviceToHost, st));
+    if (int rc = cilqr::copy_out(coarse9, bo, s_c9, st)) return rc;
+    if (int rc = cilqr::copy_out(coarse6, bo, s_c6, st)) return rc;
+    if (int rc = cilqr::copy_out(knots3, bo, s_k3, st)) return rc;
+    if (int rc = cilqr::copy_out(station, bo, s_stn, st)) return rc;
+    if (int rc = cilqr::copy_out(found, bo, s_found, st)) return rc;
   }
   HIP_TRY(hipMemcpyAsync(h->dp_fail_host.get(), d_fail, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));   // this stream alone: solves on other handles go on

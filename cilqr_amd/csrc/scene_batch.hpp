@@ -1,0 +1,70 @@
+// Private to cilqr_amd/csrc: what the entry points that take a cilqr_scene_batch (planner_batch.hip, scene_pipeline.hip)
+// share -- the checks on the batch, in the order every one of them makes them, and the device image of a HOST batch.
+#pragma once
+#include "staging.hpp"
+
+namespace cilqr {
+
+// shape, memory kind, the arrays the shape asks for
+inline int check_scene_batch(const cilqr_scene_batch& sb) {
+  if (sb.batch < 1 || sb.n_center < 2 || sb.max_static < 0 || sb.max_dynamic < 0 || sb.max_vertices < 0 || sb.max_samples < 0)
+    return CILQR_ERR_ARG;
+  if (sb.memory != CILQR_MEM_HOST && sb.memory != CILQR_MEM_DEVICE) return CILQR_ERR_ARG;
+  if ((sb.max_static > 0 && (sb.static_points == nullptr || sb.static_counts == nullptr)) ||
+      (sb.max_dynamic > 0 && (sb.dynamic_polygon_points == nullptr || sb.dynamic_polygon_counts == nullptr ||
+                              sb.dynamic_trajectories == nullptr || sb.dynamic_trajectory_counts == nullptr)))
+    return CILQR_ERR_NULL;
+  if ((sb.max_static > 0 || sb.max_dynamic > 0) && sb.max_vertices < 1) return CILQR_ERR_ARG;
+  if (sb.max_dynamic > 0 && sb.max_samples < 1) return CILQR_ERR_ARG;
+  return CILQR_OK;
+}
+
+inline bool beyond_limits(const cilqr_scene_batch& sb, int n_knots) {
+  return sb.max_vertices > CILQR_DP_MAX_VERTICES || sb.max_static > CILQR_DP_MAX_STATIC ||
+         sb.max_dynamic > CILQR_DP_MAX_DYNAMIC || sb.max_samples > CILQR_DP_MAX_SAMPLES || n_knots > CILQR_DP_MAX_KNOTS;
+}
+
+// counts of HOST arrays: negative, or above what the arrays store
+inline bool host_counts_valid(const cilqr_scene_batch& sb) {
+  const size_t B = (size_t)sb.batch;
+  for (size_t i = 0; i < B * sb.max_static; ++i)
+    if (sb.static_counts[i] < 0 || sb.static_counts[i] > sb.max_vertices) return false;
+  for (size_t i = 0; i < B * sb.max_dynamic; ++i)
+    if (sb.dynamic_polygon_counts[i] < 0 || sb.dynamic_polygon_counts[i] > sb.max_vertices ||
+        sb.dynamic_trajectory_counts[i] < 0 || sb.dynamic_trajectory_counts[i] > sb.max_samples)
+      return false;
+  return true;
+}
+
+inline bool solves_in_flight(cilqr_solver* h) {
+  std::lock_guard<std::mutex> lk(h->mu);
+  return h->job_count != 0;   // submitted solves not collected yet (cilqr_wait)
+}
+
+// The device image of a HOST scene batch: its six per-problem arrays as six slots of the caller's block.
+struct SceneImage {
+  slot sp, sc, dp, dpc, dt, dtc;
+  SceneImage(block_layout& L, const cilqr_scene_batch& sb) {
+    const size_t B = (size_t)sb.batch;
+    sp = L.add(B * sb.max_static * sb.max_vertices * 2 * 8); sc = L.add(B * sb.max_static * 4);
+    dp = L.add(B * sb.max_dynamic * sb.max_vertices * 2 * 8); dpc = L.add(B * sb.max_dynamic * 4);
+    dt = L.add(B * sb.max_dynamic * sb.max_samples * 4 * 8); dtc = L.add(B * sb.max_dynamic * 4);
+  }
+  // the arrays of `sb` (HOST) into `block`; `view` = the batch with its arrays there
+  int upload(const cilqr_scene_batch& sb, char* block, hipStream_t st, cilqr_scene_batch* view) const {
+    if (int rc = copy_in(block, sp, sb.static_points, st)) return rc;
+    if (int rc = copy_in(block, sc, sb.static_counts, st)) return rc;
+    if (int rc = copy_in(block, dp, sb.dynamic_polygon_points, st)) return rc;
+    if (int rc = copy_in(block, dpc, sb.dynamic_polygon_counts, st)) return rc;
+    if (int rc = copy_in(block, dt, sb.dynamic_trajectories, st)) return rc;
+    if (int rc = copy_in(block, dtc, sb.dynamic_trajectory_counts, st)) return rc;
+    *view = sb;
+    view->memory = CILQR_MEM_DEVICE;
+    view->static_points = sp.in<const double>(block); view->static_counts = sc.in<const int32_t>(block);
+    view->dynamic_polygon_points = dp.in<const double>(block); view->dynamic_polygon_counts = dpc.in<const int32_t>(block);
+    view->dynamic_trajectories = dt.in<const double>(block); view->dynamic_trajectory_counts = dtc.in<const int32_t>(block);
+    return CILQR_OK;
+  }
+};
+
+}  // namespace cilqr

@@ -311,7 +311,7 @@ void release_fin(cilqr_solver* h, cilqr_job& j);
 // costs nothing as long as it is shorter than an iteration -- the stream still holds the next one (kLead = 2).
 // CILQR_HOST_WAIT=spin / nap overrides the choice for both kinds of call (measurement hook).
 // ------------------------------------------------------------------------------------------
-constexpr int kWaitSpinUs = 20, kWaitNapUs = 50;
+constexpr int kWaitNapUs = 50;
 constexpr int kWaitSpinShortUs = 250, kShortIterationProblems = 2048;   // the nap policy by work size
 int host_wait_override() {
   static const int v = [] {
@@ -321,7 +321,8 @@ int host_wait_override() {
   }();
   return v;
 }
-int wait_event(hipEvent_t ev, bool relaxed, int spin_us = kWaitSpinUs) {
+}  // namespace
+int cilqr::wait_event(hipEvent_t ev, bool relaxed, int spin_us) {
   const int ov = host_wait_override();
   if (ov >= 0) relaxed = ov != 0;
   if (!relaxed) {
@@ -340,6 +341,7 @@ int wait_event(hipEvent_t ev, bool relaxed, int spin_us = kWaitSpinUs) {
       std::this_thread::sleep_for(std::chrono::microseconds(kWaitNapUs));
   }
 }
+namespace {
 // everything enqueued on `st` so far; `scratch` is an event of the caller's that nothing else is waiting on
 int wait_stream(hipStream_t st, hipEvent_t scratch, bool relaxed) {
   const int ov = host_wait_override();
@@ -1743,125 +1745,6 @@ int cilqr_stage_nearest_lane(cilqr_handle h, int32_t n, const double* xy, int32_
   }
   if (hipStreamSynchronize(h->stream) != hipSuccess) rc = CILQR_ERR_DEVICE;
   return rc;
-}
-
-// ------------------------------------------------------------------------------------------
-// corridor producer
-// ------------------------------------------------------------------------------------------
-void cilqr_default_corridor_config(cilqr_corridor_config* c) {
-  if (c == nullptr) return;
-  c->max_diff_x = 25.0; c->max_diff_y = 25.0; c->radius = 150.0;   // planner_config.h:77-79
-  c->max_axis_x = 10.0; c->max_axis_y = 10.0;                      // planner_config.h:81-82
-  c->lane_segment_length = 5.0;                                    // planner_config.h:85
-  c->is_multiple_sample = 0;                                       // planner_config.h:76
-  c->reserved0 = 0;
-}
-
-int cilqr_build_corridors(cilqr_handle h, const cilqr_corridor_config* cfg, int32_t batch, int32_t n_knots,
-                          const double* knots, const double* points, const int32_t* point_count,
-                          int32_t max_points, double* corridor, int32_t* corridor_count, int32_t cmax,
-                          int32_t memory, int32_t* n_failed, double* polygons) {
-  if (h == nullptr || cfg == nullptr || knots == nullptr || point_count == nullptr || corridor == nullptr ||
-      corridor_count == nullptr)
-    return CILQR_ERR_NULL;                                          // corridor.cc:29-35
-  if (points == nullptr && max_points > 0) return CILQR_ERR_NULL;
-  if (batch <= 0 || n_knots <= 0 || cmax < 3 || max_points < 0) return CILQR_ERR_ARG;   // empty trajectory cc:24-27
-  if (max_points + (cfg->is_multiple_sample ? 24 : 8) > kCorMaxPts) return CILQR_ERR_CAPACITY;
-  if (memory != CILQR_MEM_HOST && memory != CILQR_MEM_DEVICE) return CILQR_ERR_ARG;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)batch * n_knots;
-  const size_t b_knots = n * 3 * 8, b_pts = n * (size_t)max_points * 2 * 8, b_cnt = n * 4;
-  const size_t b_cor = n * (size_t)cmax * 3 * 8, b_poly = polygons ? n * (size_t)cmax * 2 * 8 : 0;
-  CorridorParams cp{cfg->max_diff_x, cfg->max_diff_y, cfg->radius, cfg->max_axis_x, cfg->max_axis_y,
-                    cfg->is_multiple_sample ? 6 : 2};
-  dev_mem t_in, t_out;
-  int rc = CILQR_OK;
-  // the failure counter and its landing place on the host belong to the handle: a hipMalloc / hipFree per call is a
-  // device-wide synchronisation, i.e. a producer that runs beside solves in flight (other handles, a pool) would wait for
-  // all of them
-  if (h->cor_fail.get() == nullptr) HIP_TRY(h->cor_fail.alloc(256));
-  if (h->cor_fail_host.get() == nullptr) HIP_TRY(h->cor_fail_host.alloc(64));
-  if (h->cor_done.get() == nullptr) HIP_TRY(h->cor_done.create());
-  int* t_fail = h->cor_fail.as<int>();
-  // (a producer beside solves in flight -- bench.py: end_to_end -- runs on the handle's own stream at normal priority: on a
-  // low-priority stream the call took 25 ms instead of 16.5 and the pipeline lost 1.5 %, r06 log 7)
-  hipStream_t cst = h->stream;
-  const double *d_knots = knots, *d_pts = points;
-  const int* d_cnt = point_count;
-  double* d_cor = corridor;
-  double* d_poly = polygons;
-  int* d_ccnt = corridor_count;
-  if (hipMemsetAsync(t_fail, 0, 4, cst) != hipSuccess) rc = CILQR_ERR_DEVICE;
-  if (rc == CILQR_OK && memory == CILQR_MEM_HOST) {
-    const size_t o_pts = (b_knots + 255) / 256 * 256, o_cnt = o_pts + (b_pts + 255) / 256 * 256;
-    if (t_in.alloc(o_cnt + b_cnt + 256) != hipSuccess || t_out.alloc(b_cor + 512 + b_cnt + b_poly) != hipSuccess) {
-      rc = CILQR_ERR_DEVICE;
-    } else {
-      char* bi = t_in.as<char>();
-      char* bo = t_out.as<char>();
-      if (hipMemcpyAsync(bi, knots, b_knots, hipMemcpyHostToDevice, cst) != hipSuccess ||
-          (b_pts && hipMemcpyAsync(bi + o_pts, points, b_pts, hipMemcpyHostToDevice, cst) != hipSuccess) ||
-          hipMemcpyAsync(bi + o_cnt, point_count, b_cnt, hipMemcpyHostToDevice, cst) != hipSuccess)
-        rc = CILQR_ERR_DEVICE;
-      d_knots = reinterpret_cast<const double*>(bi);
-      d_pts = reinterpret_cast<const double*>(bi + o_pts);
-      d_cnt = reinterpret_cast<const int*>(bi + o_cnt);
-      d_cor = reinterpret_cast<double*>(bo);
-      d_ccnt = reinterpret_cast<int*>(bo + (b_cor + 255) / 256 * 256);
-      if (polygons) d_poly = reinterpret_cast<double*>(bo + (b_cor + 255) / 256 * 256 + (b_cnt + 255) / 256 * 256);
-    }
-  }
-  int failed = 0;
-  if (rc == CILQR_OK) {
-    launch_build_corridors((int)n, cp, d_knots, d_pts, d_cnt, max_points, d_cor, d_ccnt, cmax, t_fail, d_poly, cst);
-    if (hipGetLastError() != hipSuccess) rc = CILQR_ERR_DEVICE;
-    if (rc == CILQR_OK && memory == CILQR_MEM_HOST) {
-      if (hipMemcpyAsync(corridor, d_cor, b_cor, hipMemcpyDeviceToHost, cst) != hipSuccess ||
-          hipMemcpyAsync(corridor_count, d_ccnt, b_cnt, hipMemcpyDeviceToHost, cst) != hipSuccess ||
-          (polygons && hipMemcpyAsync(polygons, d_poly, b_poly, hipMemcpyDeviceToHost, cst) != hipSuccess))
-        rc = CILQR_ERR_DEVICE;
-    }
-    if (rc == CILQR_OK &&
-        hipMemcpyAsync(h->cor_fail_host.get(), t_fail, 4, hipMemcpyDeviceToHost, cst) != hipSuccess)
-      rc = CILQR_ERR_DEVICE;
-    // a large batch is milliseconds of kernel time: the caller's thread naps through it instead of spinning (it usually has
-    // solves in flight whose worker threads want the cores); a small one is waited for the short way
-    if (rc == CILQR_OK && n >= (size_t)1 << 18) {
-      if (hipEventRecord(h->cor_done.get(), cst) != hipSuccess || wait_event(h->cor_done.get(), true) != CILQR_OK) rc = CILQR_ERR_DEVICE;
-    } else if (hipStreamSynchronize(cst) != hipSuccess) {
-      rc = CILQR_ERR_DEVICE;
-    }
-    if (rc == CILQR_OK) failed = *h->cor_fail_host.as<int>();
-  }
-  if (n_failed) *n_failed = failed;
-  return rc;
-}
-
-int cilqr_lane_constraints(const double* boundary, int32_t n, double segment_length, int32_t is_left,
-                           double* rows, int32_t max_rows) {
-  if (boundary == nullptr || rows == nullptr) return CILQR_ERR_NULL;
-  if (n < 1 || max_rows < 1) return CILQR_ERR_ARG;
-  // LaneBoundarySample corridor.cc:298-311: keep a point once it is a segment length from the last kept one
-  int m = 0;              // rows written
-  double lx = boundary[0], ly = boundary[1];
-  for (int i = 0; i < n; ++i) {
-    const double x = boundary[2 * i], y = boundary[2 * i + 1];
-    if (std::hypot(x - lx, y - ly) >= segment_length - 1e-10) {
-      if (m >= max_rows) return CILQR_ERR_CAPACITY;
-      // Cal{Left,Right}LaneConstraints cc:265-296: the left barrier runs from the new point back to
-      // the previous one, the right barrier forward; HalfPlaneConstraint cc:313-321
-      const double ax = is_left ? x : lx, ay = is_left ? y : ly;
-      const double bx = is_left ? lx : x, by = is_left ? ly : y;
-      const double a = by - ay, b = -(bx - ax);
-      double* r = rows + 7 * (size_t)m;
-      r[0] = a; r[1] = b; r[2] = a * ax + b * ay;
-      r[3] = ax; r[4] = ay; r[5] = bx; r[6] = by;
-      ++m;
-      lx = x; ly = y;
-    }
-  }
-  if (m < 1) return CILQR_ERR_CONSTRAINTS;   // fewer than two sampled points  cc:273-275
-  return m;
 }
 
 int cilqr_device_math(cilqr_handle h, int32_t fn, int32_t n, const double* in, double* out) {

@@ -220,7 +220,7 @@ struct cilqr_solver {
   int profiling_level = 1;
   cilqr_profile prof;         // of the last solve that completed
   cilqr_comm* comm = nullptr;   // multi-GPU results gather (cilqr_comm_create)
-  cilqr::dev_mem cor_fail;        // cilqr_build_corridors: failure counter on the device, where it lands on the host, its event
+  cilqr::dev_mem cor_fail;        // cilqr_build_corridors (corridor_batch.hip): failure counter on the device, where it lands on the host, its event
   cilqr::pinned_mem cor_fail_host;
   cilqr::hip_event cor_done;
   cilqr::TrackerParams tracker;   // CILQR_INIT_TRACKER
@@ -237,6 +237,13 @@ struct cilqr_solver {
   cilqr::dev_mem sp_tab, sp_in, sp_out, ps_work, ps_points;
   int scene_chunk = 0;            // CILQR_OPT_SCENE_CHUNK
 };
+
+namespace cilqr {
+// solver.hip (host waits): until `ev` has happened -- spinning in the runtime or, `relaxed`, with queries for `spin_us` and
+// naps from then on
+constexpr int kWaitSpinUs = 20;
+int wait_event(hipEvent_t ev, bool relaxed, int spin_us = kWaitSpinUs);
+}  // namespace cilqr
 
 // cilqr_dp_plan_batch (planner_batch.hip); times_out (HOST, [n_knots], optional): the time column every planned scene gets
 int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes, const double* start3,
