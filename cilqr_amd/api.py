@@ -122,6 +122,7 @@ class TrackerConfig(C.Structure):
 
 
 INIT_IQR, INIT_TRACKER = 0, 1
+TRACKER_MAX_ITERATIONS, TRACKER_MAX_SIM_STEPS = 1000, 32768   # CILQR_TRACKER_MAX_* of include/cilqr.h
 
 
 class Profile(C.Structure):

@@ -309,7 +309,8 @@ __global__ __launch_bounds__(64) void k_init_guess_tracker(DeviceState s, Tracke
     }
   }
   // the reference gives up when the count differs ("tacker failed", cc:205-208); here the remaining knots repeat the
-  // last state with zero controls (cannot happen for the reference's time grids: the comparisons carry 1e-10 of slack)
+  // last state with zero controls.  A guard only: cilqr_set_tracker_config replays this clock on the host and refuses a
+  // sumulation_dt that leaves knots unvisited; what is left is a handle whose own dt the default 10 ms does not divide
   for (; i < K; ++i) {
     const double u[2] = {0.0, 0.0};
     store_u(s, 0, i - 1, slot, u);

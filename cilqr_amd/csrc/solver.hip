@@ -496,6 +496,27 @@ int cilqr_default_config(cilqr_config* c, int32_t n_steps) {
   return CILQR_OK;
 }
 
+namespace {
+void apply_tracker_config(cilqr_solver* h, const cilqr_tracker_config* c) {   // (have_station belongs to the loads: load_kernels)
+  TrackerParams& t = h->tracker;
+  t.weight_l = c->weight_l; t.weight_theta = c->weight_theta; t.weight_delta = c->weight_delta;
+  t.weight_delta_rate = c->weight_delta_rate; t.preview_time = c->preview_time;
+  t.weight_s = c->weight_s; t.weight_v = c->weight_v; t.weight_a = c->weight_a; t.weight_j = c->weight_j;
+  t.sim_dt = c->sumulation_dt; t.dt = c->dt; t.tolerance = c->tolerance; t.max_num_iteration = c->max_num_iteration;
+}
+// The clock loop of k_init_guess_tracker (Tracker::lqr, tracker.cc:169-215) in the same double arithmetic: does it pass all
+// K - 1 knots?  Where it does not the reference gives up ("tacker failed", cc:205-208).  At most CILQR_TRACKER_MAX_SIM_STEPS + 2
+// rounds: the caller has bounded end_time / sim_dt.
+bool tracker_clock_passes_every_knot(int K, double knot_dt, double sim_dt) {
+  constexpr double kMathEps = 1e-10;   // algorithm/math/vec2d.h:33 (dev_model.hpp)
+  const double start_time = knot_dt * 0, end_time = knot_dt * (K - 1);
+  int i = 1;
+  for (double t = start_time; t < end_time + kMathEps; t += sim_dt)
+    if (i < K && t > knot_dt * i - kMathEps) ++i;
+  return i == K;
+}
+}  // namespace
+
 int cilqr_create(const cilqr_config* cfg, int32_t device, int32_t batch_capacity, int32_t cmax,
                  int32_t max_lane_segments, cilqr_handle* out) {
   if (cfg == nullptr || out == nullptr) return CILQR_ERR_NULL;
@@ -534,7 +555,8 @@ int cilqr_create(const cilqr_config* cfg, int32_t device, int32_t batch_capacity
   {
     cilqr_tracker_config tc;
     cilqr_default_tracker_config(&tc);
-    (void)cilqr_set_tracker_config(h, &tc);
+    apply_tracker_config(h, &tc);   // (unchecked: the defaults' time grid is the caller's dt, which the tracker may never see)
+    h->tracker.have_station = 0;
   }
   const size_t N = cfg->n_steps, K = N + 1, B = Bc;
   d.Pcap = Bc;
@@ -748,14 +770,20 @@ void cilqr_default_tracker_config(cilqr_tracker_config* c) {
 }
 
 int cilqr_set_tracker_config(cilqr_handle h, const cilqr_tracker_config* c) {
-  if (h == nullptr || c == nullptr) return CILQR_ERR_NULL;
-  if (!(c->sumulation_dt > 0.0) || !(c->dt > 0.0) || !(c->tolerance >= 0.0) || c->max_num_iteration < 1) return CILQR_ERR_ARG;
-  TrackerParams& t = h->tracker;
-  t.weight_l = c->weight_l; t.weight_theta = c->weight_theta; t.weight_delta = c->weight_delta;
-  t.weight_delta_rate = c->weight_delta_rate; t.preview_time = c->preview_time;
-  t.weight_s = c->weight_s; t.weight_v = c->weight_v; t.weight_a = c->weight_a; t.weight_j = c->weight_j;
-  t.sim_dt = c->sumulation_dt; t.dt = c->dt; t.tolerance = c->tolerance; t.max_num_iteration = c->max_num_iteration;
-  t.have_station = 0;
+  if (h == nullptr) return CILQR_ERR_NULL;
+  if (c == nullptr) return CILQR_ERR_ARG;
+  const double fields[12] = {c->weight_l, c->weight_theta, c->weight_delta, c->weight_delta_rate, c->preview_time, c->weight_s,
+                             c->weight_v, c->weight_a, c->weight_j, c->sumulation_dt, c->dt, c->tolerance};
+  for (double f : fields)
+    if (!std::isfinite(f)) return CILQR_ERR_ARG;
+  if (!(c->sumulation_dt > 0.0) || !(c->dt > 0.0) || !(c->tolerance >= 0.0) || c->max_num_iteration < 1 ||
+      c->max_num_iteration > CILQR_TRACKER_MAX_ITERATIONS)
+    return CILQR_ERR_ARG;
+  // limits of one launch (include/cilqr.h): simulation steps over the horizon, then the reference's own failure
+  const Params& p = h->ds.p;
+  if (!(p.dt * (p.K - 1) / c->sumulation_dt <= (double)CILQR_TRACKER_MAX_SIM_STEPS)) return CILQR_ERR_ARG;
+  if (!tracker_clock_passes_every_knot(p.K, p.dt, c->sumulation_dt)) return CILQR_ERR_ARG;
+  apply_tracker_config(h, c);
   return CILQR_OK;
 }
 

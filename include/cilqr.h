@@ -257,7 +257,17 @@ typedef struct cilqr_tracker_config {
   int32_t max_num_iteration;                                                      /* :40 */
   int32_t reserved0;
 } cilqr_tracker_config;
+/* Limits of one tracker launch (every problem runs n_steps * dt / sumulation_dt simulation steps, each with a DARE loop of up
+ * to max_num_iteration rounds; the reference's defaults are 150 iterations and 10 steps per knot). */
+#define CILQR_TRACKER_MAX_ITERATIONS 1000  /* largest max_num_iteration */
+#define CILQR_TRACKER_MAX_SIM_STEPS 32768  /* largest n_steps * dt / sumulation_dt (n_steps, dt of cilqr_create) */
 void cilqr_default_tracker_config(cilqr_tracker_config* cfg);
+/* CILQR_ERR_NULL: null handle.  CILQR_ERR_ARG, the handle keeping the configuration it had: a null config; a field that is
+ * not finite; sumulation_dt <= 0, dt <= 0, tolerance < 0; max_num_iteration outside 1 ... CILQR_TRACKER_MAX_ITERATIONS; more
+ * than CILQR_TRACKER_MAX_SIM_STEPS simulation steps over the handle's horizon; a sumulation_dt whose clock
+ * (t = 0, sumulation_dt, 2 sumulation_dt, ... summed in doubles, tracker.cc:186-203) does not pass every knot time i * dt
+ * up to the last -- where the reference's tracker gives up ("tacker failed", cc:205-208): e.g. 0.03 or 0.25 for n_steps = 50,
+ * dt = 0.1.  The stations a load brought (cilqr_problem_batch.coarse_station) are not touched. */
 int cilqr_set_tracker_config(cilqr_handle h, const cilqr_tracker_config* cfg);
 
 /* Asynchronous form of cilqr_solve_batch: submit returns at once (the structs are copied, the

@@ -500,3 +500,18 @@ def tracker_init_guess(start4, coarse, station=None, knot_dt=0.1, **over):
     if rc != 0:
         raise ValueError("tracker failed")
     return X, U, m.value
+
+
+def tracker_solve_lqr(A, B, Q, R, tolerance, max_num_iteration):
+    """math::SolveLQRProblem as the tracker oracle restates it (3x3 A and Q, 3x1 B, 1x1 R).  Returns (K [3], rounds of the
+    loop, smallest relative distance of a stopping test to the tolerance)."""
+    A, B, Q = _f64(A).reshape(9), _f64(B).reshape(3), _f64(Q).reshape(9)
+    K = np.zeros(3)
+    n, m = C.c_int(), C.c_double()
+    L = lib()
+    L.oracle_tracker_solve_lqr.restype = None
+    L.oracle_tracker_solve_lqr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p,
+                                           C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.oracle_tracker_solve_lqr(A.ctypes.data, B.ctypes.data, Q.ctypes.data, float(R), float(tolerance), int(max_num_iteration),
+                               K.ctypes.data, C.byref(n), C.byref(m))
+    return K, n.value, m.value

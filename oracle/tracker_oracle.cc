@@ -142,9 +142,10 @@ Mat3 Transpose(const Mat3& a) {
 }
 
 // linear_quadratic_regulator.cc:30-78 with B 3x1, R 1x1, M = 0; K out: 1x3.  *margin: smallest relative distance
-// of `diff` to the tolerance over the iterations (the loop's stopping test is the only decision in here)
+// of `diff` to the tolerance over the iterations (the loop's stopping test is the only decision in here); *rounds: how
+// often the loop's body ran
 void SolveLQRProblem(const Mat3& A, const double* B, const Mat3& Q, double R, double tolerance, unsigned max_num_iteration,
-                     double* K, double* margin) {
+                     double* K, double* margin, unsigned* rounds = nullptr) {
   const Mat3 AT = Transpose(A);
   Mat3 P = Q;
   unsigned num_iteration = 0;
@@ -184,6 +185,7 @@ void SolveLQRProblem(const Mat3& A, const double* B, const Mat3& Q, double R, do
     diff = std::fabs(maxc);                          // fabs((P_next - P).maxCoeff())
     if (margin) *margin = std::min(*margin, std::fabs(diff - tolerance) / tolerance);
     P = P_next;
+    if (rounds) ++*rounds;
   }
   double BTP[3], BTPA[3];
   row_times(B, P, BTP);
@@ -407,6 +409,19 @@ void oracle_tracker_projection(const double* rows, int n, double px, double py, 
   f.GetProjection(px, py, &p);
   out9[0] = p.time; out9[1] = p.s; out9[2] = p.x; out9[3] = p.y; out9[4] = p.theta; out9[5] = p.kappa; out9[6] = p.velocity;
   out9[7] = p.left_bound; out9[8] = p.right_bound;
+}
+/* SolveLQRProblem alone (tests/test_tracker.py): A, Q 3x3 row-major, B 3x1, R 1x1 -> the gain K (1x3), how often the
+ * loop's body ran and the smallest relative distance of a stopping test to the tolerance */
+void oracle_tracker_solve_lqr(const double* A9, const double* B3, const double* Q9, double R, double tolerance,
+                              int max_num_iteration, double* K3, int* rounds, double* min_margin) {
+  Mat3 A, Q;
+  std::memcpy(A.m, A9, sizeof(A.m));
+  std::memcpy(Q.m, Q9, sizeof(Q.m));
+  double margin = std::numeric_limits<double>::infinity();
+  unsigned n = 0;
+  SolveLQRProblem(A, B3, Q, R, tolerance, (unsigned)max_num_iteration, K3, &margin, &n);
+  *rounds = (int)n;
+  *min_margin = margin;
 }
 
 }  // extern "C"
