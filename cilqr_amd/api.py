@@ -112,6 +112,14 @@ COARSE_FIELDS = 9   # time, s, x, y, theta, kappa, velocity, a, delta
 DP_MAX_VERTICES, DP_MAX_STATIC, DP_MAX_DYNAMIC, DP_MAX_SAMPLES, DP_MAX_KNOTS = 8, 32, 32, 1024, 256
 PLAN_FIELDS = 11    # time, s, x, y, theta, kappa, velocity, a, delta, jerk, delta_rate (cilqr_plan_scenes_batch)
 PLAN_OK, PLAN_DP_FAILED, PLAN_CORRIDOR_FAILED = 0, 1, 2
+# cilqr_check_collisions / cilqr_check_collisions_batch: row layouts (CILQR_ROWS_*), doubles per row and the columns of
+# time, x, y, theta in each; the bits of a knot's mask (CILQR_HIT_*)
+ROWS_TRAJ, ROWS_PLAN, ROWS_COARSE = 0, 1, 2
+ROWS_FIELDS = {ROWS_TRAJ: 10, ROWS_PLAN: PLAN_FIELDS, ROWS_COARSE: COARSE_FIELDS}
+ROWS_POSE_COLUMNS = {ROWS_TRAJ: (0, 1, 2, 3), ROWS_PLAN: (0, 2, 3, 4), ROWS_COARSE: (0, 2, 3, 4)}
+HIT_REAR_STATIC, HIT_REAR_BARRIER, HIT_REAR_DYNAMIC = 1, 2, 4
+HIT_FRONT_STATIC, HIT_FRONT_BARRIER, HIT_FRONT_DYNAMIC = 8, 16, 32
+HIT_BITS = (HIT_REAR_STATIC, HIT_REAR_BARRIER, HIT_REAR_DYNAMIC, HIT_FRONT_STATIC, HIT_FRONT_BARRIER, HIT_FRONT_DYNAMIC)
 
 
 class TrackerConfig(C.Structure):
@@ -143,6 +151,7 @@ EXPORTS = [
     "cilqr_stage_read", "cilqr_stage_nearest_lane", "cilqr_open_loop_rollout", "cilqr_error_string",
     "cilqr_default_corridor_config", "cilqr_build_corridors", "cilqr_lane_constraints",
     "cilqr_default_dp_config", "cilqr_dp_plan", "cilqr_dp_plan_batch", "cilqr_scene_points_batch", "cilqr_plan_scenes_batch",
+    "cilqr_check_collisions", "cilqr_check_collisions_batch",
     "cilqr_road_barriers", "cilqr_default_tracker_config",
     "cilqr_set_tracker_config",
     "cilqr_multi_create", "cilqr_multi_destroy", "cilqr_multi_solve", "cilqr_multi_set_option", "cilqr_multi_shards",
@@ -215,6 +224,11 @@ def lib():
         L.cilqr_plan_scenes_batch.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(CorridorConfig),
                                               C.POINTER(SceneBatchStruct), C.c_void_p, C.c_int32, C.POINTER(SolutionBatch),
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.cilqr_check_collisions.argtypes = [C.POINTER(DpConfig), C.POINTER(SceneStruct), C.c_int32, C.c_void_p, C.c_int32,
+                                             C.c_double, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.cilqr_check_collisions_batch.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(SceneBatchStruct), C.c_int32,
+                                                   C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(C.c_int32)]
         L.cilqr_default_tracker_config.argtypes = [C.POINTER(TrackerConfig)]
         L.cilqr_default_tracker_config.restype = None
         L.cilqr_set_tracker_config.argtypes = [C.c_void_p, C.POINTER(TrackerConfig)]
@@ -618,6 +632,35 @@ class BatchIlqrOptimizer:
                                             C.byref(n_dp), C.byref(n_cor))
         return rc, int(n_dp.value), int(n_cor.value)
 
+    def check_collisions(self, packed: dict, rows, layout: int, cfg: "DpConfig | None" = None, buffer: float = 0.0):
+        """Environment::CheckOptimizationCollision for every knot of a batch of trajectories on the GPU
+        (cilqr_check_collisions_batch), host arrays.  `packed` = scene_io.pack_scene_batch(center, scenes), rows [B,K,F]
+        in `layout` (ROWS_TRAJ / ROWS_PLAN / ROWS_COARSE: only time, x, y, theta are read), buffer = collision_buffer.
+        Returns dict(mask [B,K] uint8 of HIT_* bits, first_hit [B] int32 (-1: none), n_hit [B] int32, n_colliding)."""
+        cfg = cfg or default_dp_config()
+        B = int(packed["batch"])
+        rows = _f64(rows)
+        if rows.ndim != 3 or rows.shape[0] != B or rows.shape[2] != ROWS_FIELDS.get(layout, rows.shape[2]):
+            raise ValueError(f"rows must be [{B}, K, {ROWS_FIELDS.get(layout)}]")
+        K = rows.shape[1]
+        keep = {k: np.ascontiguousarray(v) for k, v in packed.items() if isinstance(v, np.ndarray)}
+        sb = scene_batch_struct(packed, MEM_HOST, **{k: _ptr(keep[k]) for k in _SCENE_BATCH_ARRAYS})
+        mask = np.zeros((B, K), dtype=np.uint8)
+        first, n_hit = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        rc, n = self.check_collisions_raw(cfg, sb, layout, _ptr(rows), K, buffer, _ptr(mask), _ptr(first), _ptr(n_hit))
+        self._chk(rc, "check_collisions")
+        return dict(mask=mask, first_hit=first, n_hit=n_hit, n_colliding=n)
+
+    def check_collisions_raw(self, cfg, scene_batch, layout, rows_ptr, n_knots, buffer, mask_ptr, first_hit_ptr,
+                             n_hit_ptr=None):
+        """Pointer-level form (rows / mask / first_hit / n_hit in device or host memory as scene_batch.memory says: the
+        `plan` rows of plan_scenes_raw are audited where they lie); returns (rc, n_colliding)."""
+        n = C.c_int32(0)
+        rc = self.L.cilqr_check_collisions_batch(self.h, C.byref(cfg) if cfg is not None else None, C.byref(scene_batch),
+                                                 layout, rows_ptr, n_knots, C.c_double(buffer), mask_ptr, first_hit_ptr,
+                                                 n_hit_ptr, C.byref(n))
+        return rc, int(n.value)
+
     def open_loop_rollout(self, x0, U):
         x0, U = _f64(x0), _f64(U)
         B = x0.shape[0]
@@ -652,6 +695,36 @@ def dp_plan(flat: dict, start3, cfg: "DpConfig | None" = None):
     if rc not in (OK, ERR_NO_PATH):
         raise CilqrError(rc, "in cilqr_dp_plan")
     return rc == OK, coarse
+
+
+def scene_struct(flat: dict):
+    """cilqr_scene over the arrays of scene_io.flatten_scene: (the struct, the arrays it points into -- keep them alive)."""
+    keep = {k: np.ascontiguousarray(v) for k, v in flat.items()}
+    sc = SceneStruct(keep["center"].ctypes.data, keep["center"].shape[0], len(keep["static_counts"]),
+                     keep["static_points"].ctypes.data, keep["static_counts"].ctypes.data,
+                     len(keep["dynamic_polygon_counts"]), 0, keep["dynamic_polygon_points"].ctypes.data,
+                     keep["dynamic_polygon_counts"].ctypes.data, keep["dynamic_trajectories"].ctypes.data,
+                     keep["dynamic_trajectory_counts"].ctypes.data)
+    return sc, keep
+
+
+def check_collisions(flat: dict, rows, layout: int, cfg: "DpConfig | None" = None, buffer: float = 0.0):
+    """Environment::CheckOptimizationCollision for every knot of one trajectory through the C-ABI (cilqr_check_collisions,
+    host only).  `flat` = scene_io.flatten_scene(center, scene), rows [K,F] in `layout` (ROWS_*).  Returns (mask [K]
+    uint8 of HIT_* bits, first_hit (-1: none), n_hit)."""
+    cfg = cfg or default_dp_config()
+    rows = _f64(rows)
+    if rows.ndim != 2 or rows.shape[1] != ROWS_FIELDS.get(layout, rows.shape[1]):
+        raise ValueError(f"rows must be [K, {ROWS_FIELDS.get(layout)}]")
+    sc, keep = scene_struct(flat)
+    K = rows.shape[0]
+    mask = np.zeros(K, dtype=np.uint8)
+    first, n_hit = C.c_int32(0), C.c_int32(0)
+    rc = lib().cilqr_check_collisions(C.byref(cfg), C.byref(sc), layout, rows.ctypes.data, K, C.c_double(buffer),
+                                      mask.ctypes.data, C.byref(first), C.byref(n_hit))
+    if rc != OK:
+        raise CilqrError(rc, "in cilqr_check_collisions")
+    return mask, int(first.value), int(n_hit.value)
 
 
 _SCENE_BATCH_ARRAYS = ("static_points", "static_counts", "dynamic_polygon_points", "dynamic_polygon_counts",

@@ -1,0 +1,65 @@
+// Private to cilqr_amd/csrc: what the two collision audits (cilqr_check_collisions in host_planner.hip,
+// cilqr_check_collisions_batch in collision_batch.hip) and kernels_collision.hip share -- where a row layout keeps the
+// pose, the checks on the scalar arguments, the parameters of a launch and the launch function.  Every pointer of the
+// launch is device memory; nothing here synchronises.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "../../include/cilqr.h"
+#include "../../include/cilqr/dp_planner.hpp"
+
+namespace cilqr {
+
+// doubles per row and the columns of time, x, y, theta (CILQR_ROWS_*); fields = 0: no such layout
+struct RowLayout {
+  int fields, time, x, y, theta;
+};
+inline RowLayout row_layout(int layout) {
+  switch (layout) {
+    case CILQR_ROWS_TRAJ: return RowLayout{CILQR_TRAJ_FIELDS, 0, 1, 2, 3};
+    case CILQR_ROWS_PLAN: return RowLayout{CILQR_PLAN_FIELDS, 0, 2, 3, 4};
+    case CILQR_ROWS_COARSE: return RowLayout{CILQR_COARSE_FIELDS, 0, 2, 3, 4};
+  }
+  return RowLayout{0, 0, 0, 0, 0};
+}
+
+// layout, knot count and buffer of either audit: CILQR_ERR_ARG / CILQR_ERR_CAPACITY / CILQR_OK
+inline int check_audit_arguments(int layout, int n_knots, double collision_buffer) {
+  if (row_layout(layout).fields == 0 || n_knots < 1) return CILQR_ERR_ARG;
+  if (!(collision_buffer >= 0.0) || !std::isfinite(collision_buffer)) return CILQR_ERR_ARG;
+  if (n_knots > CILQR_DP_MAX_KNOTS) return CILQR_ERR_CAPACITY;
+  return CILQR_OK;
+}
+
+inline DpConfig dp_config_of(const cilqr_dp_config& c) {
+  DpConfig d;
+  d.tf = c.tf; d.delta_t = c.delta_t; d.dp_nominal_velocity = c.dp_nominal_velocity; d.dp_w_obstacle = c.dp_w_obstacle;
+  d.dp_w_lateral = c.dp_w_lateral; d.dp_w_lateral_change = c.dp_w_lateral_change;
+  d.dp_w_lateral_velocity_change = c.dp_w_lateral_velocity_change;
+  d.dp_w_longitudinal_velocity_bias = c.dp_w_longitudinal_velocity_bias;
+  d.dp_w_longitudinal_velocity_change = c.dp_w_longitudinal_velocity_change;
+  d.front_hang_length = c.front_hang_length; d.wheel_base = c.wheel_base; d.rear_hang_length = c.rear_hang_length;
+  d.width = c.width; d.max_velocity = c.max_velocity;
+  return d;
+}
+
+// what a launch shares between its scenes: the vehicle's discs with the buffer already in the half side (DpEnvironment:
+// disc_radius() + collision_buffer, added on the host as CollisionMask adds it), the x-sorted barrier table, the rows
+struct CollisionParams {
+  double h, r2x, f2x;
+  int n_knots, n_barrier;
+  int max_static, max_dynamic, max_vertices, max_samples;   // of the cilqr_scene_batch
+  RowLayout rows;
+  const double* barrier;   // [n_barrier][2], read through L2
+};
+
+// One workgroup per scene of the batch arrays.  mask [B][K] and n_hit [B] may be null; n_colliding (one int, zeroed by
+// the caller) += the scenes with first_hit >= 0.
+void launch_check_collisions(const CollisionParams& P, int n_scenes, const double* rows, const double* static_points,
+                             const int* static_counts, const double* dyn_poly, const int* dyn_poly_counts,
+                             const double* dyn_traj, const int* dyn_traj_counts, uint8_t* mask, int* first_hit, int* n_hit,
+                             int* n_colliding, hipStream_t st);
+
+}  // namespace cilqr

@@ -132,6 +132,8 @@ struct DpSquare {
 CILQR_DEV DpSquare dp_square(const DpParams& P, double cx, double cy) {
   return DpSquare{cx, cy, P.radius, cx - P.radius, cx + P.radius, cy - P.radius, cy + P.radius};
 }
+// the same square with its half side given (kernels_collision.hip: radius + collision_buffer)
+CILQR_DEV DpSquare dp_square_of(double h, double cx, double cy) { return DpSquare{cx, cy, h, cx - h, cx + h, cy - h, cy + h}; }
 CILQR_DEV bool dp_square_has_point(const DpSquare& b, double px, double py) {   // Box2d::IsPointIn, heading 0
   const double x0 = px - b.cx, y0 = py - b.cy;
   const double dx = fabs(x0 * 1.0 + y0 * 0.0);

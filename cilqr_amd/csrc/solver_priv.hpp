@@ -236,6 +236,10 @@ struct cilqr_solver {
   cilqr::pinned_mem sp_host;
   cilqr::dev_mem sp_tab, sp_in, sp_out, ps_work, ps_points;
   int scene_chunk = 0;            // CILQR_OPT_SCENE_CHUNK
+  // cilqr_check_collisions_batch (collision_batch.hip), grown likewise: the barrier table on its way to the device with the
+  // count of colliding scenes on its way back, the staging of HOST scenes and rows, of HOST masks and counts
+  cilqr::pinned_mem cc_tab_host;
+  cilqr::dev_mem cc_tab, cc_in, cc_out;
 };
 
 namespace cilqr {

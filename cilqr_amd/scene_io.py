@@ -22,7 +22,9 @@ cilqr_build_corridors / cilqr_lane_constraints.
 """
 from __future__ import annotations
 
+import bisect
 import dataclasses
+import math
 import struct
 
 import numpy as np
@@ -194,6 +196,138 @@ def environment_points(scene: Scene, times, multiple_sample: bool = False) -> tu
         out[k, :len(p)] = p
         cnt[k] = len(p)
     return out, cnt
+
+
+def _polygon_has_point(q: np.ndarray, px: float, py: float) -> bool:
+    """Polygon2d::IsPointIn (polygon2d.cpp:120-140) behind the bounding box of BuildFromPoints."""
+    if px < q[:, 0].min() or px > q[:, 0].max() or py < q[:, 1].min() or py > q[:, 1].max():
+        return False
+    inside = False
+    j = len(q) - 1
+    for i in range(len(q)):
+        xi, yi, xj, yj = q[i, 0], q[i, 1], q[j, 0], q[j, 1]
+        if (yi > py) != (yj > py):
+            side = (xi - px) * (yj - py) - (xj - px) * (yi - py)
+            if (side > 0.0) if yi < yj else (side < 0.0):
+                inside = not inside
+        j = i
+    return inside
+
+
+def _square_has_points(cx: float, cy: float, h: float, pts: np.ndarray) -> np.ndarray:
+    """Box2d::IsPointIn at heading 0 (box2d.cpp:123-129) for every row of pts."""
+    return (np.abs(pts[:, 0] - cx) <= h + K_MATH_EPS) & (np.abs(pts[:, 1] - cy) <= h + K_MATH_EPS)
+
+
+def _polygon_overlaps_square(q: np.ndarray, cx: float, cy: float, h: float) -> bool:
+    """Polygon2d::HasOverlap(Box2d) (polygon2d.cpp:150-164): boxes apart -> no; a vertex in the square -> yes; else a
+    corner of the square in the polygon."""
+    if cx + h < q[:, 0].min() or cx - h > q[:, 0].max() or cy + h < q[:, 1].min() or cy - h > q[:, 1].max():
+        return False
+    if _square_has_points(cx, cy, h, q).any():
+        return True
+    return any(_polygon_has_point(q, x, y) for x, y in ((cx + h, cy - h), (cx + h, cy + h), (cx - h, cy + h), (cx - h, cy - h)))
+
+
+def vehicle_discs(cfg) -> tuple:
+    """(radius, rear offset, front offset) of the two collision discs (vehicle_param.h:76-95); cfg carries wheel_base,
+    rear_hang_length, front_hang_length and width (api.DpConfig, or anything with those attributes)."""
+    length = cfg.wheel_base + cfg.rear_hang_length + cfg.front_hang_length
+    return math.hypot(0.25 * length, 0.5 * cfg.width), 0.25 * length - cfg.rear_hang_length, 0.75 * length - cfg.rear_hang_length
+
+
+def _normalize_angle(a: float) -> float:
+    a = math.fmod(a + math.pi, 2.0 * math.pi)      # math_utils.cpp:53-59
+    if a < 0.0:
+        a += 2.0 * math.pi
+    return a - math.pi
+
+
+def _evaluate_station(c: list, stations: list, station: float) -> tuple:
+    """DiscretizedTrajectory::EvaluateStation (discretized_trajectory.cpp:117-128, :66-89) on the rows of a centre line:
+    (x, y, theta, left_bound, right_bound) at `station`."""
+    n = len(c)
+    if station >= stations[-1]:
+        it = n - 1
+    elif station < stations[0]:
+        it = 0
+    else:
+        it = bisect.bisect_left(stations, station)      # first point with s >= station
+    it = max(it, 1)
+    p0, p1 = c[it - 1], c[it]
+    s0, s1 = p0[0], p1[0]
+    if abs(s1 - s0) < K_MATH_EPS:
+        return p0[1], p0[2], p0[3], p0[5], p0[6]
+    w = (station - s0) / (s1 - s0)
+    a0, a1 = _normalize_angle(p0[3]), _normalize_angle(p1[3])      # math::slerp, math_utils.h:208-225
+    d = a1 - a0
+    if d > math.pi:
+        d = d - 2 * math.pi
+    elif d < -math.pi:
+        d = d + 2 * math.pi
+    theta = _normalize_angle(a0 + d * ((station - s0) / (s1 - s0)))
+    lin = lambda e: (1 - w) * p0[e] + w * p1[e]
+    return lin(1), lin(2), theta, lin(5), lin(6)
+
+
+def sorted_road_barriers(center: np.ndarray) -> np.ndarray:
+    """Environment::set_reference (environment.cpp:20-43): the centre line evaluated every 0.1 m of station and shifted
+    by +left_bound / -right_bound along its normal, left and right point of a station one after the other, then stably
+    sorted by x: [n,2].  Plain Python floats and the math module, so every operation is the C library's."""
+    c = [[float(v) for v in row] for row in np.asarray(center, float)]
+    stations = [row[0] for row in c]
+    start_s, back_s = stations[0], stations[-1]
+    out = []
+    for i in range(int((back_s - start_s) / 0.1) + 1):
+        s = start_s + i * 0.1
+        x, y, th, lb, rb = _evaluate_station(c, stations, s)
+        for l in (lb, -rb):                               # ReferenceLine::GetCartesian, cpp:199-203
+            out.append((x - l * math.sin(th), y + l * math.cos(th)))
+    both = np.array(out, dtype=np.float64).reshape(-1, 2)
+    return both[np.argsort(both[:, 0], kind="stable")]
+
+
+def environment_collisions(center: np.ndarray, scene: Scene, cfg, times, poses, buffer: float = 0.0, barrier=None) -> tuple:
+    """Environment::CheckOptimizationCollision(time, pose, collision_buffer) (environment.cpp:92-111) for every knot, all
+    six tests made: (mask [K] uint8, first_hit, n_hit).  Bit 0 / 1 / 2: the rear disc against a static polygon / a road
+    barrier point / a dynamic polygon; bits 3 - 5: the front disc.  times [K], poses [K,3] = x, y, theta.  The discs
+    are axis-aligned squares of half side radius + buffer; the barrier window is two upper_bounds on x plus the one
+    predecessor; a dynamic obstacle is absent when time[0] > t or time[-1] < t (no epsilon, cpp:117), else its pose is
+    the first sample with t < time[k], past the end the last.  `barrier`: sorted_road_barriers(center), to build it once
+    for many scenes."""
+    radius, r2x, f2x = vehicle_discs(cfg)
+    h = radius + buffer
+    if barrier is None:
+        barrier = sorted_road_barriers(center)
+    bx = np.ascontiguousarray(barrier[:, 0])
+    statics = [np.asarray(p, float).reshape(-1, 2) for p in scene.static if len(p) >= 1]
+    mask = np.zeros(len(times), dtype=np.uint8)
+    for k, (t, (x, y, th)) in enumerate(zip(times, poses)):
+        placed = []
+        for d in scene.dynamic:
+            tt = d.trajectory[:, 0]
+            if len(d.polygon) < 1 or len(tt) < 1 or tt[0] > t or tt[-1] < t:
+                continue
+            i = min(int(np.searchsorted(tt, t, side="right")), len(tt) - 1)   # first sample with t < time; NaN sorts last
+            _, ox, oy, oth = d.trajectory[i]
+            c, s = math.cos(oth), math.sin(oth)     # Pose::transform (pose.h:40-46): x + rx cos - ry sin, in that order
+            placed.append(np.stack([ox + d.polygon[:, 0] * c - d.polygon[:, 1] * s,
+                                    oy + d.polygon[:, 0] * s + d.polygon[:, 1] * c], axis=1))
+        ct, st = math.cos(th), math.sin(th)
+        for shift, off in ((0, r2x), (3, f2x)):
+            cx, cy = x + off * ct, y + off * st
+            if any(_polygon_overlaps_square(q, cx, cy, h) for q in statics):
+                mask[k] |= 1 << shift
+            if len(bx) and not (cx + h < bx[0] or cx - h > bx[-1]):
+                first = int(np.searchsorted(bx, cx - h, side="right"))
+                last = int(np.searchsorted(bx, cx + h, side="right"))
+                first = max(first - 1, 0)
+                if _square_has_points(cx, cy, h, barrier[first:last]).any():
+                    mask[k] |= 2 << shift
+            if any(_polygon_overlaps_square(q, cx, cy, h) for q in placed):
+                mask[k] |= 4 << shift
+    hit = np.flatnonzero(mask)
+    return mask, (int(hit[0]) if len(hit) else -1), int(len(hit))
 
 
 def road_barriers(center: np.ndarray) -> tuple:

@@ -427,6 +427,40 @@ int cilqr_road_barriers(const double* center, int32_t n_center, double* left, do
 int cilqr_dp_plan(const cilqr_dp_config* cfg, const cilqr_scene* scene, const double* start3, double* coarse,
                   int32_t n_knots);
 
+/* ---- which knots of a trajectory touch the scene: Environment::CheckOptimizationCollision(time, pose, collision_buffer)
+ * (algorithm/utils/environment.cpp:92-111) for every knot; one scene on the host ----
+ * The solver's constraints are barriers on a corridor: a trajectory it returns, converged or not, can still cut a polygon
+ * or a road barrier.  This is the reference's own test for that, asked about every row of a trajectory.  Per knot, with
+ * h = radius + collision_buffer and radius / the disc offsets derived from cfg as for the DP planner
+ * (vehicle_param.h:76-95): the two vehicle discs, centres x + offset cos(theta), y + offset sin(theta), as axis-aligned
+ * squares of half side h against
+ *   - the static polygons (Polygon2d::HasOverlap(Box2d), polygon2d.cpp:150-164; Box2d::IsPointIn with its 1e-10);
+ *   - the x-sorted road barrier points between two upper_bounds on x, plus the one predecessor (environment.cpp:54-80);
+ *   - the dynamic polygons at the knot's time t.  An obstacle is absent when its vertex or sample count is < 1, when
+ *     time[0] > t or when time[T-1] < t (no epsilon, cpp:117 -- not the rule of the Query...Points calls); otherwise its
+ *     pose is the first sample with t < time[k], past the end the last one (the reference dereferences end() there),
+ *     placed in Pose::transform order and boxed as Polygon2d::BuildFromPoints does.  Sample times are taken as
+ *     non-decreasing.
+ * All six tests are made, none is short-circuited; mask[k] != 0 is exactly the reference's bool.  Rear / front are the
+ * geometric discs (offsets length / 4 - rear_hang and 3 length / 4 - rear_hang), not the reference's swapped variable
+ * names.  Non-finite poses are no error: the arithmetic decides (in practice every comparison is false).
+ * Only time, x, y and theta are read from a row: */
+#define CILQR_ROWS_TRAJ 0     /* [K][CILQR_TRAJ_FIELDS]    time 0, x 1, y 2, theta 3 */
+#define CILQR_ROWS_PLAN 1     /* [K][CILQR_PLAN_FIELDS]    time 0, x 2, y 3, theta 4 */
+#define CILQR_ROWS_COARSE 2   /* [K][CILQR_COARSE_FIELDS]  time 0, x 2, y 3, theta 4 */
+#define CILQR_HIT_REAR_STATIC 1     /* mask bits: the rear disc against a static polygon, */
+#define CILQR_HIT_REAR_BARRIER 2    /*            a road barrier point,                   */
+#define CILQR_HIT_REAR_DYNAMIC 4    /*            a dynamic polygon;                      */
+#define CILQR_HIT_FRONT_STATIC 8    /* the front disc likewise */
+#define CILQR_HIT_FRONT_BARRIER 16
+#define CILQR_HIT_FRONT_DYNAMIC 32
+/* mask [n_knots] and n_hit are optional (NULL to skip); *first_hit = the first knot with a non-zero mask, -1 if there is
+ * none; *n_hit = how many knots have one.  A static or dynamic slot with 0 vertices is unused.  CILQR_ERR_NULL;
+ * CILQR_ERR_ARG for an unknown layout, n_knots < 1, a negative or non-finite collision_buffer, n_center < 2, a negative
+ * count; CILQR_ERR_CAPACITY beyond the CILQR_DP_MAX_* limits below (the batched call accepts exactly the same scenes). */
+int cilqr_check_collisions(const cilqr_dp_config* cfg, const cilqr_scene* scene, int32_t layout, const double* rows,
+                           int32_t n_knots, double collision_buffer, uint8_t* mask, int32_t* first_hit, int32_t* n_hit);
+
 /* ---- the same planner for B scenes per call, on the GPU (ABI 7) ----
  * One road (centre line) for the whole batch, as the lane tables of cilqr_problem_batch are; per scene a fixed number of
  * obstacle slots, every polygon stored with max_vertices vertices and every trajectory with max_samples samples
@@ -499,6 +533,29 @@ int cilqr_dp_plan_batch(cilqr_handle h, const cilqr_dp_config* cfg, const cilqr_
 int cilqr_scene_points_batch(cilqr_handle h, const cilqr_scene_batch* scenes, int32_t n_knots, const double* knot_times,
                              int32_t is_multiple_sample, int32_t max_points, double* points, int32_t* point_count,
                              int32_t* scene_ok);
+
+/* ---- cilqr_check_collisions for B scenes per call, on the GPU (kernels_collision.hip) ----
+ * The audit behind cilqr_plan_scenes_batch: its `plan` rows (CILQR_ROWS_PLAN), the solver's traj (CILQR_ROWS_TRAJ) or
+ * the DP planner's coarse9 (CILQR_ROWS_COARSE) against the scenes they were planned in, without leaving the device.  One
+ * workgroup per scene; per knot the semantics are those of the host call above and the arithmetic is the DP kernels':
+ * the vehicle heading goes through their sin / cos, the obstacle placement through the device library's cos / sin
+ * (cilqr_device_math fn 7 / 8), so a verdict can differ from the host's only where a point lies within rounding of a
+ * square's side or a polygon's edge.
+ *   rows      [B][n_knots][fields of the layout]   (memory as scenes->memory, like the three arrays below)
+ *   mask      [B][n_knots] CILQR_HIT_* bits, optional (NULL to skip)
+ *   first_hit [B]  the first knot with a non-zero mask, -1: none
+ *   n_hit     [B]  knots with a non-zero mask, optional
+ *   *n_colliding (HOST, optional): the scenes with first_hit >= 0
+ * Checked before anything is launched: CILQR_ERR_NULL; CILQR_ERR_ARG for a bad batch, sizes, layout or memory flag,
+ * n_knots < 1, a negative or non-finite collision_buffer, n_center < 2 and HOST counts that are negative or above their
+ * max_*; CILQR_ERR_CAPACITY beyond the CILQR_DP_MAX_* limits (n_knots included); CILQR_ERR_STATE while solves are submitted
+ * on the handle.  With DEVICE arrays the counts are checked in the kernel: such a scene gets first_hit -2, n_hit 0 and a
+ * zero mask row, the others are unaffected.  Runs on the handle's stream and waits for that stream only; DEVICE arrays
+ * need no work space beyond the barrier table, HOST arrays are staged in blocks that belong to the handle and grow to
+ * the largest call. */
+int cilqr_check_collisions_batch(cilqr_handle h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes,
+                                 int32_t layout, const double* rows, int32_t n_knots, double collision_buffer,
+                                 uint8_t* mask, int32_t* first_hit, int32_t* n_hit, int32_t* n_colliding);
 
 /* ---- TrajectoryPlanner::Plan for B scenes per call (trajectory_planner.cpp:28-162) ----
  * scene batch -> cilqr_dp_plan_batch -> cilqr_scene_points_batch (at the time column the planner produced, with

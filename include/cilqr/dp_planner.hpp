@@ -255,13 +255,35 @@ class DpEnvironment {
     if (!d.time.empty()) dynamics_.push_back(std::move(d));
   }
 
-  // environment.cpp:92-111 (collision_buffer = 0)
-  bool CheckOptimizationCollision(double time, double x, double y, double theta) const {
+  // the bits of CollisionMask: which disc met what (rear / front are the geometric discs, r2x / f2x)
+  enum : unsigned {
+    kRearStatic = 1u, kRearBarrier = 2u, kRearDynamic = 4u, kFrontStatic = 8u, kFrontBarrier = 16u, kFrontDynamic = 32u
+  };
+
+  // environment.cpp:92-111; the two discs as squares of half side radius + collision_buffer (radius + 0.0 is radius)
+  bool CheckOptimizationCollision(double time, double x, double y, double theta, double collision_buffer = 0.0) const {
+    const double h = radius_ + collision_buffer;
     const double ct = std::cos(theta), st = std::sin(theta);
     const double ax = x + f2x_ * ct, ay = y + f2x_ * st;   // vehicle_param.h:88-95
     const double bx = x + r2x_ * ct, by = y + r2x_ * st;
-    return StaticCollision(bx, by) || StaticCollision(ax, ay) || DynamicCollision(time, bx, by) ||
-           DynamicCollision(time, ax, ay);
+    return StaticCollision(bx, by, h) || StaticCollision(ax, ay, h) || DynamicCollision(time, bx, by, h) ||
+           DynamicCollision(time, ax, ay, h);
+  }
+
+  // the same test with nothing short-circuited: every one of the six (disc, kind of obstacle) verdicts; != 0 is the bool above
+  unsigned CollisionMask(double time, double x, double y, double theta, double collision_buffer = 0.0) const {
+    const double h = radius_ + collision_buffer;
+    const double ct = std::cos(theta), st = std::sin(theta);
+    const Square front = MakeSquare(x + f2x_ * ct, y + f2x_ * st, h);
+    const Square rear = MakeSquare(x + r2x_ * ct, y + r2x_ * st, h);
+    unsigned mask = 0;
+    if (StaticPolygonCollision(rear)) mask |= kRearStatic;
+    if (BarrierCollision(rear)) mask |= kRearBarrier;
+    if (DynamicCollision(time, rear)) mask |= kRearDynamic;
+    if (StaticPolygonCollision(front)) mask |= kFrontStatic;
+    if (BarrierCollision(front)) mask |= kFrontBarrier;
+    if (DynamicCollision(time, front)) mask |= kFrontDynamic;
+    return mask;
   }
 
  private:
@@ -279,13 +301,11 @@ class DpEnvironment {
     return q;
   }
 
-  // axis-aligned square of half side radius_ centred at (cx, cy), as Box2d(AABox2d) (box2d.cpp:93-105)
+  // axis-aligned square of half side h centred at (cx, cy), as Box2d(AABox2d) (box2d.cpp:93-105)
   struct Square {
     double cx, cy, h, min_x, max_x, min_y, max_y;
   };
-  Square MakeSquare(double cx, double cy) const {
-    return Square{cx, cy, radius_, cx - radius_, cx + radius_, cy - radius_, cy + radius_};
-  }
+  static Square MakeSquare(double cx, double cy, double h) { return Square{cx, cy, h, cx - h, cx + h, cy - h, cy + h}; }
   static bool SquareHasPoint(const Square& b, const DpPoint2& p) {   // Box2d::IsPointIn, heading 0 (box2d.cpp:123-129)
     const double x0 = p.x - b.cx, y0 = p.y - b.cy;
     const double dx = std::abs(x0 * 1.0 + y0 * 0.0);
@@ -315,10 +335,16 @@ class DpEnvironment {
            PolyHasPoint(q, b.cx - b.h, b.cy + b.h) || PolyHasPoint(q, b.cx - b.h, b.cy - b.h);
   }
 
-  bool StaticCollision(double cx, double cy) const {   // environment.cpp:45-80
-    const Square b = MakeSquare(cx, cy);
+  bool StaticCollision(double cx, double cy, double h) const {   // environment.cpp:45-80
+    const Square b = MakeSquare(cx, cy, h);
+    return StaticPolygonCollision(b) || BarrierCollision(b);
+  }
+  bool StaticPolygonCollision(const Square& b) const {   // environment.cpp:47-52
     for (const auto& q : statics_)
       if (Overlap(q, b)) return true;
+    return false;
+  }
+  bool BarrierCollision(const Square& b) const {   // environment.cpp:54-80
     if (barrier_.empty()) return false;
     if (b.max_x < barrier_.front().x || b.min_x > barrier_.back().x) return false;
     auto upper = [&](double val) {   // first barrier point with val < point.x
@@ -338,8 +364,10 @@ class DpEnvironment {
     return false;
   }
 
-  bool DynamicCollision(double time, double cx, double cy) const {   // environment.cpp:113-130
-    const Square b = MakeSquare(cx, cy);
+  bool DynamicCollision(double time, double cx, double cy, double h) const {
+    return DynamicCollision(time, MakeSquare(cx, cy, h));
+  }
+  bool DynamicCollision(double time, const Square& b) const {   // environment.cpp:113-130
     for (const auto& d : dynamics_) {
       if (d.time.front() > time || d.time.back() < time) continue;
       size_t i = 0;   // first sample with time < sample time (std::upper_bound)
