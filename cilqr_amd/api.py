@@ -75,6 +75,11 @@ class SolutionBatch(C.Structure):
     ]
 
 
+class WarmStart(C.Structure):
+    """cilqr_warm_start (include/cilqr.h): control rows of earlier trajectories as the first iterate of a solve."""
+    _fields_ = [("memory", C.c_int32), ("layout", C.c_int32), ("rows", C.c_void_p), ("shift", C.c_void_p)]
+
+
 class CorridorConfig(C.Structure):
     """CorridorConfig of the reference (algorithm/params/planner_config.h:75-86)."""
     _fields_ = [("max_diff_x", C.c_double), ("max_diff_y", C.c_double), ("radius", C.c_double),
@@ -115,6 +120,7 @@ PLAN_OK, PLAN_DP_FAILED, PLAN_CORRIDOR_FAILED = 0, 1, 2
 # cilqr_check_collisions / cilqr_check_collisions_batch: row layouts (CILQR_ROWS_*), doubles per row and the columns of
 # time, x, y, theta in each; the bits of a knot's mask (CILQR_HIT_*)
 ROWS_TRAJ, ROWS_PLAN, ROWS_COARSE = 0, 1, 2
+ROWS_CONTROLS = 3   # cilqr_warm_start only: [N][2] jerk, delta_rate
 ROWS_FIELDS = {ROWS_TRAJ: 10, ROWS_PLAN: PLAN_FIELDS, ROWS_COARSE: COARSE_FIELDS}
 ROWS_POSE_COLUMNS = {ROWS_TRAJ: (0, 1, 2, 3), ROWS_PLAN: (0, 2, 3, 4), ROWS_COARSE: (0, 2, 3, 4)}
 HIT_REAR_STATIC, HIT_REAR_BARRIER, HIT_REAR_DYNAMIC = 1, 2, 4
@@ -154,6 +160,7 @@ EXPORTS = [
     "cilqr_check_collisions", "cilqr_check_collisions_batch",
     "cilqr_road_barriers", "cilqr_default_tracker_config",
     "cilqr_set_tracker_config",
+    "cilqr_solve_batch_warm", "cilqr_submit_warm", "cilqr_stage_load_warm", "cilqr_pool_submit_warm", "cilqr_multi_solve_warm",
     "cilqr_multi_create", "cilqr_multi_destroy", "cilqr_multi_solve", "cilqr_multi_set_option", "cilqr_multi_shards",
     "cilqr_multi_device_bytes",
     "cilqr_pool_create", "cilqr_pool_destroy", "cilqr_pool_submit", "cilqr_pool_wait", "cilqr_pool_depth", "cilqr_pool_handle_at",
@@ -195,6 +202,11 @@ def lib():
         L.cilqr_solve_batch.argtypes = [C.c_void_p, C.POINTER(ProblemBatch), C.POINTER(SolutionBatch)]
         L.cilqr_submit.argtypes = [C.c_void_p, C.POINTER(ProblemBatch), C.POINTER(SolutionBatch)]
         L.cilqr_wait.argtypes = [C.c_void_p]
+        L.cilqr_solve_batch_warm.argtypes = [C.c_void_p, C.POINTER(ProblemBatch), C.POINTER(WarmStart), C.POINTER(SolutionBatch)]
+        L.cilqr_submit_warm.argtypes = [C.c_void_p, C.POINTER(ProblemBatch), C.POINTER(WarmStart), C.POINTER(SolutionBatch)]
+        L.cilqr_stage_load_warm.argtypes = [C.c_void_p, C.POINTER(ProblemBatch), C.POINTER(WarmStart)]
+        L.cilqr_pool_submit_warm.argtypes = [C.c_void_p, C.POINTER(ProblemBatch), C.POINTER(WarmStart), C.POINTER(SolutionBatch)]
+        L.cilqr_multi_solve_warm.argtypes = [C.c_void_p, C.POINTER(ProblemBatch), C.POINTER(WarmStart), C.POINTER(SolutionBatch)]
         L.cilqr_default_corridor_config.argtypes = [C.POINTER(CorridorConfig)]
         L.cilqr_default_corridor_config.restype = None
         L.cilqr_build_corridors.argtypes = [C.c_void_p, C.POINTER(CorridorConfig), C.c_int32, C.c_int32, C.c_void_p,
@@ -280,6 +292,41 @@ def _f64(a):
 
 def _ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _is_device_tensor(a) -> bool:
+    return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
+
+
+def make_warm(warm, n_steps: int | None = None):
+    """warm: None, a WarmStart, or (rows, shift=None, layout=ROWS_TRAJ) -- rows / shift NumPy arrays (host memory) or torch
+    device tensors (contiguous float64 / int32), both of the same kind, the kind the problem's arrays are.
+    Returns (WarmStart or None, what must stay alive until the solve is collected)."""
+    if warm is None or isinstance(warm, WarmStart):
+        return warm, None
+    if isinstance(warm, dict):
+        rows, shift, layout = warm["rows"], warm.get("shift"), warm.get("layout", ROWS_TRAJ)
+    else:
+        warm = tuple(warm) if isinstance(warm, (tuple, list)) else (warm,)
+        rows = warm[0]
+        shift = warm[1] if len(warm) > 1 else None
+        layout = warm[2] if len(warm) > 2 else ROWS_TRAJ
+    if _is_device_tensor(rows):
+        if not rows.is_cuda or not rows.is_contiguous() or str(rows.dtype) != "torch.float64":
+            raise ValueError("warm rows on the device: a contiguous float64 tensor")
+        if shift is not None and (not _is_device_tensor(shift) or not shift.is_cuda or not shift.is_contiguous()
+                                  or str(shift.dtype) != "torch.int32"):
+            raise ValueError("warm shift on the device: a contiguous int32 tensor, like the rows")
+        w = WarmStart(MEM_DEVICE, int(layout), rows.data_ptr(), shift.data_ptr() if shift is not None else None)
+        return w, (rows, shift)
+    rows = _f64(rows)
+    shift = None if shift is None else np.ascontiguousarray(shift, dtype=np.int32)
+    w = WarmStart(MEM_HOST, int(layout), rows.ctypes.data, shift.ctypes.data if shift is not None else None)
+    return w, (rows, shift)
+
+
+def _warm_ref(w):
+    return C.byref(w) if w is not None else None
 
 
 class BatchIlqrOptimizer:
@@ -370,12 +417,24 @@ class BatchIlqrOptimizer:
     def device_bytes(self) -> int:
         return int(self.L.cilqr_device_bytes(self.h))
 
-    def solve_raw(self, prob: ProblemBatch, sol: SolutionBatch) -> int:
-        return self.L.cilqr_solve_batch(self.h, C.byref(prob), C.byref(sol))
+    def solve_raw(self, prob: ProblemBatch, sol: SolutionBatch, warm: "WarmStart | None" = None) -> int:
+        """warm: a WarmStart whose arrays live where the problem's do (make_warm), None: a plain solve"""
+        if warm is None:
+            return self.L.cilqr_solve_batch(self.h, C.byref(prob), C.byref(sol))
+        return self.L.cilqr_solve_batch_warm(self.h, C.byref(prob), C.byref(warm), C.byref(sol))
 
-    def submit_raw(self, prob: ProblemBatch, sol: SolutionBatch) -> int:
-        """Asynchronous solve_raw; collect the result code with wait()."""
-        return self.L.cilqr_submit(self.h, C.byref(prob), C.byref(sol))
+    def submit_raw(self, prob: ProblemBatch, sol: SolutionBatch, warm: "WarmStart | None" = None) -> int:
+        """Asynchronous solve_raw; collect the result code with wait().  The warm arrays stay alive until then, too."""
+        if warm is None:
+            return self.L.cilqr_submit(self.h, C.byref(prob), C.byref(sol))
+        return self.L.cilqr_submit_warm(self.h, C.byref(prob), C.byref(warm), C.byref(sol))
+
+    def stage_load_raw(self, prob: ProblemBatch, warm: "WarmStart | None" = None) -> int:
+        rc = self.L.cilqr_stage_load_warm(self.h, C.byref(prob), _warm_ref(warm))
+        if rc == OK:
+            self.B = prob.batch
+            self.nl, self.nr = prob.n_left, prob.n_right
+        return rc
 
     def wait(self) -> int:
         return self.L.cilqr_wait(self.h)
@@ -430,10 +489,55 @@ class BatchIlqrOptimizer:
             prob.lane_group_right = a["g_right"].ctypes.data
         return prob, a
 
-    def plan(self, scene: dict, max_iter_trajs: int = 0, check: bool = True, alpha_trace: bool = False):
+    def _plan_solution(self, B, max_iter_trajs, alpha_trace):
+        K, M = self.K, self.cfg.max_iter
+        r = dict(traj=np.zeros((B, K, 10)), cost_hist=np.zeros((B, M + 1, 5)), n_cost=np.zeros(B, np.int32),
+                 status=np.zeros(B, np.int32), n_iter=np.zeros(B, np.int32),
+                 iter_trajs=np.zeros((B, max_iter_trajs, K, 10)) if max_iter_trajs else None,
+                 n_iter_trajs=np.zeros(B, np.int32) if max_iter_trajs else None,
+                 alpha_trace=np.full((B, M), -3, np.int8) if alpha_trace else None)
+        sol = SolutionBatch(MEM_HOST, max_iter_trajs, _ptr(r["traj"]), _ptr(r["cost_hist"]), _ptr(r["n_cost"]),
+                            _ptr(r["status"]), _ptr(r["n_iter"]), _ptr(r["iter_trajs"]), _ptr(r["n_iter_trajs"]),
+                            _ptr(r["alpha_trace"]))
+        return sol, r
+
+    def submit(self, scene: dict, max_iter_trajs: int = 0, alpha_trace: bool = False, warm=None):
+        """Asynchronous plan(): returns a ticket; collect(ticket) -- oldest first -- waits and returns plan()'s dict."""
+        prob, keep = self._host_problem(scene)
+        w, wkeep = make_warm(warm, self.N)
+        sol, r = self._plan_solution(prob.batch, max_iter_trajs, alpha_trace)
+        rc = self.submit_raw(prob, sol, w)
+        if rc != OK:
+            raise CilqrError(rc, "in cilqr_submit")
+        return dict(result=r, keep=(prob, keep, w, wkeep, sol))
+
+    def collect(self, ticket: dict, check: bool = True):
+        rc = self.wait()
+        ticket["keep"] = None
+        if rc != OK:
+            if check:
+                raise CilqrError(rc, "in cilqr_wait")
+            return dict(rc=rc)
+        return dict(rc=rc, **ticket["result"])
+
+    def plan(self, scene: dict, max_iter_trajs: int = 0, check: bool = True, alpha_trace: bool = False, warm=None):
         """scene: dict from cilqr_amd.scenario.generate (problem-major numpy arrays).
         alpha_trace=True adds "alpha_trace" [B, max_iter] int8: the accepted step-size index of every
-        iteration (-1 all rejected, -2 left before the line search, -3 not run)."""
+        iteration (-1 all rejected, -2 left before the line search, -3 not run).
+        warm=(rows, shift=None, layout=ROWS_TRAJ): start from the controls of earlier trajectories (make_warm,
+        cilqr_amd.warm.warm_controls for the rule); the returned dict has the same shape."""
+        if warm is not None:
+            prob, keep = self._host_problem(scene)
+            w, wkeep = make_warm(warm, self.N)
+            sol, r = self._plan_solution(prob.batch, max_iter_trajs, alpha_trace)
+            rc = self.solve_raw(prob, sol, w)
+            del keep, wkeep
+            if rc != OK:
+                if check:
+                    raise CilqrError(rc, "in cilqr_solve_batch_warm")
+                return dict(rc=rc)
+            self.B = prob.batch
+            return dict(rc=rc, **r)
         prob, keep = self._host_problem(scene)
         B, K, M = prob.batch, self.K, self.cfg.max_iter
         traj = np.zeros((B, K, 10))
@@ -461,8 +565,13 @@ class BatchIlqrOptimizer:
         if rc != OK:
             raise CilqrError(rc, what)
 
-    def stage_load(self, scene: dict):
+    def stage_load(self, scene: dict, warm=None):
+        """warm (see plan): the stage_init_guess that follows produces the warm first iterate"""
         prob, keep = self._host_problem(scene)
+        if warm is not None:
+            w, wkeep = make_warm(warm, self.N)
+            self._chk(self.stage_load_raw(prob, w), "stage_load_warm")
+            return
         self._chk(self.L.cilqr_stage_load(self.h, C.byref(prob)), "stage_load")
         self.B = prob.batch
         self.nl, self.nr = prob.n_left, prob.n_right
@@ -840,8 +949,29 @@ class HandlePool:
     def device_bytes(self) -> int:
         return int(self.L.cilqr_pool_device_bytes(self.h))
 
-    def submit_raw(self, prob: ProblemBatch, sol: SolutionBatch) -> int:
-        return self.L.cilqr_pool_submit(self.h, C.byref(prob), C.byref(sol))
+    def submit_raw(self, prob: ProblemBatch, sol: SolutionBatch, warm: "WarmStart | None" = None) -> int:
+        if warm is None:
+            return self.L.cilqr_pool_submit(self.h, C.byref(prob), C.byref(sol))
+        return self.L.cilqr_pool_submit_warm(self.h, C.byref(prob), C.byref(warm), C.byref(sol))
+
+    def submit(self, scene: dict, max_iter_trajs: int = 0, alpha_trace: bool = False, warm=None):
+        """Asynchronous BatchIlqrOptimizer.plan on the pool's next handle: returns a ticket for collect() (oldest first)."""
+        prob, keep = BatchIlqrOptimizer._host_problem(self, scene)
+        w, wkeep = make_warm(warm, self.cfg.n_steps)
+        sol, r = BatchIlqrOptimizer._plan_solution(self, prob.batch, max_iter_trajs, alpha_trace)
+        rc = self.submit_raw(prob, sol, w)
+        if rc != OK:
+            raise CilqrError(rc, "in cilqr_pool_submit")
+        return dict(result=r, keep=(prob, keep, w, wkeep, sol))
+
+    def collect(self, ticket: dict, check: bool = True):
+        rc = self.wait()
+        ticket["keep"] = None
+        if rc != OK:
+            if check:
+                raise CilqrError(rc, "in cilqr_pool_wait")
+            return dict(rc=rc)
+        return dict(rc=rc, **ticket["result"])
 
     def wait(self) -> int:
         return self.L.cilqr_pool_wait(self.h)
@@ -906,10 +1036,23 @@ class MultiDeviceOptimizer:
     def device_bytes(self) -> int:
         return int(self.L.cilqr_multi_device_bytes(self.h))
 
-    def solve_raw(self, prob: ProblemBatch, sol: SolutionBatch) -> int:
-        return self.L.cilqr_multi_solve(self.h, C.byref(prob), C.byref(sol))
+    def solve_raw(self, prob: ProblemBatch, sol: SolutionBatch, warm: "WarmStart | None" = None) -> int:
+        if warm is None:
+            return self.L.cilqr_multi_solve(self.h, C.byref(prob), C.byref(sol))
+        return self.L.cilqr_multi_solve_warm(self.h, C.byref(prob), C.byref(warm), C.byref(sol))
 
-    def plan(self, scene: dict, max_iter_trajs: int = 0, check: bool = True, alpha_trace: bool = False):
+    def plan(self, scene: dict, max_iter_trajs: int = 0, check: bool = True, alpha_trace: bool = False, warm=None):
+        if warm is not None:
+            prob, keep = BatchIlqrOptimizer._host_problem(self, scene)
+            w, wkeep = make_warm(warm, self.cfg.n_steps)
+            sol, r = BatchIlqrOptimizer._plan_solution(self, prob.batch, max_iter_trajs, alpha_trace)
+            rc = self.solve_raw(prob, sol, w)
+            del keep, wkeep
+            if rc != OK:
+                if check:
+                    raise CilqrError(rc, "in cilqr_multi_solve_warm")
+                return dict(rc=rc)
+            return dict(rc=rc, **r)
         prob, keep = BatchIlqrOptimizer._host_problem(self, scene)
         B, K, M = prob.batch, self.K, self.cfg.max_iter
         traj = np.zeros((B, K, 10))

@@ -293,9 +293,11 @@ void launch_load(const DeviceState& s, int B, const ProblemView& in, const doubl
 // Init guess: time-varying LQR along the goals + clamped closed-loop rollout (iqr, cc:793-842).
 // One lane per problem: backward sweep stores K_i in the gains arena, forward sweep rolls out.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_init_guess(DeviceState s, int B) {
+// warm_shift (nullable): the problems with a shift >= 0 are warm-started (kernels_warm.hip) and left alone here.
+__global__ __launch_bounds__(64) void k_init_guess(DeviceState s, int B, const int* __restrict__ warm_shift) {
   const int slot = blockIdx.x * blockDim.x + threadIdx.x;
   if (slot >= B) return;
+  if (warm_shift != nullptr && warm_shift[slot] >= 0) return;
   const Params& p = s.p;
   const int N = p.N, Bc = s.Bcap;
   const double Qd[6] = {0.001, 0.001, 0.001, 0.001, 0.01, 0.005};  // cc:801-807
@@ -439,11 +441,12 @@ __global__ __launch_bounds__(64) void k_init_guess(DeviceState s, int B) {
 // LDS: jac [N][12] | A 36 | B 12 | P 36 | BtP 12 | AtP 36 | M 4 | BtPA 12 | K 12 | AmBK 36 | Kall [N][12]
 // ---------------------------------------------------------------------------------------------
 constexpr int kIgFixed = 36 + 12 + 36 + 12 + 36 + 4 + 12 + 12 + 36;
-__global__ __launch_bounds__(64) void k_init_guess_wave(DeviceState s, int B) {
+__global__ __launch_bounds__(64) void k_init_guess_wave(DeviceState s, int B, const int* __restrict__ warm_shift) {
   extern __shared__ double ig_lds[];
   // eight consecutive slots -- one 128-byte line of every row -- per XCD (a handful of problems: launched as they are)
   const int slot = (gridDim.x & 63u) == 0 ? xcd_local_position((int)blockIdx.x) : (int)blockIdx.x;
   if (slot >= B) return;
+  if (warm_shift != nullptr && warm_shift[slot] >= 0) return;   // warm-started (kernels_warm.hip): the whole wave leaves
   const int lane = threadIdx.x;
   const Params& p = s.p;
   const int N = p.N, Bc = s.Bcap;
@@ -582,7 +585,7 @@ __global__ __launch_bounds__(64) void k_init_guess_wave(DeviceState s, int B) {
 // Batches up to this size give every problem a wavefront (4096 problems are 4 waves per SIMD of ~0.1 ms each; the one-lane
 // kernel needs 0.185 ms whatever the batch, and wins from there on).  CILQR_INIT_GUESS_WAVE=0 / 1: never / always (tests).
 constexpr int kInitGuessWaveMax = 4096;
-void launch_init_guess(const DeviceState& s, int B, hipStream_t st) {
+void launch_init_guess(const DeviceState& s, int B, hipStream_t st, const int* warm_shift) {
   static const int forced = [] {
     const char* e = std::getenv("CILQR_INIT_GUESS_WAVE");
     return e ? std::atoi(e) : -1;
@@ -590,9 +593,9 @@ void launch_init_guess(const DeviceState& s, int B, hipStream_t st) {
   const size_t lds = ((size_t)s.p.N * 24 + kIgFixed) * sizeof(double);
   const bool wave = forced >= 0 ? forced != 0 : B <= kInitGuessWaveMax;
   if (wave && lds <= 64 * 1024)
-    hipLaunchKernelGGL(k_init_guess_wave, dim3(B >= 64 ? (B + 63) / 64 * 64 : B), dim3(64), lds, st, s, B);
+    hipLaunchKernelGGL(k_init_guess_wave, dim3(B >= 64 ? (B + 63) / 64 * 64 : B), dim3(64), lds, st, s, B, warm_shift);
   else
-    hipLaunchKernelGGL(k_init_guess, dim3((B + 63) / 64), dim3(64), 0, st, s, B);
+    hipLaunchKernelGGL(k_init_guess, dim3((B + 63) / 64), dim3(64), 0, st, s, B, warm_shift);
 }
 
 // ---------------------------------------------------------------------------------------------

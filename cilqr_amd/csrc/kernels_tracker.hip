@@ -112,9 +112,11 @@ struct FollowPt {
 
 }  // namespace
 
-__global__ __launch_bounds__(64) void k_init_guess_tracker(DeviceState s, TrackerParams tp, int B) {
+__global__ __launch_bounds__(64) void k_init_guess_tracker(DeviceState s, TrackerParams tp, int B,
+                                                             const int* __restrict__ warm_shift) {
   const int slot = blockIdx.x * blockDim.x + threadIdx.x;
   if (slot >= B) return;
+  if (warm_shift != nullptr && warm_shift[slot] >= 0) return;   // warm-started (kernels_warm.hip)
   const Params& p = s.p;
   const int K = p.K, Bc = s.Bcap;
   // the coarse trajectory: knot 0 from coarse0 (goals_[0] holds the start state), time_i = i dt (dp_planner.cpp:236)
@@ -319,8 +321,8 @@ __global__ __launch_bounds__(64) void k_init_guess_tracker(DeviceState s, Tracke
   }
 }
 
-void launch_init_guess_tracker(const DeviceState& s, const TrackerParams& tp, int B, hipStream_t st) {
-  hipLaunchKernelGGL(k_init_guess_tracker, dim3((B + 63) / 64), dim3(64), 0, st, s, tp, B);
+void launch_init_guess_tracker(const DeviceState& s, const TrackerParams& tp, int B, hipStream_t st, const int* warm_shift) {
+  hipLaunchKernelGGL(k_init_guess_tracker, dim3((B + 63) / 64), dim3(64), 0, st, s, tp, B, warm_shift);
 }
 
 }  // namespace cilqr

@@ -103,7 +103,15 @@ int64_t cilqr_multi_device_bytes(cilqr_multi_handle m) {
 }
 
 int cilqr_multi_solve(cilqr_multi_handle m, const cilqr_problem_batch* in, cilqr_solution_batch* out) {
+  return cilqr_multi_solve_warm(m, in, nullptr, out);
+}
+
+int cilqr_multi_solve_warm(cilqr_multi_handle m, const cilqr_problem_batch* in, const cilqr_warm_start* warm,
+                           cilqr_solution_batch* out) {
   if (m == nullptr || in == nullptr || out == nullptr) return CILQR_ERR_NULL;
+  if (const int wrc = cilqr_check_warm(in, warm)) return wrc;
+  int wstride = 0, wrows = 0, wcol = 0;
+  if (warm != nullptr) (void)cilqr_warm_geometry(warm->layout, in->n_knots, &wstride, &wrows, &wcol);
   if (in->batch <= 0) return CILQR_ERR_ARG;
   if (in->batch > m->capacity) return CILQR_ERR_CAPACITY;
   if (in->n_lane_groups > 1) return CILQR_ERR_ARG;   // one lane table per call: the groups would straddle the shards
@@ -111,6 +119,7 @@ int cilqr_multi_solve(cilqr_multi_handle m, const cilqr_problem_batch* in, cilqr
   const size_t K = (size_t)in->n_knots, M1 = (size_t)m->max_iter + 1;
   std::vector<cilqr_problem_batch> pin(n);
   std::vector<cilqr_solution_batch> pout(n);
+  std::vector<cilqr_warm_start> pwarm(n);
   std::vector<char> submitted(n, 0);
   int rc = CILQR_OK;
   for (int k = 0; k < n && rc == CILQR_OK; ++k) {
@@ -135,7 +144,12 @@ int cilqr_multi_solve(cilqr_multi_handle m, const cilqr_problem_batch* in, cilqr
     po.iter_trajs = out->iter_trajs ? out->iter_trajs + (size_t)b0 * out->max_iter_trajs * K * CILQR_TRAJ_FIELDS : nullptr;
     po.n_iter_trajs = out->n_iter_trajs ? out->n_iter_trajs + b0 : nullptr;
     po.alpha_trace = out->alpha_trace ? out->alpha_trace + (size_t)b0 * m->max_iter : nullptr;
-    rc = cilqr_submit(m->shard[k], &pi, &po);   // the shard's own host threads drive its device from here on
+    if (warm != nullptr) {   // the shard's rows of the warm arrays
+      pwarm[k] = *warm;
+      pwarm[k].rows = warm->rows + (size_t)b0 * wrows * wstride;
+      pwarm[k].shift = warm->shift ? warm->shift + b0 : nullptr;
+    }
+    rc = cilqr_submit_warm(m->shard[k], &pi, warm ? &pwarm[k] : nullptr, &po);   // the shard's own host threads drive its device from here on
     if (rc == CILQR_OK) submitted[k] = 1;
   }
   for (int k = 0; k < n; ++k) {

@@ -80,10 +80,15 @@ int64_t cilqr_pool_device_bytes(cilqr_pool_handle p) {
 }
 
 int cilqr_pool_submit(cilqr_pool_handle p, const cilqr_problem_batch* in, cilqr_solution_batch* out) {
+  return cilqr_pool_submit_warm(p, in, nullptr, out);
+}
+
+int cilqr_pool_submit_warm(cilqr_pool_handle p, const cilqr_problem_batch* in, const cilqr_warm_start* warm,
+                           cilqr_solution_batch* out) {
   if (p == nullptr || in == nullptr || out == nullptr) return CILQR_ERR_NULL;
   const long long n = (long long)p->handle.size();
   if (p->submitted - p->collected >= kJobRing * n) return CILQR_ERR_STATE;   // the oldest solve has to be waited for first
-  const int rc = cilqr_submit(p->handle[(size_t)(p->submitted % n)], in, out);
+  const int rc = cilqr_submit_warm(p->handle[(size_t)(p->submitted % n)], in, warm, out);
   if (rc == CILQR_OK) ++p->submitted;
   return rc;
 }

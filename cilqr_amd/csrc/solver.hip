@@ -76,6 +76,29 @@ void fill_params(const cilqr_config& c, Params* p) {
   p->shrink_lane = disc_radius;
 }
 
+}  // namespace
+
+bool cilqr_warm_geometry(int32_t layout, int32_t n_knots, int* stride, int* rows_per, int* col) {
+  switch (layout) {
+    case CILQR_ROWS_TRAJ: *stride = CILQR_TRAJ_FIELDS; *rows_per = n_knots; *col = 8; return true;
+    case CILQR_ROWS_PLAN: *stride = CILQR_PLAN_FIELDS; *rows_per = n_knots; *col = 9; return true;
+    case CILQR_ROWS_CONTROLS: *stride = CILQR_NU; *rows_per = n_knots - 1; *col = 0; return true;
+    default: return false;   // CILQR_ROWS_COARSE carries no controls
+  }
+}
+
+int cilqr_check_warm(const cilqr_problem_batch* in, const cilqr_warm_start* warm) {
+  if (warm == nullptr) return CILQR_OK;
+  if (warm->rows == nullptr) return CILQR_ERR_NULL;
+  int stride, rows_per, col;
+  if (!cilqr_warm_geometry(warm->layout, in->n_knots, &stride, &rows_per, &col)) return CILQR_ERR_ARG;
+  if (warm->memory != CILQR_MEM_HOST && warm->memory != CILQR_MEM_DEVICE) return CILQR_ERR_ARG;
+  if (warm->memory != in->memory) return CILQR_ERR_ARG;
+  return CILQR_OK;
+}
+
+namespace {
+
 int check_problem(const cilqr_solver* h, const cilqr_problem_batch* in) {
   if (in == nullptr) return CILQR_ERR_NULL;
   if (in->batch <= 0) return CILQR_ERR_ARG;
@@ -140,19 +163,38 @@ void release_in_buffer(cilqr_solver* h, int k, hipStream_t st) {   // behind the
   h->cv.notify_all();
 }
 
-size_t input_payload_bytes(const cilqr_solver* h, const cilqr_problem_batch* in) {
+// doubles of the warm rows and ints of the shift array that travel with a batch of B problems (0, 0: no warm start)
+void warm_counts(const cilqr_problem_batch* in, const cilqr_warm_start* warm, size_t* n_rows, size_t* n_shift) {
+  *n_rows = 0;
+  *n_shift = 0;
+  int stride = 0, rows_per = 0, col = 0;
+  if (warm == nullptr || !cilqr_warm_geometry(warm->layout, in->n_knots, &stride, &rows_per, &col)) return;
+  *n_rows = (size_t)in->batch * rows_per * stride;
+  *n_shift = warm->shift ? (size_t)in->batch : 0;
+}
+
+size_t input_payload_bytes(const cilqr_solver* h, const cilqr_problem_batch* in, const cilqr_warm_start* warm) {
   const size_t B = (size_t)in->batch, K = (size_t)in->n_knots;
   const bool want_station = h->cfg.init_guess == CILQR_INIT_TRACKER && in->coarse_station != nullptr;
-  return (B * 4 + B * K * 6 + B * K * in->cmax * 3 + (want_station ? B * K : 0)) * sizeof(double) + B * K * sizeof(int);
+  size_t n_wrows, n_wshift;
+  warm_counts(in, warm, &n_wrows, &n_wshift);
+  return (B * 4 + B * K * 6 + B * K * in->cmax * 3 + (want_station ? B * K : 0) + n_wrows) * sizeof(double) +
+         (B * K + n_wshift) * sizeof(int);
 }
 
 // Where the kernels find the problem-major inputs: the caller's own arrays (device memory), or a copy of them in the job
 // set's staging block, enqueued on `st` (host memory).  A small batch travels through one pinned block in one copy; a large
 // one array by array -- from pageable memory the runtime's own staged path sustains 51 GB/s on these boxes (57 from pinned
 // memory; tools/host_path_probe.cc), so nothing is gained by copying through a ring of our own first.
-int stage_inputs(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_in_buffer* ib, hipStream_t st, ProblemView* out_pv) {
+// `warm` (nullable, checked by the caller: cilqr_check_warm) is one more per-problem input and travels the same way.
+int stage_inputs(cilqr_solver* h, const cilqr_problem_batch* in, const cilqr_warm_start* warm, cilqr_in_buffer* ib, hipStream_t st,
+                 ProblemView* out_pv, WarmView* out_wv) {
   const int B = in->batch, K = in->n_knots;
   ProblemView pv;
+  WarmView wv;
+  size_t n_wrows, n_wshift;
+  warm_counts(in, warm, &n_wrows, &n_wshift);
+  if (warm != nullptr && !cilqr_warm_geometry(warm->layout, K, &wv.stride, &wv.rows_per, &wv.col)) return CILQR_ERR_ARG;
   pv.cmax_in = in->cmax;
   const size_t n_start = (size_t)B * 4, n_coarse = (size_t)B * K * 6,
                n_cor = (size_t)B * K * in->cmax * 3, n_cnt = (size_t)B * K;
@@ -160,8 +202,8 @@ int stage_inputs(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_in_buffer
   const size_t n_sta = want_station ? (size_t)B * K : 0;
   pv.station = nullptr;
   if (in->memory == CILQR_MEM_HOST) {
-    const size_t bytes = (n_start + n_coarse + n_cor + n_sta) * sizeof(double) + n_cnt * sizeof(int) + 1024;
-    const size_t payload = (n_start + n_coarse + n_cor + n_sta) * sizeof(double) + n_cnt * sizeof(int);
+    const size_t payload = (n_start + n_coarse + n_cor + n_sta + n_wrows) * sizeof(double) + (n_cnt + n_wshift) * sizeof(int);
+    const size_t bytes = payload + 1024;
     // (a small batch lands in a block of its own: it is staged by the solving thread on the solve's stream, so the next
     // small batch's copy is ordered behind this one's load kernels by the stream itself)
     const bool small = payload <= kSmallTransfer;
@@ -180,14 +222,18 @@ int stage_inputs(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_in_buffer
       std::memcpy(q, in->coarse, n_coarse * 8); q += n_coarse * 8;
       std::memcpy(q, in->corridor, n_cor * 8); q += n_cor * 8;
       if (want_station) { std::memcpy(q, in->coarse_station, n_sta * 8); q += n_sta * 8; }
-      std::memcpy(q, in->corridor_count, n_cnt * 4);
+      if (n_wrows) { std::memcpy(q, warm->rows, n_wrows * 8); q += n_wrows * 8; }
+      std::memcpy(q, in->corridor_count, n_cnt * 4); q += n_cnt * 4;
+      if (n_wshift) std::memcpy(q, warm->shift, n_wshift * 4);
       HIP_TRY(hipMemcpyAsync(d, h->in_pinned.get(), payload, hipMemcpyHostToDevice, st));
       HIP_TRY(hipEventRecord(h->in_pinned_ev.get(), st));
       pv.start = d; d += n_start;
       pv.coarse = d; d += n_coarse;
       pv.corridor = d; d += n_cor;
       if (want_station) { pv.station = d; d += n_sta; }
+      if (n_wrows) { wv.rows = d; d += n_wrows; }
       pv.ccount = reinterpret_cast<const int*>(d);
+      if (n_wshift) wv.shift = pv.ccount + n_cnt;
     } else {
       HIP_TRY(hipMemcpyAsync(d, in->start, n_start * 8, hipMemcpyHostToDevice, st));
       pv.start = d; d += n_start;
@@ -199,47 +245,66 @@ int stage_inputs(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_in_buffer
         HIP_TRY(hipMemcpyAsync(d, in->coarse_station, n_sta * 8, hipMemcpyHostToDevice, st));
         pv.station = d; d += n_sta;
       }
+      if (n_wrows) {
+        HIP_TRY(hipMemcpyAsync(d, warm->rows, n_wrows * 8, hipMemcpyHostToDevice, st));
+        wv.rows = d; d += n_wrows;
+      }
       HIP_TRY(hipMemcpyAsync(d, in->corridor_count, n_cnt * 4, hipMemcpyHostToDevice, st));
       pv.ccount = reinterpret_cast<const int*>(d);
+      if (n_wshift) {
+        int* ds = reinterpret_cast<int*>(d) + n_cnt;
+        HIP_TRY(hipMemcpyAsync(ds, warm->shift, n_wshift * 4, hipMemcpyHostToDevice, st));
+        wv.shift = ds;
+      }
     }
   } else {
     pv.start = in->start; pv.coarse = in->coarse; pv.corridor = in->corridor;
     pv.ccount = in->corridor_count;
     if (want_station) pv.station = in->coarse_station;
+    if (n_wrows) { wv.rows = warm->rows; wv.shift = warm->shift; }
   }
   *out_pv = pv;
+  *out_wv = wv;
   return CILQR_OK;
 }
 
 // inputs staged (unless `staged` says the transfer thread has done it: the caller has made `st` wait for its event) +
 // prepare kernels, on stream `st`, into the arena `*v` (whose lane geometry is filled in here)
-int load_kernels(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_job_set& js, DeviceState* v, hipStream_t st, const ProblemView& pv);
+int load_kernels(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_job_set& js, DeviceState* v, hipStream_t st, const ProblemView& pv,
+                 const WarmView& wv);
 
-int do_load(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_job_set& js, DeviceState* v, hipStream_t st,
-            const ProblemView* staged = nullptr, int staged_buf = -1) {
+// `warm`: nullable (a plain load); with it the load ends with the gather of the warm controls (launch_warm_gather)
+int do_load(cilqr_solver* h, const cilqr_problem_batch* in, const cilqr_warm_start* warm, cilqr_job_set& js, DeviceState* v,
+            hipStream_t st, const ProblemView* staged = nullptr, const WarmView* staged_warm = nullptr, int staged_buf = -1) {
   int rc = check_problem(h, in);
+  if (rc == CILQR_OK) rc = cilqr_check_warm(in, warm);
   if (rc != CILQR_OK) { release_in_buffer(h, staged_buf, st); return rc; }
   HIP_TRY(hipSetDevice(h->device));
   ProblemView pv;
+  WarmView wv;
   int buf = staged_buf;
   if (staged) {
     pv = *staged;
+    if (staged_warm) wv = *staged_warm;
   } else {
-    if (in->memory == CILQR_MEM_HOST && input_payload_bytes(h, in) > kSmallTransfer) {
+    if (in->memory == CILQR_MEM_HOST && input_payload_bytes(h, in, warm) > kSmallTransfer) {
       // (never refused: the transfer thread uploads for a solve only once every solve before it is past its load, so at
       // most one buffer is ever ahead of the solve that stages here)
       buf = acquire_in_buffer(h, false);
       if (buf < 0) return buf == -1 ? CILQR_ERR_STATE : CILQR_ERR_DEVICE;
     }
-    rc = stage_inputs(h, in, buf >= 0 ? &h->in_bufs[buf] : nullptr, st, &pv);
+    rc = stage_inputs(h, in, warm, buf >= 0 ? &h->in_bufs[buf] : nullptr, st, &pv, &wv);
   }
-  if (rc == CILQR_OK) rc = load_kernels(h, in, js, v, st, pv);
+  if (rc == CILQR_OK) rc = load_kernels(h, in, js, v, st, pv, wv);
   release_in_buffer(h, buf, st);
   return rc;
 }
 
-int load_kernels(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_job_set& js, DeviceState* v, hipStream_t st, const ProblemView& pv) {
+int load_kernels(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_job_set& js, DeviceState* v, hipStream_t st, const ProblemView& pv,
+                 const WarmView& wv) {
   const int B = in->batch;
+  // (sized once for the handle's capacity, before anything of this load is enqueued: growing frees the smaller block)
+  if (wv.rows != nullptr) HIP_TRY(js.warm_shift.grow((size_t)h->capacity * sizeof(int), &h->grown_bytes));
   const bool want_station = h->cfg.init_guess == CILQR_INIT_TRACKER && in->coarse_station != nullptr;
   h->tracker.have_station = want_station ? 1 : 0;
   // The lane tables of consecutive solves are usually the same road: their device image and the lane grid built
@@ -289,6 +354,8 @@ int load_kernels(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_job_set& 
     v->gny = (int)std::ceil(hgt / cell);
   }
   launch_load(*v, B, pv, same_lanes ? nullptr : js.lanes_raw, st);
+  // warm controls -> U of buffer 0, here because the staged rows are given back with the load (release_in_buffer)
+  if (wv.rows != nullptr) launch_warm_gather(*v, B, wv, js.warm_shift.as<int>(), st);
   HIP_TRY(hipGetLastError());
   js.lane_cache_nl = in->n_left;
   js.lane_cache_nr = in->n_right;
@@ -805,22 +872,36 @@ int64_t cilqr_device_bytes(cilqr_handle h) {
   return h->bytes + h->grown_bytes.load(std::memory_order_relaxed);   // arenas (fixed at create) + staging and tail workspaces
 }
 
-static int solve_sync(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_solution_batch* out);
+static int solve_sync(cilqr_solver* h, const cilqr_problem_batch* in, const cilqr_warm_start* warm, cilqr_solution_batch* out);
 
-int cilqr_solve_batch(cilqr_handle h, const cilqr_problem_batch* in, cilqr_solution_batch* out) {
+int cilqr_solve_batch_warm(cilqr_handle h, const cilqr_problem_batch* in, const cilqr_warm_start* warm,
+                           cilqr_solution_batch* out) {
   if (h == nullptr || out == nullptr) return CILQR_ERR_NULL;
+  if (warm != nullptr) {
+    if (in == nullptr) return CILQR_ERR_NULL;
+    const int rc = cilqr_check_warm(in, warm);
+    if (rc != CILQR_OK) return rc;
+  }
   {
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->job_count != 0) return CILQR_ERR_STATE;   // submitted solves not collected yet (cilqr_wait)
   }
-  return solve_sync(h, in, out);
+  return solve_sync(h, in, warm, out);
+}
+
+int cilqr_solve_batch(cilqr_handle h, const cilqr_problem_batch* in, cilqr_solution_batch* out) {
+  return cilqr_solve_batch_warm(h, in, nullptr, out);
 }
 
 // one synchronous solve (both stages on the handle's stream), lane groups one after the other
-static int solve_groups(cilqr_solver* h, cilqr_job& j, const cilqr_problem_batch* in, cilqr_solution_batch* out);
+static int solve_groups(cilqr_solver* h, cilqr_job& j, const cilqr_problem_batch* in, const cilqr_warm_start* warm,
+                        cilqr_solution_batch* out);
 
-static int solve_one(cilqr_solver* h, cilqr_job& j, const cilqr_problem_batch* in, cilqr_solution_batch* out) {
+static int solve_one(cilqr_solver* h, cilqr_job& j, const cilqr_problem_batch* in, const cilqr_warm_start* warm,
+                     cilqr_solution_batch* out) {
   if (in) j.in = *in; else std::memset(&j.in, 0, sizeof(j.in));
+  j.has_warm = warm != nullptr;
+  if (warm) j.warm = *warm;
   j.out = *out;
   j.upload = 0;          // staged inline, on the solve's own stream
   j.zero_inline = true;
@@ -836,7 +917,7 @@ static int solve_one(cilqr_solver* h, cilqr_job& j, const cilqr_problem_batch* i
   return rc;
 }
 
-static int solve_sync(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_solution_batch* out) {
+static int solve_sync(cilqr_solver* h, const cilqr_problem_batch* in, const cilqr_warm_start* warm, cilqr_solution_batch* out) {
   cilqr_job& j = h->jobs[0];
   j.set = 0;
   j.spec_threshold = h->spec_threshold;
@@ -844,20 +925,23 @@ static int solve_sync(cilqr_solver* h, const cilqr_problem_batch* in, cilqr_solu
   j.st1 = h->stream;
   j.st2 = h->stream;
   j.relaxed_wait = false;    // the caller's own thread waits, and the call's latency is what it is measured by (wait_event)
-  const int rc = solve_groups(h, j, in, out);
+  const int rc = solve_groups(h, j, in, warm, out);
   std::lock_guard<std::mutex> lk(h->mu);
   h->prof = j.prof;
   return rc;
 }
 
-static int solve_groups(cilqr_solver* h, cilqr_job& j, const cilqr_problem_batch* in, cilqr_solution_batch* out) {
-  if (in == nullptr || in->n_lane_groups <= 1) return solve_one(h, j, in, out);   // j.prof: published by the caller's thread
+static int solve_groups(cilqr_solver* h, cilqr_job& j, const cilqr_problem_batch* in, const cilqr_warm_start* warm,
+                        cilqr_solution_batch* out) {
+  if (in == nullptr || in->n_lane_groups <= 1) return solve_one(h, j, in, warm, out);   // j.prof: published by the caller's thread
   // problems grouped by lane table: one solve per group on contiguous sub-ranges of every array
   if (in->lane_group_start == nullptr || in->lane_group_left == nullptr || in->lane_group_right == nullptr ||
       in->left_lane == nullptr || in->right_lane == nullptr)
     return CILQR_ERR_CONSTRAINTS;
   if (in->lane_group_start[0] != 0 || in->lane_group_start[in->n_lane_groups] != in->batch) return CILQR_ERR_ARG;
   const size_t K = (size_t)in->n_knots, M1 = (size_t)h->cfg.max_iter + 1;
+  int wstride = 0, wrows = 0, wcol = 0;
+  if (warm != nullptr && !cilqr_warm_geometry(warm->layout, in->n_knots, &wstride, &wrows, &wcol)) return CILQR_ERR_ARG;
   size_t lrow = 0, rrow = 0;
   cilqr_profile acc;
   std::memset(&acc, 0, sizeof(acc));
@@ -886,7 +970,13 @@ static int solve_groups(cilqr_solver* h, cilqr_job& j, const cilqr_problem_batch
       po.iter_trajs = out->iter_trajs ? out->iter_trajs + (size_t)b0 * out->max_iter_trajs * K * CILQR_TRAJ_FIELDS : nullptr;
       po.n_iter_trajs = out->n_iter_trajs ? out->n_iter_trajs + b0 : nullptr;
       po.alpha_trace = out->alpha_trace ? out->alpha_trace + (size_t)b0 * h->cfg.max_iter : nullptr;
-      const int rc = solve_one(h, j, &pi, &po);
+      cilqr_warm_start wi;
+      if (warm != nullptr) {
+        wi = *warm;
+        wi.rows = warm->rows ? warm->rows + (size_t)b0 * wrows * wstride : nullptr;
+        wi.shift = warm->shift ? warm->shift + b0 : nullptr;
+      }
+      const int rc = solve_one(h, j, &pi, warm ? &wi : nullptr, &po);
       if (rc != CILQR_OK) return rc;
       acc.iterations += j.prof.iterations;
       acc.backward_launches += j.prof.backward_launches;
@@ -948,6 +1038,7 @@ bool host_out_is_big(const cilqr_solver* h, int B, const cilqr_solution_batch* o
 int job_begin(cilqr_solver* h, cilqr_job& j) {
   const cilqr_problem_batch* in = &j.in;
   const cilqr_solution_batch* out = &j.out;
+  const cilqr_warm_start* warm = j.has_warm ? &j.warm : nullptr;
   if (out->traj == nullptr || out->cost_hist == nullptr || out->n_cost == nullptr || out->status == nullptr)
     return CILQR_ERR_NULL;                                                     // cc:64-66
   if (out->memory != CILQR_MEM_HOST && out->memory != CILQR_MEM_DEVICE) return CILQR_ERR_ARG;
@@ -982,10 +1073,10 @@ int job_begin(cilqr_solver* h, cilqr_job& j) {
       return j.upload_rc;
     }
     HIP_TRY(hipStreamWaitEvent(st, h->in_bufs[j.in_buf].ready.get(), 0));
-    rc = do_load(h, in, js, &j.gmain, st, &j.pv, j.in_buf);
+    rc = do_load(h, in, warm, js, &j.gmain, st, &j.pv, &j.wv, j.in_buf);
     j.in_buf = -1;   // (given back behind the load kernels, whatever happened)
   } else {
-    rc = do_load(h, in, js, &j.gmain, st);
+    rc = do_load(h, in, warm, js, &j.gmain, st);
   }
   {   // (the transfer thread uploads for the next solve only now: worker_io_main)
     std::lock_guard<std::mutex> lk(h->mu);
@@ -1035,8 +1126,14 @@ int job_begin(cilqr_solver* h, cilqr_job& j) {
     }
   }
 
-  if (h->cfg.init_guess == CILQR_INIT_TRACKER) launch_init_guess_tracker(j.d, h->tracker, B, st);   // cc:168 (InitGuess)
-  else launch_init_guess(j.d, B, st);                  // cc:169
+  // the first iterate: the configured init guess, except for the problems a warm start covers (shift >= 0; without a shift
+  // array: all of them, and the init guess is not launched at all)
+  const int* warm_shift = warm ? js.warm_shift.as<int>() : nullptr;
+  if (warm == nullptr || warm->shift != nullptr) {
+    if (h->cfg.init_guess == CILQR_INIT_TRACKER) launch_init_guess_tracker(j.d, h->tracker, B, st, warm_shift);   // cc:168 (InitGuess)
+    else launch_init_guess(j.d, B, st, warm_shift);      // cc:169
+  }
+  if (warm_shift) launch_warm_rollout(j.d, B, warm_shift, st);
   launch_cost_only(j.d, nullptr, B, 0, st);            // cc:172
   launch_init_cost_commit(j.d, B, st);                 // cc:170,173
   if (j.o_it) launch_export_iter_traj(j.d, nullptr, B, j.o_it, out->max_iter_trajs, st);
@@ -1401,7 +1498,8 @@ void worker1_main(cilqr_solver* h) {
       j.st2 = j.st1;
       cilqr_problem_batch in = j.in;
       cilqr_solution_batch out = j.out;
-      rc = solve_groups(h, j, &in, &out);
+      const cilqr_warm_start warm = j.warm;
+      rc = solve_groups(h, j, &in, j.has_warm ? &warm : nullptr, &out);
     } else {
       rc = job_begin(h, j);
       if (rc == CILQR_OK) rc = job_iterate(h, j, 1);
@@ -1484,7 +1582,9 @@ void worker_io_main(cilqr_solver* h) {
     lk.unlock();
     int rc = CILQR_OK;
     if (upload) {
+      const cilqr_warm_start* warm = j.has_warm ? &j.warm : nullptr;
       rc = check_problem(h, &j.in);
+      if (rc == CILQR_OK) rc = cilqr_check_warm(&j.in, warm);
       if (rc == CILQR_OK) rc = io_streams(h);
       int buf = -1;
       if (rc == CILQR_OK) {
@@ -1492,7 +1592,7 @@ void worker_io_main(cilqr_solver* h) {
         if (buf < 0) rc = CILQR_ERR_DEVICE;
       }
       hipStream_t si = h->stream_in.get();
-      if (rc == CILQR_OK) rc = stage_inputs(h, &j.in, &h->in_bufs[buf], si, &j.pv);
+      if (rc == CILQR_OK) rc = stage_inputs(h, &j.in, warm, &h->in_bufs[buf], si, &j.pv, &j.wv);
       if (rc == CILQR_OK && hipEventRecord(h->in_bufs[buf].ready.get(), si) != hipSuccess) rc = CILQR_ERR_DEVICE;
       if (rc != CILQR_OK && buf >= 0) {   // nothing will read it
         (void)hipStreamSynchronize(si);
@@ -1520,7 +1620,12 @@ void worker_io_main(cilqr_solver* h) {
 extern "C" {
 
 int cilqr_submit(cilqr_handle h, const cilqr_problem_batch* in, cilqr_solution_batch* out) {
+  return cilqr_submit_warm(h, in, nullptr, out);
+}
+
+int cilqr_submit_warm(cilqr_handle h, const cilqr_problem_batch* in, const cilqr_warm_start* warm, cilqr_solution_batch* out) {
   if (h == nullptr || in == nullptr || out == nullptr) return CILQR_ERR_NULL;
+  if (const int rc = cilqr_check_warm(in, warm)) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   if (h->job_count >= kJobRing) return CILQR_ERR_STATE;   // two in flight and one queued: collect the oldest first (cilqr_wait)
   if (!h->workers_started) {
@@ -1533,6 +1638,8 @@ int cilqr_submit(cilqr_handle h, const cilqr_problem_batch* in, cilqr_solution_b
   cilqr_job& j = h->jobs[slot];
   j.in = *in;
   j.out = *out;
+  j.has_warm = warm != nullptr;
+  if (warm) j.warm = *warm;
   j.set = 0;            // taken when the first stage starts (worker1_main)
   j.in_buf = -1;
   j.past_load = false;
@@ -1544,7 +1651,7 @@ int cilqr_submit(cilqr_handle h, const cilqr_problem_batch* in, cilqr_solution_b
   // host arrays of a large batch: the transfer thread starts on them now (worker_io_main)
   const bool plain = in->n_lane_groups <= 1 && in->batch > 0 && in->batch <= h->capacity;
   j.upload = (plain && in->memory == CILQR_MEM_HOST && check_problem(h, in) == CILQR_OK &&
-              input_payload_bytes(h, in) > kSmallTransfer) ? 1 : 0;
+              input_payload_bytes(h, in, warm) > kSmallTransfer) ? 1 : 0;
   j.zero_by_io = plain && out->cost_hist != nullptr && host_out_is_big(h, in->batch, out);
   j.zero_inline = !j.zero_by_io;
   j.io_busy = j.upload == 1 || j.zero_by_io;
@@ -1576,17 +1683,26 @@ int cilqr_wait(cilqr_handle h) {
 // ------------------------------------------------------------------------------------------
 // stages
 // ------------------------------------------------------------------------------------------
-int cilqr_stage_load(cilqr_handle h, const cilqr_problem_batch* in) {
+int cilqr_stage_load(cilqr_handle h, const cilqr_problem_batch* in) { return cilqr_stage_load_warm(h, in, nullptr); }
+
+int cilqr_stage_load_warm(cilqr_handle h, const cilqr_problem_batch* in, const cilqr_warm_start* warm) {
   if (h == nullptr) return CILQR_ERR_NULL;
+  if (warm != nullptr) {
+    if (in == nullptr) return CILQR_ERR_NULL;
+    if (const int rc = cilqr_check_warm(in, warm)) return rc;
+  }
   {
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->job_count != 0) return CILQR_ERR_STATE;   // the main arena belongs to the submitted solves
   }
   h->stage = 0;
-  const int rc = do_load(h, in, h->sets[0], &h->ds, h->stream);
+  h->stage_warm = false;
+  const int rc = do_load(h, in, warm, h->sets[0], &h->ds, h->stream);
   if (rc != CILQR_OK) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   h->B = in->batch;
+  h->stage_warm = warm != nullptr;
+  h->stage_warm_all = warm != nullptr && warm->shift == nullptr;
   h->stage = 1;
   return CILQR_OK;
 }
@@ -1595,8 +1711,12 @@ int cilqr_stage_init_guess(cilqr_handle h) {
   if (h == nullptr) return CILQR_ERR_NULL;
   if (!(h->stage & 1)) return CILQR_ERR_STATE;
   HIP_TRY(hipSetDevice(h->device));
-  if (h->cfg.init_guess == CILQR_INIT_TRACKER) launch_init_guess_tracker(h->ds, h->tracker, h->B, h->stream);
-  else launch_init_guess(h->ds, h->B, h->stream);
+  const int* warm_shift = h->stage_warm ? h->sets[0].warm_shift.as<int>() : nullptr;   // (as job_begin)
+  if (!h->stage_warm_all) {
+    if (h->cfg.init_guess == CILQR_INIT_TRACKER) launch_init_guess_tracker(h->ds, h->tracker, h->B, h->stream, warm_shift);
+    else launch_init_guess(h->ds, h->B, h->stream, warm_shift);
+  }
+  if (warm_shift) launch_warm_rollout(h->ds, h->B, warm_shift, h->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   h->stage = 1 | 2;

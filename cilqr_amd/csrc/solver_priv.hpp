@@ -66,6 +66,9 @@ struct cilqr_job_set {
   std::vector<cilqr::hip_event> ev;       // profiling
   cilqr::hip_event handoff;         // survivors copied into the finishing arena (recorded on the first stage's stream)
   cilqr::hip_event sync_ev;         // what a relaxed host wait for a whole stream polls (solver.hip: wait_stream)
+  // warm start: int [B], the shift of every problem of the load in force (0 where the caller gave no array), written by the
+  // gather kernel for the init-guess launches behind it -- the caller's own array, staged, is given back with the load
+  cilqr::dev_mem warm_shift;
 };
 
 struct cilqr_timer {  // event pairs around kernels / phases, resolved after the final sync
@@ -107,6 +110,8 @@ constexpr int kJobRing = 3;
 struct cilqr_job {
   cilqr_problem_batch in;
   cilqr_solution_batch out;
+  cilqr_warm_start warm;    // has_warm only: the warm start of this solve (cilqr_submit_warm; copied like `in`)
+  bool has_warm = false;
   int set = 0;              // the cilqr_job_set it runs on: taken when its first stage starts, given back when it is done
   int spec_threshold = 0;   // the threshold of this solve (cilqr_solver::spec_threshold or spec_threshold_submit)
   int tail_threshold = 0;   // likewise (cilqr_solver::tail_threshold or tail_threshold_submit)
@@ -140,6 +145,7 @@ struct cilqr_job {
   int upload = 0;
   int upload_rc = CILQR_OK;
   cilqr::ProblemView pv;      // where the staged inputs lie (filled by whoever staged them)
+  cilqr::WarmView wv;         // ... and the warm rows (rows == nullptr: none)
   bool past_load = false;     // its inputs are staged and its load kernels enqueued (or it failed before): the transfer thread may
                               // upload for the solve behind it
   int in_buf = -1;            // the cilqr_in_buffer they lie in (-1: the caller's own device arrays)
@@ -184,6 +190,8 @@ struct cilqr_solver {
   double* lambda_stage = nullptr;
   int B = 0;               // problems loaded
   int stage = 0;           // bit0 loaded, bit1 iterate, bit2 quadratized, bit3 gains
+  bool stage_warm_all = false;   // ... without a shift array: every problem is warm-started, the init guess is not launched
+  bool stage_warm = false; // the load in force was cilqr_stage_load_warm with a warm start: sets[0].warm_shift is current
   int spec_threshold = 8192;  // active sets up to this size evaluate all 11 step sizes at once (cilqr_solve_batch)
   // ... and for solves submitted with cilqr_submit: other solves share the GPU then, and eleven candidates per problem
   // where two or three would do is throughput taken from them (measured: pool of two 1.90 -> 1.98 M solves/s, one handle
@@ -248,6 +256,11 @@ namespace cilqr {
 constexpr int kWaitSpinUs = 20;
 int wait_event(hipEvent_t ev, bool relaxed, int spin_us = kWaitSpinUs);
 }  // namespace cilqr
+
+// The argument checks of a warm start against its problem batch (solver.hip; `in` not NULL): CILQR_OK for warm == NULL.
+int cilqr_check_warm(const cilqr_problem_batch* in, const cilqr_warm_start* warm);
+// doubles per row, rows per problem and first control column of a warm layout (n_knots = N + 1); false: no such layout
+bool cilqr_warm_geometry(int32_t layout, int32_t n_knots, int* stride, int* rows_per, int* col);
 
 // cilqr_dp_plan_batch (planner_batch.hip); times_out (HOST, [n_knots], optional): the time column every planned scene gets
 int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes, const double* start3,

@@ -191,13 +191,26 @@ struct ProblemView {  // device pointers to the problem-major inputs
   int cmax_in;
 };
 
+// Warm start (cilqr_warm_start, include/cilqr.h): where the caller's control rows lie on the device.  rows == nullptr: none.
+struct WarmView {
+  const double* rows = nullptr;   // [B][rows_per][stride], the controls of a row at columns col, col + 1
+  const int* shift = nullptr;     // [B] or nullptr (0 for every problem)
+  int rows_per = 0, stride = 0, col = 0;
+};
+
 void launch_load(const DeviceState& s, int B, const ProblemView& in, const double* lanes_raw,
                  hipStream_t st);
+// kernels_warm.hip.  Gather: the shift rule applied to the caller's rows -> U of buffer 0 for the problems with shift >= 0,
+// and shift_out [B] = the shift of every problem (0 where the caller gave none) for the two launches that follow it:
+// launch_warm_rollout rolls those problems out from goals[0]; the init-guess launchers skip them (`warm_shift`, nullable).
+void launch_warm_gather(const DeviceState& s, int B, const WarmView& w, int* shift_out, hipStream_t st);
+void launch_warm_rollout(const DeviceState& s, int B, const int* warm_shift, hipStream_t st);
 void launch_build_lane_grid(const DeviceState& s, hipStream_t st);
 void launch_nearest_lane(const DeviceState& s, int n, const double* xy, int* left, int* right, int use_grid,
                          hipStream_t st);
-void launch_init_guess(const DeviceState& s, int B, hipStream_t st);
-void launch_init_guess_tracker(const DeviceState& s, const TrackerParams& tp, int B, hipStream_t st);
+void launch_init_guess(const DeviceState& s, int B, hipStream_t st, const int* warm_shift = nullptr);
+void launch_init_guess_tracker(const DeviceState& s, const TrackerParams& tp, int B, hipStream_t st,
+                               const int* warm_shift = nullptr);
 void launch_set_trajectory(const DeviceState& s, int B, const double* X, const double* U, hipStream_t st);
 // cost of buffer (cur ^ cand) for the n listed slots -> trial[], no accept logic
 void launch_cost_only(const DeviceState& s, const int* list, int n, int cand, hipStream_t st);

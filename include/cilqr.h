@@ -248,6 +248,41 @@ int64_t cilqr_device_bytes(cilqr_handle h);
 
 int cilqr_solve_batch(cilqr_handle h, const cilqr_problem_batch* in, cilqr_solution_batch* out);
 
+/* ---- warm start: the first iterate from control sequences the caller already has ----
+ * Every solve above starts from the handle's configured init guess, built from the coarse trajectory alone.  The batches
+ * of a stream are rarely unrelated (the same scenes with new obstacle predictions, variants of one scene around a nominal
+ * solution), and the previous solution lies in device memory in the layout of cilqr_solution_batch::traj.  A warm start
+ * hands its controls to the solver.  For problem b with s = shift[b] (a NULL shift array: 0 for every problem):
+ *   s <  0   the problem is not warm-started: it takes the handle's configured init guess, and all its outputs are
+ *            bit-identical to the same batch solved without a warm start;
+ *   s >= 0   for every step i < N, with r = i + s:  U_i = the two control columns of row r of the problem's warm rows if
+ *            r < N (the bits are copied: not clamped, not angle-wrapped), U_i = (0, 0) otherwise (s >= N is compared
+ *            before anything is added: s = 2^31 - 1 is valid and gives all zeros);
+ *            X_0 = goals_[0] = (start.x, start.y, start.theta, start.v, 0, 0), X_{i+1} = Dynamics(X_i, U_i) with the
+ *            arithmetic of cilqr_open_loop_rollout, bit for bit.
+ * From there Optimize() runs unchanged: iter_trajs[0] is this pair and cost row 0 its TotalCost.  Knot 0 stays goals_[0]
+ * with a = delta = 0, because Forward restarts every rollout there (cc:392-415); `shift` only spares a caller who has
+ * advanced the problems in time the repacking of the controls.  Non-finite warm rows are no error: the arithmetic decides,
+ * and every other problem of the batch is unaffected.  Any shift value is valid.
+ *   layout   CILQR_ROWS_TRAJ      rows [B][K][CILQR_TRAJ_FIELDS], controls in columns 8 and 9
+ *            CILQR_ROWS_PLAN      rows [B][K][CILQR_PLAN_FIELDS], controls in columns 9 and 10
+ *            CILQR_ROWS_CONTROLS  rows [B][N][2]
+ * (K rows per problem are addressed, the first N are read; no alignment beyond that of a double is assumed.)
+ * With warm == NULL every call below is exactly its plain counterpart.  Checked before anything is launched, the handle
+ * staying usable: CILQR_ERR_NULL for NULL rows; CILQR_ERR_ARG for an unknown layout or CILQR_ROWS_COARSE (which carries
+ * no controls), and for a `memory` that is not a CILQR_MEM_* value or differs from in->memory.  The arrays of a submitted
+ * solve must stay valid until its wait, like the other inputs.  cilqr_stage_load_warm arms cilqr_stage_init_guess, which then
+ * produces this first iterate (readable as CILQR_T_X / CILQR_T_U). */
+#define CILQR_ROWS_CONTROLS 3   /* [N][2] jerk, delta_rate (beside CILQR_ROWS_TRAJ / _PLAN / _COARSE below) */
+typedef struct cilqr_warm_start {
+  int32_t memory;        /* CILQR_MEM_*; must equal in->memory */
+  int32_t layout;        /* CILQR_ROWS_TRAJ, CILQR_ROWS_PLAN or CILQR_ROWS_CONTROLS */
+  const double*  rows;   /* [B][K][10] | [B][K][11] | [B][N][2] */
+  const int32_t* shift;  /* [B], optional (NULL: 0 for all); < 0: cold */
+} cilqr_warm_start;
+int cilqr_solve_batch_warm(cilqr_handle h, const cilqr_problem_batch* in, const cilqr_warm_start* warm,
+                           cilqr_solution_batch* out);
+
 /* TrackerConfig / LateralTrackerConfig / LongitudinalTrackerConfig (algorithm/params/planner_config.h:18-43) for
  * CILQR_INIT_TRACKER; cilqr_create starts from the reference's defaults. */
 typedef struct cilqr_tracker_config {
@@ -290,10 +325,15 @@ int cilqr_set_tracker_config(cilqr_handle h, const cilqr_tracker_config* cfg);
 int cilqr_submit(cilqr_handle h, const cilqr_problem_batch* in, cilqr_solution_batch* out);
 int cilqr_wait(cilqr_handle h);
 
+/* cilqr_submit with a warm start (see cilqr_solve_batch_warm) */
+int cilqr_submit_warm(cilqr_handle h, const cilqr_problem_batch* in, const cilqr_warm_start* warm, cilqr_solution_batch* out);
+
 /* ---- stage entry points (operate on the handle's device state, whole batch) ----
  * A cilqr_solve_batch / cilqr_submit on the same handle invalidates the staged state: call
  * cilqr_stage_load again afterwards (CILQR_ERR_STATE otherwise). */
 int cilqr_stage_load(cilqr_handle h, const cilqr_problem_batch* in);
+/* the load of a warm-started solve: the cilqr_stage_init_guess that follows produces the warm first iterate */
+int cilqr_stage_load_warm(cilqr_handle h, const cilqr_problem_batch* in, const cilqr_warm_start* warm);
 int cilqr_stage_init_guess(cilqr_handle h);
 /* overwrite the current iterate: X [B][K][6], U [B][N][2] */
 int cilqr_stage_set_trajectory(cilqr_handle h, const double* X, const double* U, int32_t memory);
@@ -600,6 +640,9 @@ int cilqr_multi_create(const cilqr_config* cfg, const int32_t* devices, int32_t 
                        int32_t cmax, int32_t max_lane_segments, cilqr_multi_handle* out);
 int cilqr_multi_destroy(cilqr_multi_handle m);
 int cilqr_multi_solve(cilqr_multi_handle m, const cilqr_problem_batch* in, cilqr_solution_batch* out);
+/* ... with a warm start (see cilqr_solve_batch_warm); its arrays are cut into the same shards */
+int cilqr_multi_solve_warm(cilqr_multi_handle m, const cilqr_problem_batch* in, const cilqr_warm_start* warm,
+                           cilqr_solution_batch* out);
 /* cilqr_set_option on every shard */
 int cilqr_multi_set_option(cilqr_multi_handle m, int32_t option, int64_t value);
 /* the split of a batch: first problem and device of every shard (arrays of max_shards entries, NULL to skip);
@@ -626,6 +669,8 @@ int cilqr_pool_create(const cilqr_config* cfg, int32_t device, int32_t n_handles
                       int32_t max_lane_segments, cilqr_pool_handle* out);
 int cilqr_pool_destroy(cilqr_pool_handle p);
 int cilqr_pool_submit(cilqr_pool_handle p, const cilqr_problem_batch* in, cilqr_solution_batch* out);
+int cilqr_pool_submit_warm(cilqr_pool_handle p, const cilqr_problem_batch* in, const cilqr_warm_start* warm,
+                           cilqr_solution_batch* out);   /* see cilqr_solve_batch_warm */
 int cilqr_pool_wait(cilqr_pool_handle p);
 int32_t cilqr_pool_depth(cilqr_pool_handle p);   /* 3 x n_handles */
 /* handle k (0 <= k < n_handles) for what the pool has no call of its own for -- cilqr_set_profiling, cilqr_set_stream, a

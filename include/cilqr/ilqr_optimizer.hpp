@@ -34,6 +34,9 @@
 //   * iter_trajs is appended to (init guess + accepted non-final iterates, cc:170,294), cost()
 //     is cleared per Plan (cc:62).
 //   * One handle per optimizer, sized for one problem; not re-entrant, like the reference.
+//
+// Not in the reference: WarmStart(previous, shift) hands the NEXT Plan the controls of an earlier trajectory as its first
+// iterate (cilqr_solve_batch_warm, include/cilqr.h) instead of the init guess; that Plan clears it again.
 #ifndef CILQR_ILQR_OPTIMIZER_HPP_
 #define CILQR_ILQR_OPTIMIZER_HPP_
 
@@ -112,6 +115,8 @@ class IlqrOptimizerT {
             const LaneConstraints& right_lane_cons, DiscretizedTrajectory* const opt_trajectory,
             std::vector<DiscretizedTrajectory>* const iter_trajs) {
     cost_.clear();
+    const bool warm_armed = warm_armed_;
+    warm_armed_ = false;   // armed for one Plan, whatever becomes of it
     if (opt_trajectory == nullptr || iter_trajs == nullptr) return false;          // cc:64-66
     if (corridor.size() == 0 || left_lane_cons.size() == 0 || right_lane_cons.size() == 0) {
       std::fprintf(stderr, "ilqr input constraints error\n");                      // cc:68-73
@@ -168,6 +173,7 @@ class IlqrOptimizerT {
     in.lane_group_start = nullptr;
     in.lane_group_left = nullptr;
     in.lane_group_right = nullptr;
+    in.coarse_station = nullptr;
 
     const int max_it = cfg_.max_iter + 1;
     // result buffers live with the object: 0.8 MB of iterates need not be allocated and cleared per call
@@ -190,7 +196,13 @@ class IlqrOptimizerT {
     out.n_iter_trajs = &n_it;
     out.alpha_trace = nullptr;
     const auto t_call = std::chrono::steady_clock::now();
-    const int rc = cilqr_solve_batch(handle_, &in, &out);
+    cilqr_warm_start warm;
+    warm.memory = CILQR_MEM_HOST;
+    warm.layout = CILQR_ROWS_CONTROLS;   // the first N of the K (jerk, delta_rate) pairs are read
+    warm.rows = warm_controls_.data();
+    warm.shift = &warm_shift_;
+    const bool use_warm = warm_armed && warm_controls_.size() == static_cast<size_t>(K) * 2;
+    const int rc = cilqr_solve_batch_warm(handle_, &in, use_warm ? &warm : nullptr, &out);
     const auto t_back = std::chrono::steady_clock::now();
     if (rc != CILQR_OK) {
       std::fprintf(stderr, "cilqr_solve_batch failed: %s\n", cilqr_error_string(rc));
@@ -216,6 +228,21 @@ class IlqrOptimizerT {
   }
 
   std::vector<Cost> cost() { return cost_; }            // ilqr_optimizer.h:50-52
+
+  // not in the reference: the next Plan -- and only that one -- starts from the controls of `previous`, step i taking those
+  // of its point i + shift ((0, 0) past the end; cilqr_warm_start in include/cilqr.h), rolled out from the start state.
+  // A negative shift disarms.  A `previous` with another knot count than the Plan's is ignored there (a cold start).
+  void WarmStart(const DiscretizedTrajectory& previous, int shift = 0) {
+    warm_controls_.clear();
+    warm_armed_ = false;
+    if (shift < 0) return;
+    for (const auto& pt : previous.trajectory()) {
+      warm_controls_.push_back(pt.jerk);
+      warm_controls_.push_back(pt.delta_rate);
+    }
+    warm_shift_ = shift;
+    warm_armed_ = true;
+  }
 
   // not in the reference: CILQR_ST_* of the last Plan
   int status() const { return status_; }
@@ -291,6 +318,9 @@ class IlqrOptimizerT {
     configured_ = o.configured_;
     cost_ = o.cost_;
     status_ = o.status_;
+    warm_controls_ = o.warm_controls_;
+    warm_shift_ = o.warm_shift_;
+    warm_armed_ = o.warm_armed_;
     handle_ = nullptr;   // device state is re-created lazily
     cmax_ = smax_ = 0;
   }
@@ -303,6 +333,9 @@ class IlqrOptimizerT {
   int status_ = 0;
   std::vector<Cost> cost_;
   std::vector<double> traj_buf_, hist_buf_, iters_buf_;
+  std::vector<double> warm_controls_;   // [K][2] jerk, delta_rate of the trajectory given to WarmStart
+  int32_t warm_shift_ = 0;
+  bool warm_armed_ = false;
   PlanTiming timing_;
 };
 
