@@ -126,6 +126,8 @@ ROWS_POSE_COLUMNS = {ROWS_TRAJ: (0, 1, 2, 3), ROWS_PLAN: (0, 2, 3, 4), ROWS_COAR
 HIT_REAR_STATIC, HIT_REAR_BARRIER, HIT_REAR_DYNAMIC = 1, 2, 4
 HIT_FRONT_STATIC, HIT_FRONT_BARRIER, HIT_FRONT_DYNAMIC = 8, 16, 32
 HIT_BITS = (HIT_REAR_STATIC, HIT_REAR_BARRIER, HIT_REAR_DYNAMIC, HIT_FRONT_STATIC, HIT_FRONT_BARRIER, HIT_FRONT_DYNAMIC)
+# cilqr_resample_rows / cilqr_resample_rows_batch: the key column of a query (CILQR_KEY_*)
+KEY_TIME, KEY_STATION = 0, 1
 
 
 class TrackerConfig(C.Structure):
@@ -157,7 +159,7 @@ EXPORTS = [
     "cilqr_stage_read", "cilqr_stage_nearest_lane", "cilqr_open_loop_rollout", "cilqr_error_string",
     "cilqr_default_corridor_config", "cilqr_build_corridors", "cilqr_lane_constraints",
     "cilqr_default_dp_config", "cilqr_dp_plan", "cilqr_dp_plan_batch", "cilqr_scene_points_batch", "cilqr_plan_scenes_batch",
-    "cilqr_check_collisions", "cilqr_check_collisions_batch",
+    "cilqr_check_collisions", "cilqr_check_collisions_batch", "cilqr_resample_rows", "cilqr_resample_rows_batch",
     "cilqr_road_barriers", "cilqr_default_tracker_config",
     "cilqr_set_tracker_config",
     "cilqr_solve_batch_warm", "cilqr_submit_warm", "cilqr_stage_load_warm", "cilqr_pool_submit_warm", "cilqr_multi_solve_warm",
@@ -241,6 +243,9 @@ def lib():
         L.cilqr_check_collisions_batch.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(SceneBatchStruct), C.c_int32,
                                                    C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.POINTER(C.c_int32)]
+        L.cilqr_resample_rows.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.cilqr_resample_rows_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                                C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
         L.cilqr_default_tracker_config.argtypes = [C.POINTER(TrackerConfig)]
         L.cilqr_default_tracker_config.restype = None
         L.cilqr_set_tracker_config.argtypes = [C.c_void_p, C.POINTER(TrackerConfig)]
@@ -770,6 +775,44 @@ class BatchIlqrOptimizer:
                                                  n_hit_ptr, C.byref(n))
         return rc, int(n.value)
 
+    def resample(self, rows, layout: int, queries, key: int = KEY_TIME):
+        """DiscretizedTrajectory::EvaluateTime / EvaluateStation for a batch of trajectories on the GPU
+        (cilqr_resample_rows_batch).  rows [B,K,F] in `layout` (ROWS_TRAJ / ROWS_PLAN / ROWS_COARSE); queries [M] -- one axis
+        for the whole batch -- or [B,M], one per problem; key = KEY_TIME or KEY_STATION.  NumPy arrays, or contiguous float64
+        device tensors (both of the same kind); the result [B,M,F] is of that kind."""
+        on_device = _is_device_tensor(rows)
+        if on_device != _is_device_tensor(queries):
+            raise ValueError("rows and queries must both be NumPy arrays or both device tensors")
+        if on_device:
+            for t in (rows, queries):
+                if not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64":
+                    raise ValueError("rows / queries on the device: contiguous float64 tensors")
+        else:
+            rows, queries = _f64(rows), _f64(queries)
+        if rows.ndim != 3 or rows.shape[2] != ROWS_FIELDS.get(layout, rows.shape[2]):
+            raise ValueError(f"rows must be [B, K, {ROWS_FIELDS.get(layout)}]")
+        B, K, F = (int(v) for v in rows.shape)
+        if queries.ndim not in (1, 2) or (queries.ndim == 2 and queries.shape[0] != B):
+            raise ValueError(f"queries must be [M] or [{B}, M]")
+        M = int(queries.shape[-1])
+        if on_device:
+            import torch
+            out = torch.empty((B, M, F), dtype=torch.float64, device=rows.device)
+            ptrs = (rows.data_ptr(), queries.data_ptr(), out.data_ptr())
+        else:
+            out = np.empty((B, M, F))
+            ptrs = (rows.ctypes.data, queries.ctypes.data, out.ctypes.data)
+        rc = self.resample_raw(B, layout, ptrs[0], K, key, ptrs[1], M, queries.ndim == 2, ptrs[2],
+                               MEM_DEVICE if on_device else MEM_HOST)
+        self._chk(rc, "resample")
+        return out
+
+    def resample_raw(self, batch, layout, rows_ptr, n_knots, key, queries_ptr, n_queries, per_problem, out_ptr, memory) -> int:
+        """Pointer-level form (rows / queries / out in device or host memory as `memory` says: resampled plan rows feed
+        check_collisions_raw where they lie); returns the code."""
+        return self.L.cilqr_resample_rows_batch(self.h, batch, layout, rows_ptr, n_knots, key, queries_ptr, n_queries,
+                                                int(per_problem), out_ptr, memory)
+
     def open_loop_rollout(self, x0, U):
         x0, U = _f64(x0), _f64(U)
         B = x0.shape[0]
@@ -834,6 +877,20 @@ def check_collisions(flat: dict, rows, layout: int, cfg: "DpConfig | None" = Non
     if rc != OK:
         raise CilqrError(rc, "in cilqr_check_collisions")
     return mask, int(first.value), int(n_hit.value)
+
+
+def resample_rows(rows, layout: int, queries, key: int = KEY_TIME) -> np.ndarray:
+    """DiscretizedTrajectory::EvaluateTime / EvaluateStation for one trajectory through the C-ABI (cilqr_resample_rows, host
+    only): rows [K,F] in `layout` (ROWS_*), queries [M], key = KEY_TIME or KEY_STATION -> [M,F]."""
+    rows, queries = _f64(rows), _f64(queries).ravel()
+    if rows.ndim != 2 or rows.shape[1] != ROWS_FIELDS.get(layout, rows.shape[1]):
+        raise ValueError(f"rows must be [K, {ROWS_FIELDS.get(layout)}]")
+    out = np.empty((len(queries), rows.shape[1]))
+    rc = lib().cilqr_resample_rows(layout, rows.ctypes.data, rows.shape[0], key, queries.ctypes.data, len(queries),
+                                   out.ctypes.data)
+    if rc != OK:
+        raise CilqrError(rc, "in cilqr_resample_rows")
+    return out
 
 
 _SCENE_BATCH_ARRAYS = ("static_points", "static_counts", "dynamic_polygon_points", "dynamic_polygon_counts",

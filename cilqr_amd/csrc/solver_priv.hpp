@@ -248,6 +248,8 @@ struct cilqr_solver {
   // count of colliding scenes on its way back, the staging of HOST scenes and rows, of HOST masks and counts
   cilqr::pinned_mem cc_tab_host;
   cilqr::dev_mem cc_tab, cc_in, cc_out;
+  // cilqr_resample_rows_batch (resample_batch.hip), grown likewise: the staging of HOST rows and queries, of HOST output rows
+  cilqr::dev_mem rs_in, rs_out;
 };
 
 namespace cilqr {

@@ -29,6 +29,9 @@
  *                           (algorithm/utils/environment.cpp:133-182) at every knot's time, B scenes per call on the GPU
  *   cilqr_plan_scenes_batch   TrajectoryPlanner::Plan (algorithm/planner/trajectory_planner.cpp:28-162) for B scenes:
  *                           DP -> obstacle points -> corridors -> lane constraints -> solve -> result rows
+ *   cilqr_resample_rows     DiscretizedTrajectory::EvaluateTime / EvaluateStation (algorithm/utils/discretized_trajectory.cpp:50-136,
+ *                           math::slerp math_utils.h:208-225) for a list of queries, one trajectory on the host;
+ *                           cilqr_resample_rows_batch: B trajectories per call on the GPU
  *
  * Layout convention: every per-problem array is problem-major ("[B][...]"), IEEE fp64,
  * in host or device memory as flagged by `memory`.
@@ -596,6 +599,55 @@ int cilqr_scene_points_batch(cilqr_handle h, const cilqr_scene_batch* scenes, in
 int cilqr_check_collisions_batch(cilqr_handle h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes,
                                  int32_t layout, const double* rows, int32_t n_knots, double collision_buffer,
                                  uint8_t* mask, int32_t* first_hit, int32_t* n_hit, int32_t* n_colliding);
+
+/* ---- resample: trajectory rows on another time or station axis (DiscretizedTrajectory::EvaluateTime / EvaluateStation,
+ * algorithm/utils/discretized_trajectory.cpp:50-136; math::slerp, math_utils.h:208-225); one trajectory on the host ----
+ * What the solver and the planners return are knot rows, delta_t apart; the reference's consumers read its result through
+ * these two queries.  One trajectory is K >= 2 rows in one of the CILQR_ROWS_TRAJ / _PLAN / _COARSE layouts; `key` is its
+ * time column (CILQR_KEY_TIME) or its station column (CILQR_KEY_STATION: _PLAN and _COARSE only, _TRAJ has none).  Keys are
+ * taken as non-decreasing.  For a query q:
+ *   bracket   (QueryLowerBound{Time,Station}Point, then Evaluate*)  if q >= key[K-1]: i = K-1; else if q < key[0]: i = 0;
+ *             else i = std::lower_bound's halving written out,
+ *                 first = 0, len = K;  while (len > 0) { half = len >> 1;
+ *                     if (key[first + half] < q) { first += half + 1; len -= half + 1; } else len = half; }   i = first
+ *             -- defined for any input, sorted or not.  If i == 0, i = 1.  p0 = row i-1, p1 = row i.  Outside the key
+ *             range this extrapolates, as the reference does; a NaN query ends at i = 1 and the arithmetic decides.
+ *   degenerate pair   |key1 - key0| < 1e-10 (strict; kMathEpsilon): the output row is p0 copied as bits, its key column
+ *             included.
+ *   otherwise w = (q - key0) / (key1 - key0), every operation rounded once (no fused multiply-add), and
+ *             the key column      q itself;
+ *             theta               slerp(p0.theta, key0, p1.theta, key1, q) with the reference's NormalizeAngle (slerp's own
+ *                                 `<=` against 1e-10 stays as written);
+ *             jerk, delta_rate    (where the layout has them) p0's bits: a control holds over its step;
+ *             every other column  (1 - w) * p0 + w * p1 -- a and delta included, which the reference leaves at their
+ *                                 default 0 and which are linear over a step in this model.
+ * The output row has the layout of the input rows.  Non-finite rows and queries are no error: the arithmetic decides (a
+ * result that is a NaN is a NaN in either call; which NaN is not part of the rule), the other queries are unaffected.
+ *   rows [n_knots][fields], queries [n_queries], out [n_queries][fields]; HOST memory; no handle
+ * CILQR_ERR_NULL; CILQR_ERR_ARG for n_knots < 2, n_queries < 1, an unknown layout or key, CILQR_KEY_STATION with
+ * CILQR_ROWS_TRAJ, out == rows; CILQR_ERR_CAPACITY for n_knots > CILQR_DP_MAX_KNOTS.  C++ callers use
+ * include/cilqr/trajectory_queries.hpp directly. */
+#define CILQR_KEY_TIME 0
+#define CILQR_KEY_STATION 1
+int cilqr_resample_rows(int32_t layout, const double* rows, int32_t n_knots, int32_t key,
+                        const double* queries, int32_t n_queries, double* out);
+/* ---- the same for B trajectories per call, on the GPU (kernels_resample.hip; ABI 7) ----
+ *   rows    [B][n_knots][fields]
+ *   queries [n_queries], one axis for the whole batch (per_problem = 0), or [B][n_queries] (per_problem = 1)
+ *   out     [B][n_queries][fields]
+ * all three in `memory`; nothing beyond the alignment of a double is assumed.  Every element of `out` is the host call's
+ * bit for bit (the kernel is built without contraction and wraps angles with the routine of cilqr_device_math fn 6).  Rows
+ * resampled in CILQR_ROWS_PLAN layout feed cilqr_check_collisions_batch where they lie (up to CILQR_DP_MAX_KNOTS of them:
+ * 51 knots at five times the rate are 251), and the next cycle's start state is the previous plan at the cycle time.
+ * Runs on the handle's stream and waits for that stream only; DEVICE arrays need no work space, HOST arrays are staged in
+ * blocks that belong to the handle and grow to the largest call.  Checked before anything is launched, the handle staying
+ * usable: CILQR_ERR_NULL; CILQR_ERR_ARG for batch < 1, n_knots < 2, n_queries < 1, an unknown layout, key or memory flag,
+ * CILQR_KEY_STATION with CILQR_ROWS_TRAJ, per_problem not 0 or 1, out == rows; CILQR_ERR_CAPACITY for n_knots >
+ * CILQR_DP_MAX_KNOTS (n_queries has no limit beyond int32: sizes are computed in size_t); CILQR_ERR_STATE while solves are
+ * submitted on the handle. */
+int cilqr_resample_rows_batch(cilqr_handle h, int32_t batch, int32_t layout, const double* rows, int32_t n_knots,
+                              int32_t key, const double* queries, int32_t n_queries, int32_t per_problem,
+                              double* out, int32_t memory);
 
 /* ---- TrajectoryPlanner::Plan for B scenes per call (trajectory_planner.cpp:28-162) ----
  * scene batch -> cilqr_dp_plan_batch -> cilqr_scene_points_batch (at the time column the planner produced, with
