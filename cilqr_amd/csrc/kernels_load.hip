@@ -732,6 +732,10 @@ __global__ __launch_bounds__(256) void k_compact(DeviceState a, DeviceState b, i
     b.done_now[j] = 0;
     b.act[j] = j;
     if (b.posn) b.posn[j] = j;
+    if (a.knot0 != nullptr && b.knot0 != nullptr) {   // the first-knot cache follows its problem
+      b.knot0[j] = a.knot0[src];
+      b.knot0[(size_t)b.Bcap + j] = a.knot0[(size_t)a.Bcap + src];
+    }
   }
 }
 void launch_compact(const DeviceState& src, const DeviceState& dst, int n_max, hipStream_t st) {

@@ -47,7 +47,7 @@ namespace cilqr {
 template <int D, bool EX>
 __global__ __launch_bounds__(256) CILQR_COST_ATTR void k_cost_knots(DeviceState s, const int* __restrict__ list,
                                                     const int* __restrict__ n_ptr, int n_max, int cand,
-                                                    int skip_done) {
+                                                    int skip_done, int fill0) {
   extern __shared__ double lds[];
 #ifdef CILQR_COST_PROFILE
   unsigned long long cp_t = wall_clock64();
@@ -55,6 +55,16 @@ __global__ __launch_bounds__(256) CILQR_COST_ATTR void k_cost_knots(DeviceState 
 #endif
   const int n = n_ptr ? min(*n_ptr, n_max) : active_count(s, n_max);
   if ((int)(blockIdx.x * blockDim.x) >= n) return;   // whole block idle: skip the LDS staging too
+  if (blockIdx.y == 0 && s.knot0 != nullptr && !fill0) {   // knot 0 from the first-knot cache (block-uniform; no lane tables)
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
+      const int slot = list ? list[j] : j;
+      if (skip_done && s.acc_idx[slot] != -1) continue;
+      double u[2] = {0.0, 0.0};
+      if (0 < s.p.N) load_u(s, s.cur[slot] ^ cand, 0, slot, u);
+      knot0_cost_cached(s, slot, u, s.part + slot, (size_t)s.Bcap);
+    }
+    return;
+  }
   const double* lanes = stage_lanes(s, lds);
   CP_STAMP(0);   // kernel arguments + lane tables staged
   const int i = blockIdx.y;
@@ -70,6 +80,7 @@ __global__ __launch_bounds__(256) CILQR_COST_ATTR void k_cost_knots(DeviceState 
     CP_STAMP(1);   // cur[slot] -> state loaded
 #endif
     knot_cost<D, EX>(s, lanes, i, slot, x, u, s.part + (size_t)i * kPartPairs * s.Bcap + slot, (size_t)s.Bcap);
+    if (i == 0 && fill0 && s.knot0 != nullptr) knot0_fill(s, slot, s.part + slot, (size_t)s.Bcap);
   }
 #ifdef CILQR_COST_PROFILE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -93,9 +104,23 @@ __global__ __launch_bounds__(256) CILQR_COST_ATTR void k_spec_cost(DeviceState s
   extern __shared__ double lds[];
   const int n = list_count(s, n_ptr, off, n_max);   // `list` points at entry `off` already
   if ((int)(blockIdx.x * blockDim.x) >= n) return;
+  const size_t cap = (size_t)s.spec_cap;
+  if (blockIdx.y == 0 && s.knot0 != nullptr) {   // knot 0 from the first-knot cache (block-uniform; no lane tables)
+    const int r = r0 + blockIdx.z;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
+      const int slot = list[j];
+      if (s.acc_idx[slot] != -1) continue;
+      double u[2] = {0.0, 0.0};
+      if (0 < s.p.N) {
+        const double2 q = s.Us[(size_t)r * s.p.N * cap + j];
+        u[0] = q.x; u[1] = q.y;
+      }
+      knot0_cost_cached(s, slot, u, s.parts + (size_t)r * s.p.K * kPartPairs * cap + j, cap);
+    }
+    return;
+  }
   const double* lanes = stage_lanes(s, lds);
   const int i = blockIdx.y, r = r0 + blockIdx.z;
-  const size_t cap = (size_t)s.spec_cap;
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
     const int slot = list[j];
     if (s.acc_idx[slot] != -1) continue;   // left at the gradient-norm exit
@@ -124,9 +149,24 @@ __global__ __launch_bounds__(256) CILQR_COST_ATTR void k_spec_cost_packed(Device
   const int n = list_count(s, n_ptr, off, n_max);
   constexpr int per_block = 256 / P;
   if ((int)(blockIdx.x * per_block) >= n) return;
+  const size_t cap = (size_t)s.spec_cap;
+  if (blockIdx.y == 0 && s.knot0 != nullptr) {   // knot 0 from the first-knot cache (block-uniform; no lane tables)
+    const int r = r0 + (int)(threadIdx.x % P);
+    if (r >= r_end) return;
+    for (int j = blockIdx.x * per_block + threadIdx.x / P; j < n; j += gridDim.x * per_block) {
+      const int slot = list[j];
+      if (s.acc_idx[slot] != -1) continue;
+      double u[2] = {0.0, 0.0};
+      if (0 < s.p.N) {
+        const double2 q = s.Us[(size_t)r * s.p.N * cap + j];
+        u[0] = q.x; u[1] = q.y;
+      }
+      knot0_cost_cached(s, slot, u, s.parts + (size_t)r * s.p.K * kPartPairs * cap + j, cap);
+    }
+    return;
+  }
   const double* lanes = stage_lanes(s, lds);
   const int i = blockIdx.y, r = r0 + (int)(threadIdx.x % P);
-  const size_t cap = (size_t)s.spec_cap;
   if (r >= r_end) return;
   for (int j = blockIdx.x * per_block + threadIdx.x / P; j < n; j += gridDim.x * per_block) {
     const int slot = list[j];
@@ -186,9 +226,24 @@ __global__ __launch_bounds__(256) CILQR_COST_ATTR void k_round_cost(DeviceState 
   const int n = (r0 == 0) ? active_count(s, n_max) : min(s.counters[r0], n_max);
   constexpr int per_block = 256 / G;
   if ((int)(blockIdx.x * per_block) >= n) return;
+  const size_t cap = (size_t)s.spec_cap;
+  if (blockIdx.y == 0 && s.knot0 != nullptr) {   // knot 0 from the first-knot cache (block-uniform; no lane tables)
+    const int r = r0 + (int)(threadIdx.x % G);
+    for (int e = blockIdx.x * per_block + threadIdx.x / G; e < n; e += gridDim.x * per_block) {
+      const int j = (r0 == 0) ? e : list[e];
+      const int slot = s.act[j];
+      if (s.acc_idx[slot] != -1) continue;
+      double u[2] = {0.0, 0.0};
+      if (0 < s.p.N) {
+        const double2 q = s.Us[(size_t)r * s.p.N * cap + j];
+        u[0] = q.x; u[1] = q.y;
+      }
+      knot0_cost_cached(s, slot, u, s.parts + (size_t)r * s.p.K * kPartPairs * cap + j, cap);
+    }
+    return;
+  }
   const double* lanes = stage_lanes(s, lds);
   const int i = blockIdx.y, r = r0 + (int)(threadIdx.x % G);
-  const size_t cap = (size_t)s.spec_cap;
   for (int e = blockIdx.x * per_block + threadIdx.x / G; e < n; e += gridDim.x * per_block) {
     const int j = (r0 == 0) ? e : list[e];
     const int slot = s.act[j];
@@ -232,15 +287,15 @@ __global__ __launch_bounds__(64) void k_reduce_only(DeviceState s, const int* __
 
 // n_max bounds the list length; n_grid sizes the grid (threads stride over the rest)
 void launch_cost_knots(const DeviceState& s, const int* list, const int* n_ptr, int n_max, int n_grid,
-                       int cand, int skip_done, hipStream_t st) {
+                       int cand, int skip_done, hipStream_t st, int fill0) {
   if (n_grid <= 0) return;
   dim3 g((n_grid + 255) / 256, s.p.K);
-  CILQR_LAUNCH_BY_DISCS(k_cost_knots, g, dim3(256), lane_lds_bytes(s), st, s, list, n_ptr, n_max, cand, skip_done);
+  CILQR_LAUNCH_BY_DISCS(k_cost_knots, g, dim3(256), lane_lds_bytes(s), st, s, list, n_ptr, n_max, cand, skip_done, fill0);
 }
 
-void launch_cost_only(const DeviceState& s, const int* list, int n, int cand, hipStream_t st) {
+void launch_cost_only(const DeviceState& s, const int* list, int n, int cand, hipStream_t st, int fill0) {
   if (n == 0) return;
-  launch_cost_knots(s, list, nullptr, n, n, cand, 0, st);
+  launch_cost_knots(s, list, nullptr, n, n, cand, 0, st, fill0);
   hipLaunchKernelGGL(k_reduce_only, dim3((n + 63) / 64), dim3(64), 0, st, s, list, n);
 }
 
@@ -294,6 +349,42 @@ void launch_quadratize(const DeviceState& s, const int* list, int n, int only_up
   if (n == 0) return;
   dim3 g((n + 255) / 256, s.p.K);
   CILQR_LAUNCH_BY_DISCS(k_quadratize, g, dim3(256), lane_lds_bytes(s), st, s, list, n, only_upd);
+}
+
+// The first iterate of a solve, once: the trajectory job_begin would cost (k_cost_knots) and iteration 0 would then
+// quadratise is walked a single time -- same planes, same five disc centres, same ten lane searches -- and leaves lin / term,
+// the cost pairs in `part` and the first-knot cache.  Slots 0..n-1, positions = slots (k_load_goals).  Three waves per SIMD:
+// the cost's groups ride on top of the quadratisation's registers, and the fourth wave bought k_quadratize nothing.
+// At that budget (170 VGPRs) the kernel uses 167 and SPILLS 6 to scratch -- tolerable once per solve (0.97 ms against the 1.28 ms
+// of the two kernels it replaces), but anything that adds register pressure here spills more: check the resource usage
+// (-Rpass-analysis=kernel-resource-usage) after a change to knot_quadratize or the barrier groups.
+#ifndef CILQR_REF_ORDER
+template <bool EX>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_quadratize_first(DeviceState s, int n) {
+  extern __shared__ double lds[];
+  if ((int)(blockIdx.x * blockDim.x) >= n) return;
+  const double* lanes = stage_lanes(s, lds);
+  const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= n) return;
+  const int i = blockIdx.y;
+  double2* out = s.part + (size_t)i * kPartPairs * s.Bcap + slot;
+  knot_quadratize_cost<5, EX>(s, lanes, s.cur[slot], i, slot, out, (size_t)s.Bcap);
+  if (i == 0 && s.knot0 != nullptr) knot0_fill(s, slot, out, (size_t)s.Bcap);
+}
+#endif
+bool launch_quadratize_first(const DeviceState& s, int n, hipStream_t st) {
+#ifdef CILQR_REF_ORDER
+  (void)s; (void)n; (void)st;
+  return false;
+#else
+  if (s.p.num_of_disc != 5) return false;
+  if (n == 0) return true;
+  dim3 g((n + 255) / 256, s.p.K);
+  if (s.exact_ties) hipLaunchKernelGGL(k_quadratize_first<true>, g, dim3(256), lane_lds_bytes(s), st, s, n);
+  else hipLaunchKernelGGL(k_quadratize_first<false>, g, dim3(256), lane_lds_bytes(s), st, s, n);
+  hipLaunchKernelGGL(k_reduce_only, dim3((n + 63) / 64), dim3(64), 0, st, s, (const int*)nullptr, n);
+  return true;
+#endif
 }
 
 }  // namespace cilqr

@@ -270,6 +270,31 @@ CILQR_DEV void knot_cost(const DeviceState& s, const double* __restrict__ lanes,
   else knot_cost_generic<EX>(s, lanes, i, slot, x, u, out, stride);
 }
 
+// Knot 0 of a candidate whose view carries the first-knot cache (DeviceState::knot0): the state is goals[0] whatever the
+// candidate, so pairs 0 and 2 are copies; pair 1 is evaluated from the candidate's control with the expressions of
+// knot_cost_core / knot_bound_cost (same operands, same order: the same bits).  Both disc-count variants share it.
+CILQR_DEV void knot0_cost_cached(const DeviceState& s, int slot, const double* u, double2* __restrict__ out, size_t stride) {
+  const Params& p = s.p;
+  const double2 a = s.knot0[slot], c = s.knot0[(size_t)s.Bcap + slot];
+  double ju = 0.0, du = 0.0;
+  if (0 < p.N) {
+    ju = p.w_jerk * (u[0] * u[0]) + p.w_delta_rate * (u[1] * u[1]);
+    BarGroup g;
+    const double gu[4] = {u[0] - p.jerk_max, p.jerk_min - u[0],                    // cc:543-546
+                          u[1] - p.delta_rate_max, p.delta_rate_min - u[1]};
+    bar_accumulate(p, gu, g);
+    du = bar_group_value(p, g);
+  }
+  out[0] = a;
+  out[stride] = make_double2(ju, du);
+  out[2 * stride] = c;
+}
+// the first evaluation of a solve fills the cache from the pairs it has just stored (the storing thread reads its own stores)
+CILQR_DEV void knot0_fill(const DeviceState& s, int slot, const double2* out, size_t stride) {
+  s.knot0[slot] = out[0];
+  s.knot0[(size_t)s.Bcap + slot] = out[2 * stride];
+}
+
 // ---------------------------------------------------------------------------------------------
 // quadratisation of knot i: A, B, lx, lu, lxx, luu (terminal knot: lx, lxx with u = 0)
 // ---------------------------------------------------------------------------------------------
@@ -341,8 +366,24 @@ __device__ unsigned long long g_quad_prof[kQuadProfWaves * 8];
 // OnlyFirstPart: stop after the part that is a function of the knot's state and control alone -- the bounds' barriers,
 // the dynamics' Jacobian and the entries of lx / lu / lxx / luu no corridor or lane plane touches (the tail kernel's
 // split quadratisation evaluates the planes on other lanes: knot_plane_items / knot_commit_items below).
-template <int D, bool EX = false, bool InLds = false, bool OnlyFirstPart = false>
-CILQR_DEV void knot_quadratize(const DeviceState& s, const double* __restrict__ lanes, int buf, int i, int slot) {
+// What the fused pass (Cost) carries beside the quadratisation; nothing at all in every other instantiation -- k_quadratize
+// and the tail kernel's variants declare no group, no sum and execute no instruction for it.
+template <bool On>
+struct KnotCostGroups {};
+template <>
+struct KnotCostGroups<true> {
+  BarGroup grp[5];      // corridor, per disc
+  BarGroup lall;        // lanes
+  double ccost = 0.0;
+};
+// Cost (D = 5 only): the pass also carries what knot_cost_core carries -- the five corridor BarGroups and the lane BarGroup, fed
+// with the g = a px + b py - c this function evaluates anyway -- and stores the knot's three cost pairs at cost_out (stride
+// cstride) with the bits knot_cost_core gives: per disc the planes in ascending order in chunks of kCostChunk (the padding
+// planes of the last chunk included), bar_renormalize at the same points, discs merged 0..4, lanes disc by disc, left then right.
+template <int D, bool EX = false, bool InLds = false, bool OnlyFirstPart = false, bool Cost = false>
+CILQR_DEV void knot_quadratize(const DeviceState& s, const double* __restrict__ lanes, int buf, int i, int slot,
+                               double2* __restrict__ cost_out = nullptr, size_t cstride = 0) {
+  static_assert(!Cost || (D == 5 && !OnlyFirstPart && kQuadChunk == kCostChunk), "the fused cost follows knot_cost_core's plane order");
 #ifdef CILQR_QUAD_PROFILE
   unsigned long long qp_t = wall_clock64();
   const unsigned long long qp_t0 = qp_t;
@@ -443,12 +484,21 @@ CILQR_DEV void knot_quadratize(const DeviceState& s, const double* __restrict__ 
     o[(size_t)16 * Bc] = make_double2(q.huu[0], q.huu[1]);
   }
   if constexpr (OnlyFirstPart) return;
+  if constexpr (Cost) {   // the pairs knot_cost_core stores first (JCost cc:501-513, DynamicsCost cc:518-551)
+    const double ex = x[0] - g0.x, ey = x[1] - g0.y, eth = x[2] - gth;
+    const double jx = p.w_x * (ex * ex) + p.w_y * (ey * ey) + p.w_theta * (eth * eth);
+    const double ju = (i < p.N) ? p.w_jerk * (u[0] * u[0]) + p.w_delta_rate * (u[1] * u[1]) : 0.0;
+    const double2 dyn = knot_bound_cost(p, i, x, u);
+    cost_out[0] = make_double2(jx, dyn.x);
+    cost_out[cstride] = make_double2(ju, dyn.y);
+  }
   double sn, cs;
   lean_sincos(x[2], &sn, &cs);
 #ifdef CILQR_QUAD_PROFILE
   asm volatile("" :: "v"(sn), "v"(cs), "v"(pc.a[0]), "v"(q.lx[0]));
   QP_STAMP(0);   // state, goals, first planes arrived; bounds, Jacobian, early stores, sincos
 #endif
+  [[maybe_unused]] KnotCostGroups<Cost> cg;
   // corridor planes x discs (cc:690-727); planes outer (each read once), discs inner
   for (int c0 = 0; c0 < cnt; c0 += C) {
     PlaneChunk<C> nx;
@@ -461,6 +511,10 @@ CILQR_DEV void knot_quadratize(const DeviceState& s, const double* __restrict__ 
         for (int j = 0; j < D; ++j) {
           const double lc = p.disc_off[j] * cs, ls = p.disc_off[j] * sn;
           plane_disc(p, pc.a[k], pc.b[k], pc.c[k], x[0] + lc, x[1] + ls, lc, ls, m);
+          if constexpr (Cost) {   // CorridorCost cc:553-581: plane_disc's g, into the disc's group
+            const double g[1] = {pc.a[k] * (x[0] + lc) + pc.b[k] * (x[1] + ls) - pc.c[k]};
+            bar_accumulate(p, g, cg.grp[j]);
+          }
         }
       } else {
 #pragma unroll 1
@@ -471,7 +525,22 @@ CILQR_DEV void knot_quadratize(const DeviceState& s, const double* __restrict__ 
       }
       plane_commit(q, pc.a[k], pc.b[k], m);
     }
+    if constexpr (Cost) {
+      if ((c0 & 63) == 64 - C) {   // every 64 planes: keep the products in range
+#pragma unroll
+        for (int j = 0; j < 5; ++j) bar_renormalize(cg.grp[j]);
+      }
+    }
     pc = nx;
+  }
+  if constexpr (Cost) {
+    BarGroup call;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      bar_renormalize(cg.grp[j]);
+      bar_merge(call, cg.grp[j]);
+    }
+    cg.ccost = bar_group_value(p, call);
   }
 #ifdef CILQR_QUAD_PROFILE
   asm volatile("" :: "v"(q.h[0]), "v"(q.h[8]), "v"(q.lx[2]));
@@ -494,7 +563,12 @@ CILQR_DEV void knot_quadratize(const DeviceState& s, const double* __restrict__ 
     const double* Rr = lanes + (s.nl + nearest_segment<EX>(s, lanes, 1, px, py)) * kLaneFields;
     plane_disc(p, Rr[0], Rr[1], Rr[2], px, py, lcj, lsj, mr);
     plane_commit(q, Rr[0], Rr[1], mr);
+    if constexpr (Cost) {   // LaneBoundaryCost cc:583-603
+      const double g[2] = {L[0] * px + L[1] * py - L[2], Rr[0] * px + Rr[1] * py - Rr[2]};
+      bar_accumulate(p, g, cg.lall);
+    }
   }
+  if constexpr (Cost) cost_out[2 * cstride] = make_double2(cg.ccost, bar_group_value(p, cg.lall));
 #ifdef CILQR_QUAD_PROFILE
   asm volatile("" :: "v"(q.h[0]), "v"(q.h[8]), "v"(q.lx[2]));
   QP_STAMP(2);   // lanes
@@ -523,6 +597,13 @@ CILQR_DEV void knot_quadratize(const DeviceState& s, const double* __restrict__ 
   o[(size_t)12 * Bc] = make_double2(q.h[4], q.h[5]);
   o[(size_t)13 * Bc] = make_double2(q.h[6], q.h[7]);
   o[(size_t)14 * Bc].x = q.h[8];
+}
+
+// knot_quadratize that also leaves the knot's cost pairs (what knot_cost_core gives for the same state) at `out`
+template <int D, bool EX>
+CILQR_DEV void knot_quadratize_cost(const DeviceState& s, const double* __restrict__ lanes, int buf, int i, int slot,
+                                    double2* __restrict__ out, size_t stride) {
+  knot_quadratize<D, EX, false, false, true>(s, lanes, buf, i, slot, out, stride);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -639,6 +639,7 @@ int cilqr_create(const cilqr_config* cfg, int32_t device, int32_t batch_capacity
     ALLOCM(lambda, cap); ALLOCM(dlambda, cap); ALLOCM(cost_old, cap); ALLOCM(dcost, cap);
     ALLOCM(upd, cap); ALLOCM(acc_idx, cap); ALLOCM(emit, cap); ALLOCM(pid, cap); ALLOCM(done_now, cap);
     ALLOCM(act, cap); ALLOCM(act_next, cap); ALLOCM(posn, cap);
+    ALLOCM(knot0, 2 * cap);
 #undef ALLOCM
     return CILQR_OK;
   };
@@ -707,6 +708,16 @@ int cilqr_create(const cilqr_config* cfg, int32_t device, int32_t batch_capacity
     HIP_TRY(b.ready.create());
     HIP_TRY(b.loaded.create());
   }
+  // the first-knot cache belongs to solves (job_begin): the stage API's trajectories may start anywhere
+  h->knot0_main = d.knot0;
+  d.knot0 = nullptr;
+#ifdef CILQR_REF_ORDER
+  h->use_knot0 = false;   // (the test-only build re-evaluates whole trajectories)
+  h->fuse_first = false;
+#else
+  if (const char* e = std::getenv("CILQR_NO_KNOT0_CACHE")) h->use_knot0 = !(e[0] != '\0' && e[0] != '0');
+  if (const char* e = std::getenv("CILQR_NO_FUSED_FIRST")) h->fuse_first = !(e[0] != '\0' && e[0] != '0');
+#endif
   {   // the stage API works on the main arena with the first set
     const DeviceState v = main_view(h, h->sets[0]);
     d.hist = v.hist; d.iter = v.iter; d.status = v.status; d.n_cost = v.n_cost; d.n_iter_trajs = v.n_iter_trajs;
@@ -1017,6 +1028,7 @@ DeviceState twin_of(const DeviceState& own, const DeviceState& tw) {
   t.lambda = tw.lambda; t.dlambda = tw.dlambda; t.cost_old = tw.cost_old; t.dcost = tw.dcost;
   t.upd = tw.upd; t.acc_idx = tw.acc_idx; t.emit = tw.emit; t.pid = tw.pid; t.done_now = tw.done_now;
   t.act = tw.act; t.act_next = tw.act_next; t.posn = tw.posn;
+  t.knot0 = own.knot0 ? tw.knot0 : nullptr;
   return t;
 }
 
@@ -1053,6 +1065,7 @@ int job_begin(cilqr_solver* h, cilqr_job& j) {
   j.bwd_iter.clear();
   if (j.tm.begin(3)) return CILQR_ERR_DEVICE;
   j.gmain = main_view(h, js);
+  j.gmain.knot0 = h->use_knot0 ? h->knot0_main : nullptr;
   int rc;
   int upload_state;
   {   // (under the lock: the transfer thread moves the field while it works -- found by the ThreadSanitizer run of round 6)
@@ -1134,7 +1147,12 @@ int job_begin(cilqr_solver* h, cilqr_job& j) {
     else launch_init_guess(j.d, B, st, warm_shift);      // cc:169
   }
   if (warm_shift) launch_warm_rollout(j.d, B, warm_shift, st);
-  launch_cost_only(j.d, nullptr, B, 0, st);            // cc:172
+  // cc:172, and the first-knot cache.  Unless the whole batch goes to the tail kernel next (which linearises for itself), the
+  // same pass leaves iteration 0's lin / term: positions are slots (k_load_goals), and nothing up to that iteration's
+  // backward pass writes X, U, lin or term.
+  const bool to_tail = tail_supported(j.d) && B <= j.tail_threshold;
+  j.first_quad = h->fuse_first && !to_tail && launch_quadratize_first(j.d, B, st);
+  if (!j.first_quad) launch_cost_only(j.d, nullptr, B, 0, st, 1);
   launch_init_cost_commit(j.d, B, st);                 // cc:170,173
   if (j.o_it) launch_export_iter_traj(j.d, nullptr, B, j.o_it, out->max_iter_trajs, st);
   if (j.tm.end()) return CILQR_ERR_DEVICE;
@@ -1227,6 +1245,8 @@ int job_iterate(cilqr_solver* h, cilqr_job& j, int stage) {
       a.n_next = d.counters + kCntActive + it % 3;
       DeviceState f = h->fin;
       adopt_job_fields(&f, j.gmain);
+      if (d.knot0 == nullptr) f.knot0 = nullptr;
+      j.first_quad = false;   // (a hand-over before iteration 0: lin / term stay behind, the finishing arena linearises anew)
       launch_compact(a, f, n_hint, st);
       hipLaunchKernelGGL(k_seed_counters, dim3(1), dim3(64), 0, st, f.counters, a.n_next, kCntActive + it % 3);
       HIP_TRY(hipGetLastError());
@@ -1263,7 +1283,8 @@ int job_iterate(cilqr_solver* h, cilqr_job& j, int stage) {
     // every active problem is linearised every iteration: the rows of `lin` belong to POSITIONS of this iteration's active
     // list (DeviceState::posn), so a problem whose line search was rejected (1.3 % of the iterations; cc:296-308 keeps its
     // linearisation) computes the same numbers again instead of finding them at last iteration's position
-    launch_quadratize(d, d.act, n_hint, 0, st);        // cc:203-214
+    if (j.first_quad) j.first_quad = false;            // iteration 0: job_begin's pass has done it
+    else launch_quadratize(d, d.act, n_hint, 0, st);   // cc:203-214
     hipEvent_t eb0, eb1;
     if (j.tm.end() || j.tm.pair(1, &eb0, &eb1)) return CILQR_ERR_DEVICE;
     cilqr_phase_mark_begin(1);

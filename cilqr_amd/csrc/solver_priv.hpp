@@ -126,6 +126,7 @@ struct cilqr_job {
   bool owns_fin = false;    // this solve holds the finishing arena / the tail workspace (cilqr_solver::fin_busy)
   bool tail_used = false;
   int tail_n = 0;
+  bool first_quad = false;  // job_begin's fused pass has left lin / term of the first iterate in d: iteration 0 does not quadratise
   std::vector<int> bwd_iter;  // iteration index of every profiled backward launch
   cilqr_timer tm;
   cilqr_profile prof;
@@ -166,6 +167,11 @@ struct cilqr_solver {
   // left, so that the main arena is free for the next solve (cilqr_submit) while the stragglers finish
   cilqr::DeviceState fin, fin_twin;
   int fin_cap = 0;
+  // first-knot cache of the main arena (DeviceState::knot0).  Kept out of `ds`, whose views the stage API uses: a solve's view
+  // gets it in job_begin.  use_knot0 / fuse_first: test hooks, CILQR_NO_KNOT0_CACHE / CILQR_NO_FUSED_FIRST at cilqr_create.
+  double2* knot0_main = nullptr;
+  bool use_knot0 = true;
+  bool fuse_first = true;
   int fin_threshold = 0;     // hand the survivors over at this active count (CILQR_OPT_FINISH_THRESHOLD); 0 = never
   bool compaction = true;
   int compact_percent = 75;  // re-pack when the survivors fill at most this share of the occupied slots

@@ -18,6 +18,7 @@
 //   term   [9][Bcap]       double2   lx_N 6 | lxx_N (3x3 block + 3 diagonal)
 //   gains  [N][7][Bcap]    double2   K (2x6 row-major) | k (2)
 //   part   [K][3][Bcap]    double2   per-knot cost partials (J, bounds) of the state | of the control | (corridor, lane)
+//   knot0  [2][Bcap]       double2   pairs 0 and 2 of knot 0's partials: constants of the problem (every rollout starts from goals[0])
 //   hist   [max_iter+1][5][Bcap] double
 //
 // Lane tables are shared by the batch and read through wave-uniform (scalar) loads.
@@ -123,6 +124,12 @@ struct DeviceState {
   double* dV;      // [2][Bcap]
   double* gnorm;   // [Bcap]
   double2* part;   // [K][3][Bcap]
+  // First-knot cache.  Every rollout of a solve starts from goals[0] (search_core.hpp: forward_core; the init guesses and the
+  // warm rollouts do the same), so the state terms of knot 0 -- (J, bounds) of the state and (corridor, lane) -- are the same
+  // for every candidate of every iteration: the first cost evaluation of a solve stores them here, the cost kernels of the
+  // line search copy them and evaluate only the control's pair.  Moved by k_compact.  nullptr = evaluate knot 0 like any other:
+  // the stage API (its trajectories may start anywhere), the tail kernel's view, the CILQR_REF_ORDER build, CILQR_NO_KNOT0_CACHE.
+  double2* knot0;  // [2][Bcap]
   double* trial;   // [5][Bcap] cost components of the last evaluated trajectory
   double* hist;    // [max_iter+1][5][Bcap]
 
@@ -213,9 +220,14 @@ void launch_init_guess_tracker(const DeviceState& s, const TrackerParams& tp, in
                                const int* warm_shift = nullptr);
 void launch_set_trajectory(const DeviceState& s, int B, const double* X, const double* U, hipStream_t st);
 // cost of buffer (cur ^ cand) for the n listed slots -> trial[], no accept logic
-void launch_cost_only(const DeviceState& s, const int* list, int n, int cand, hipStream_t st);
+// fill0 (with a first-knot cache in the view): the first evaluation of a solve -- knot 0 is evaluated in full and cached
+void launch_cost_only(const DeviceState& s, const int* list, int n, int cand, hipStream_t st, int fill0 = 0);
 void launch_cost_knots(const DeviceState& s, const int* list, const int* n_ptr, int n_max, int n_grid,
-                       int cand, int skip_done, hipStream_t st);
+                       int cand, int skip_done, hipStream_t st, int fill0 = 0);
+// the first iterate of a solve in one pass: launch_quadratize of slots 0..n-1 (positions = slots) that also leaves what
+// launch_cost_only leaves (part, trial) and fills the first-knot cache.  False: not available for this view (disc count
+// other than 5, the reference-order build) -- nothing was launched.
+bool launch_quadratize_first(const DeviceState& s, int n, hipStream_t st);
 void launch_spec_cost(const DeviceState& s, const int* list, const int* n_ptr, int off, int n_max, int n_grid, int r0,
                       int sparse, hipStream_t st);
 int spec_open_capacity(const DeviceState& s);   // most active problems an all-eleven-step-sizes pass can take (kernels_search.hip)
