@@ -128,6 +128,11 @@ HIT_FRONT_STATIC, HIT_FRONT_BARRIER, HIT_FRONT_DYNAMIC = 8, 16, 32
 HIT_BITS = (HIT_REAR_STATIC, HIT_REAR_BARRIER, HIT_REAR_DYNAMIC, HIT_FRONT_STATIC, HIT_FRONT_BARRIER, HIT_FRONT_DYNAMIC)
 # cilqr_resample_rows / cilqr_resample_rows_batch: the key column of a query (CILQR_KEY_*)
 KEY_TIME, KEY_STATION = 0, 1
+# cilqr_frenet_rows / cilqr_frenet_rows_batch: plain [K][2] x, y rows (CILQR_ROWS_POINTS; these two calls only), the doubles
+# of a centre-line row and of a result row (CILQR_FRENET_FIELDS), doubles per row of every layout they accept
+ROWS_POINTS = 4
+CENTER_FIELDS, FRENET_FIELDS = 7, 8
+FRENET_ROWS_FIELDS = {**ROWS_FIELDS, ROWS_POINTS: 2}
 
 
 class TrackerConfig(C.Structure):
@@ -160,6 +165,7 @@ EXPORTS = [
     "cilqr_default_corridor_config", "cilqr_build_corridors", "cilqr_lane_constraints",
     "cilqr_default_dp_config", "cilqr_dp_plan", "cilqr_dp_plan_batch", "cilqr_scene_points_batch", "cilqr_plan_scenes_batch",
     "cilqr_check_collisions", "cilqr_check_collisions_batch", "cilqr_resample_rows", "cilqr_resample_rows_batch",
+    "cilqr_frenet_rows", "cilqr_cartesian_points", "cilqr_frenet_rows_batch", "cilqr_cartesian_points_batch",
     "cilqr_road_barriers", "cilqr_default_tracker_config",
     "cilqr_set_tracker_config",
     "cilqr_solve_batch_warm", "cilqr_submit_warm", "cilqr_stage_load_warm", "cilqr_pool_submit_warm", "cilqr_multi_solve_warm",
@@ -246,6 +252,12 @@ def lib():
         L.cilqr_resample_rows.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         L.cilqr_resample_rows_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                                 C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+        L.cilqr_frenet_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.cilqr_cartesian_points.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.cilqr_frenet_rows_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_int32]
+        L.cilqr_cartesian_points_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                   C.c_int32]
         L.cilqr_default_tracker_config.argtypes = [C.POINTER(TrackerConfig)]
         L.cilqr_default_tracker_config.restype = None
         L.cilqr_set_tracker_config.argtypes = [C.c_void_p, C.POINTER(TrackerConfig)]
@@ -813,6 +825,66 @@ class BatchIlqrOptimizer:
         return self.L.cilqr_resample_rows_batch(self.h, batch, layout, rows_ptr, n_knots, key, queries_ptr, n_queries,
                                                 int(per_problem), out_ptr, memory)
 
+    def frenet(self, center, rows, layout: int = ROWS_POINTS):
+        """DiscretizedTrajectory::GetProjection of every row of a batch of trajectories onto the centre line, on the GPU
+        (cilqr_frenet_rows_batch).  center [n,7] (NumPy, host memory); rows [B,K,F] in `layout` (ROWS_TRAJ / ROWS_PLAN /
+        ROWS_COARSE / ROWS_POINTS: only x and y are read), a NumPy array or a contiguous float64 device tensor; the result
+        [B,K,8] = station, lateral, then x, y, theta, kappa, left_bound, right_bound of the projected point, is of that kind."""
+        center = _center_line(center)
+        on_device = _is_device_tensor(rows)
+        if on_device:
+            if not rows.is_cuda or not rows.is_contiguous() or str(rows.dtype) != "torch.float64":
+                raise ValueError("rows on the device: a contiguous float64 tensor")
+        else:
+            rows = _f64(rows)
+        if rows.ndim != 3 or rows.shape[2] != FRENET_ROWS_FIELDS.get(layout, rows.shape[2]):
+            raise ValueError(f"rows must be [B, K, {FRENET_ROWS_FIELDS.get(layout)}]")
+        B, K = int(rows.shape[0]), int(rows.shape[1])
+        if on_device:
+            import torch
+            out = torch.empty((B, K, FRENET_FIELDS), dtype=torch.float64, device=rows.device)
+            ptrs = (rows.data_ptr(), out.data_ptr())
+        else:
+            out = np.empty((B, K, FRENET_FIELDS))
+            ptrs = (rows.ctypes.data, out.ctypes.data)
+        self._chk(self.frenet_raw(center, B, layout, ptrs[0], K, ptrs[1], MEM_DEVICE if on_device else MEM_HOST), "frenet")
+        return out
+
+    def frenet_raw(self, center, batch, layout, rows_ptr, n_knots, frenet_ptr, memory) -> int:
+        """Pointer-level form (rows / frenet in device or host memory as `memory` says: the `plan` rows of plan_scenes_raw
+        and the output of resample_raw are projected where they lie); center [n,7] float64 in host memory; returns the code."""
+        return self.L.cilqr_frenet_rows_batch(self.h, center.ctypes.data, center.shape[0], batch, layout, rows_ptr, n_knots,
+                                              frenet_ptr, memory)
+
+    def cartesian(self, center, sl):
+        """DiscretizedTrajectory::GetCartesian for a list of (station, lateral) pairs on the GPU
+        (cilqr_cartesian_points_batch).  center [n,7] (NumPy); sl [...,2], a NumPy array or a contiguous float64 device
+        tensor; the result [...,3] = x, y, theta is of that kind."""
+        center = _center_line(center)
+        on_device = _is_device_tensor(sl)
+        if on_device:
+            if not sl.is_cuda or not sl.is_contiguous() or str(sl.dtype) != "torch.float64":
+                raise ValueError("sl on the device: a contiguous float64 tensor")
+        else:
+            sl = _f64(sl)
+        if sl.ndim < 1 or sl.shape[-1] != 2:
+            raise ValueError("sl must be [..., 2]")
+        shape = tuple(int(v) for v in sl.shape[:-1]) + (3,)
+        n = int(np.prod(shape[:-1], dtype=np.int64))
+        if on_device:
+            import torch
+            out = torch.empty(shape, dtype=torch.float64, device=sl.device)
+            ptrs = (sl.data_ptr(), out.data_ptr())
+        else:
+            out = np.empty(shape)
+            ptrs = (sl.ctypes.data, out.ctypes.data)
+        self._chk(self.cartesian_raw(center, n, ptrs[0], ptrs[1], MEM_DEVICE if on_device else MEM_HOST), "cartesian")
+        return out
+
+    def cartesian_raw(self, center, n, sl_ptr, xyt_ptr, memory) -> int:
+        """Pointer-level form (sl / xyt in device or host memory as `memory` says); returns the code."""
+        return self.L.cilqr_cartesian_points_batch(self.h, center.ctypes.data, center.shape[0], n, sl_ptr, xyt_ptr, memory)
+
     def open_loop_rollout(self, x0, U):
         x0, U = _f64(x0), _f64(U)
         B = x0.shape[0]
@@ -890,6 +962,40 @@ def resample_rows(rows, layout: int, queries, key: int = KEY_TIME) -> np.ndarray
                                    out.ctypes.data)
     if rc != OK:
         raise CilqrError(rc, "in cilqr_resample_rows")
+    return out
+
+
+def _center_line(center) -> np.ndarray:
+    center = _f64(center)
+    if center.ndim != 2 or center.shape[1] != CENTER_FIELDS:
+        raise ValueError(f"center must be [n, {CENTER_FIELDS}]")
+    return center
+
+
+def frenet_rows(center, rows, layout: int = ROWS_POINTS) -> np.ndarray:
+    """DiscretizedTrajectory::GetProjection of every row of one trajectory through the C-ABI (cilqr_frenet_rows, host
+    only): center [n,7], rows [K,F] in `layout` (ROWS_*, ROWS_POINTS included) -> [K,8] = station, lateral, then x, y,
+    theta, kappa, left_bound, right_bound of the projected point."""
+    center, rows = _center_line(center), _f64(rows)
+    if rows.ndim != 2 or rows.shape[1] != FRENET_ROWS_FIELDS.get(layout, rows.shape[1]):
+        raise ValueError(f"rows must be [K, {FRENET_ROWS_FIELDS.get(layout)}]")
+    out = np.empty((rows.shape[0], FRENET_FIELDS))
+    rc = lib().cilqr_frenet_rows(center.ctypes.data, center.shape[0], layout, rows.ctypes.data, rows.shape[0], out.ctypes.data)
+    if rc != OK:
+        raise CilqrError(rc, "in cilqr_frenet_rows")
+    return out
+
+
+def cartesian_points(center, sl) -> np.ndarray:
+    """DiscretizedTrajectory::GetCartesian through the C-ABI (cilqr_cartesian_points, host only): center [n,7], sl [M,2]
+    station, lateral -> [M,3] x, y, theta."""
+    center, sl = _center_line(center), _f64(sl)
+    if sl.ndim != 2 or sl.shape[1] != 2:
+        raise ValueError("sl must be [M, 2]")
+    out = np.empty((sl.shape[0], 3))
+    rc = lib().cilqr_cartesian_points(center.ctypes.data, center.shape[0], sl.ctypes.data, sl.shape[0], out.ctypes.data)
+    if rc != OK:
+        raise CilqrError(rc, "in cilqr_cartesian_points")
     return out
 
 

@@ -256,6 +256,10 @@ struct cilqr_solver {
   cilqr::dev_mem cc_tab, cc_in, cc_out;
   // cilqr_resample_rows_batch (resample_batch.hip), grown likewise: the staging of HOST rows and queries, of HOST output rows
   cilqr::dev_mem rs_in, rs_out;
+  // cilqr_frenet_rows_batch / cilqr_cartesian_points_batch (frenet_batch.hip), grown likewise: the centre line's tables on
+  // their way to the device, the staging of HOST rows / pairs and of HOST results
+  cilqr::pinned_mem fr_tab_host;
+  cilqr::dev_mem fr_tab, fr_in, fr_out;
 };
 
 namespace cilqr {

@@ -32,6 +32,9 @@
  *   cilqr_resample_rows     DiscretizedTrajectory::EvaluateTime / EvaluateStation (algorithm/utils/discretized_trajectory.cpp:50-136,
  *                           math::slerp math_utils.h:208-225) for a list of queries, one trajectory on the host;
  *                           cilqr_resample_rows_batch: B trajectories per call on the GPU
+ *   cilqr_frenet_rows       DiscretizedTrajectory::GetProjection (discretized_trajectory.cpp:138-190) of every row of a
+ *                           trajectory onto the centre line, and cilqr_cartesian_points, its inverse GetCartesian
+ *                           (cpp:192-196), on the host; cilqr_frenet_rows_batch / cilqr_cartesian_points_batch on the GPU
  *
  * Layout convention: every per-problem array is problem-major ("[B][...]"), IEEE fp64,
  * in host or device memory as flagged by `memory`.
@@ -648,6 +651,64 @@ int cilqr_resample_rows(int32_t layout, const double* rows, int32_t n_knots, int
 int cilqr_resample_rows_batch(cilqr_handle h, int32_t batch, int32_t layout, const double* rows, int32_t n_knots,
                               int32_t key, const double* queries, int32_t n_queries, int32_t per_problem,
                               double* out, int32_t memory);
+
+/* ---- frenet: points in the frame of the centre line (DiscretizedTrajectory::GetProjection / GetCartesian,
+ * algorithm/utils/discretized_trajectory.cpp:138-196); host calls, no handle ----
+ * The reference plans in the Frenet frame of the road: DpPlanner starts from GetProjection of the start state, Environment
+ * builds its barriers with GetCartesian, and the bounds a trajectory has to respect are left_bound / right_bound at a
+ * station.  `center` is [n_center][7] = s x y theta kappa left_bound right_bound (as in cilqr_scene_batch: HOST memory,
+ * one line per call), n_center >= 2.  Every operation below is rounded once (no fused multiply-add).
+ * Projection of a point (px, py):
+ *   nearest   at = the FIRST index minimising dx*dx + dy*dy with dx = x_i - px, dy = y_i - py: a scan over all points
+ *             with a strict `<`, starting from DBL_MAX at index 0 (QueryNearestPoint) -- if every distance is a NaN or
+ *             >= DBL_MAX, at = 0.
+ *   pair      i0 = max(0, at-1), i1 = min(n_center-1, at+1); the projected point starts as row `at`.  If i0 < i1 (always,
+ *             for n_center >= 2): v0 = p - c[i0], v1 = c[i1] - c[i0], delta_s = (v0.v1) / sqrt(v1.v1), and the projected
+ *             point is LinearInterpolateTrajectory(c[i0], c[i1], s_i0 + delta_s):
+ *                 |s_i1 - s_i0| < 1e-10 (strict): row i0 as bits (not the nearest row);
+ *                 otherwise w = (s - s_i0) / (s_i1 - s_i0), s the query station itself, theta by slerp with the reference's
+ *                 NormalizeAngle (as under "resample"), x y kappa left_bound right_bound (1 - w) * a + w * b.
+ *             It extrapolates past either end (w < 0, w > 1), as the reference does.  c[i0] and c[i1] coincident in x, y
+ *             divide by zero: the arithmetic decides.
+ *   lateral   copysign(hypot(nr_x, nr_y), nr_y * cos(theta) - nr_x * sin(theta)) with nr = p - projected point and theta
+ *             the projected point's; positive to the left of the line.
+ *   row       CILQR_FRENET_FIELDS doubles: station, lateral, then the projected point's x, y, theta, kappa, left_bound,
+ *             right_bound.  The margins to the road edges are left_bound - lateral and lateral + right_bound.
+ * Inverse, for a pair (station, lateral): ref = EvaluateStation(station) -- the bracket of "resample" on the station
+ * column, interpolated as above -- and the output is [3]: ref.x - lateral * sin(ref.theta), ref.y + lateral * cos(ref.theta),
+ * ref.theta.
+ * Non-finite inputs are no error: the arithmetic decides.  A result that is a NaN is a NaN in every implementation; which
+ * NaN is not part of the rule, and neither is the sign that a NaN cross product lends to `lateral`.
+ * sin / cos in the host calls are the C library's sincos of the angle: what the reference's build (g++ -O2) makes of its
+ * std::sin and std::cos of one argument; glibc's sincos is not its sin / cos in the last bit for every angle.
+ *   rows [n_rows][fields] in one of CILQR_ROWS_TRAJ / _PLAN / _COARSE / _POINTS: only x and y are read.
+ * CILQR_ERR_NULL; CILQR_ERR_ARG for n_center < 2, n_rows / n < 1, an unknown layout, an output that overlaps an input.
+ * C++ callers use include/cilqr/trajectory_queries.hpp directly (project_point, project_rows, cartesian_point). */
+#define CILQR_ROWS_POINTS 4      /* [K][2] x 0, y 1: the two projection calls only (resample and the audit refuse it) */
+#define CILQR_FRENET_FIELDS 8    /* station, lateral, x, y, theta, kappa, left_bound, right_bound */
+int cilqr_frenet_rows(const double* center, int32_t n_center, int32_t layout, const double* rows, int32_t n_rows,
+                      double* frenet /* [n_rows][CILQR_FRENET_FIELDS] */);
+int cilqr_cartesian_points(const double* center, int32_t n_center, const double* sl /* [n][2] station, lateral */, int32_t n,
+                           double* xyt /* [n][3] x, y, theta */);
+/* ---- the same for B trajectories of K knots / n pairs per call, on the GPU (kernels_frenet.hip; ABI 7) ----
+ *   rows [B][n_knots][fields], frenet [B][n_knots][CILQR_FRENET_FIELDS]; sl [n][2], xyt [n][3]: in `memory`, nothing beyond
+ *   the alignment of a double is assumed.  `center` is HOST memory in either case.
+ * The nearest point is found by the full scan, unpruned, so `at` is the host call's.  Every element of `frenet` is the host
+ * call's bit for bit, except the SIGN of lateral: the kernel takes sin / cos for the cross product from its own lean
+ * routine (about an ulp off the C library's), so the sign can differ where |cross| is within rounding of 0 -- a point on
+ * the line (the host's |cross| <= 1e-9 |nr|); |lateral| is the host's bits there too.  hypot follows the C library's
+ * evaluation for components up to 2^511 whose larger one is 0 or at least 2^-459.  In `xyt`, theta is the host call's
+ * bits; x and y use the device library's sin / cos (cilqr_device_math fn 8 / 7) in the host's expression.
+ * Both calls run on the handle's stream and wait for that stream only.  DEVICE arrays need no work space beyond the
+ * centre line's tables, which are kept in a block that belongs to the handle and grows to the largest call; HOST arrays
+ * are staged in blocks of the same kind.  There is no limit on n_center, n_knots or n beyond int32: sizes are computed in
+ * size_t.  Checked before anything is launched, the handle staying usable: CILQR_ERR_NULL; CILQR_ERR_ARG for n_center < 2,
+ * batch / n_knots / n < 1, an unknown layout or memory flag, an output that overlaps an input; CILQR_ERR_STATE while solves
+ * are submitted on the handle. */
+int cilqr_frenet_rows_batch(cilqr_handle h, const double* center, int32_t n_center, int32_t batch, int32_t layout,
+                            const double* rows, int32_t n_knots, double* frenet, int32_t memory);
+int cilqr_cartesian_points_batch(cilqr_handle h, const double* center, int32_t n_center, int32_t n, const double* sl,
+                                 double* xyt, int32_t memory);
 
 /* ---- TrajectoryPlanner::Plan for B scenes per call (trajectory_planner.cpp:28-162) ----
  * scene batch -> cilqr_dp_plan_batch -> cilqr_scene_points_batch (at the time column the planner produced, with

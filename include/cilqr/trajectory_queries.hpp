@@ -1,7 +1,10 @@
 // include/cilqr/trajectory_queries.hpp -- DiscretizedTrajectory::EvaluateTime / EvaluateStation
 // (algorithm/utils/discretized_trajectory.cpp:50-136, math::slerp math_utils.h:208-225) on rows in the layouts of
 // include/cilqr.h: the host statement of cilqr_resample_rows, which cilqr_resample_rows_batch is held to bit for bit.
-// Header-only, C++14, no HIP.  The rule is stated once, in include/cilqr.h ("resample"); this file follows it step by step.
+// Further down, GetProjection / GetCartesian (cpp:138-196) on a centre line: the host statement of cilqr_frenet_rows and
+// cilqr_cartesian_points.
+// Header-only, C++14, no HIP.  The rules are stated once, in include/cilqr.h ("resample", "frenet"); this file follows
+// them step by step.
 #ifndef CILQR_TRAJECTORY_QUERIES_HPP_
 #define CILQR_TRAJECTORY_QUERIES_HPP_
 
@@ -111,6 +114,115 @@ inline void resample_rows(int layout, const double* rows, int n_knots, int key, 
     interpolate(c, kc, rows + (size_t)(i - 1) * c.fields, rows + (size_t)i * c.fields, queries[m],
                 out + (size_t)m * c.fields);
   }
+}
+
+// ---- the Frenet frame of a centre line (DiscretizedTrajectory::GetProjection / GetCartesian, cpp:138-196): the host
+// statement of cilqr_frenet_rows / cilqr_cartesian_points.  The rule is stated in include/cilqr.h ("frenet").
+// center [n][7] = s x y theta kappa left_bound right_bound, n >= 2.
+constexpr int kCenterFields = 7;
+constexpr int kFrenetFields = 8;   // station, lateral, then x y theta kappa left_bound right_bound of the projected point
+
+// where a layout keeps x (y follows it) and how many doubles a row has; layout 4 is CILQR_ROWS_POINTS.  false: no such layout
+inline bool point_columns(int layout, int* fields, int* x_col) {
+  switch (layout) {
+    case 0: *fields = 10; *x_col = 1; return true;
+    case 1: *fields = 11; *x_col = 2; return true;
+    case 2: *fields = 9; *x_col = 2; return true;
+    case 4: *fields = 2; *x_col = 0; return true;
+  }
+  return false;
+}
+
+// sin and cos of one angle as the reference's build evaluates them: g++ -O2 turns its std::sin / std::cos of one argument
+// into ONE sincos call, and glibc's sincos differs from its sin / cos in the last bit for some angles
+inline void sin_cos(double angle, double* sn, double* cs) {
+#if defined(__GLIBC__)
+  ::sincos(angle, sn, cs);
+#else
+  *sn = std::sin(angle);
+  *cs = std::cos(angle);
+#endif
+}
+
+// LinearInterpolateTrajectory (cpp:66-87) on centre rows: out[7]
+inline void interpolate_center(const double* p0, const double* p1, double s, double* out) {
+  const double s0 = p0[0], s1 = p1[0];
+  if (std::fabs(s1 - s0) < kMathEpsilon) {
+    std::memcpy(out, p0, sizeof(double) * kCenterFields);
+    return;
+  }
+  const double w = (s - s0) / (s1 - s0);
+  out[0] = s;
+  out[1] = (1 - w) * p0[1] + w * p1[1];
+  out[2] = (1 - w) * p0[2] + w * p1[2];
+  out[3] = slerp(p0[3], s0, p1[3], s1, s);
+  out[4] = (1 - w) * p0[4] + w * p1[4];
+  out[5] = (1 - w) * p0[5] + w * p1[5];
+  out[6] = (1 - w) * p0[6] + w * p1[6];
+}
+
+// QueryNearestPoint (cpp:138-157): the first index with the smallest squared distance; 0 when none is below DBL_MAX
+inline int nearest_center_point(const double* center, int n_center, double px, double py) {
+  int at = 0;
+  double nearest = 1.7976931348623157e308;   // std::numeric_limits<double>::max()
+  for (int i = 0; i < n_center; ++i) {
+    const double dx = center[(size_t)i * kCenterFields + 1] - px, dy = center[(size_t)i * kCenterFields + 2] - py;
+    const double d = dx * dx + dy * dy;
+    if (d < nearest) {
+      at = i;
+      nearest = d;
+    }
+  }
+  return at;
+}
+
+// GetProjection (cpp:159-190): out[8].  `cross` (optional) receives what the sign of the lateral offset was taken from.
+inline void project_point(const double* center, int n_center, double px, double py, double* out, double* cross = nullptr) {
+  const int at = nearest_center_point(center, n_center, px, py);
+  const int i0 = at > 0 ? at - 1 : 0;
+  const int i1 = at + 1 < n_center - 1 ? at + 1 : n_center - 1;
+  double pp[kCenterFields];
+  std::memcpy(pp, center + (size_t)at * kCenterFields, sizeof(pp));
+  if (i0 < i1) {
+    const double* c0 = center + (size_t)i0 * kCenterFields;
+    const double* c1 = center + (size_t)i1 * kCenterFields;
+    const double v0x = px - c0[1], v0y = py - c0[2];
+    const double v1x = c1[1] - c0[1], v1y = c1[2] - c0[2];
+    const double v1_norm = std::sqrt(v1x * v1x + v1y * v1y);
+    const double dot = v0x * v1x + v0y * v1y;
+    const double delta_s = dot / v1_norm;
+    interpolate_center(c0, c1, c0[0] + delta_s, pp);
+  }
+  const double nr_x = px - pp[1], nr_y = py - pp[2];
+  double sn, cs;
+  sin_cos(pp[3], &sn, &cs);
+  const double side = nr_y * cs - nr_x * sn;
+  out[0] = pp[0];
+  out[1] = std::copysign(std::hypot(nr_x, nr_y), side);
+  std::memcpy(out + 2, pp + 1, sizeof(double) * (kCenterFields - 1));
+  if (cross != nullptr) *cross = side;
+}
+
+// rows [n_rows][fields] of `layout` -> frenet [n_rows][8]; the arguments are taken as checked (cilqr_frenet_rows)
+inline void project_rows(const double* center, int n_center, int layout, const double* rows, int n_rows, double* frenet) {
+  int fields = 0, xc = 0;
+  if (!point_columns(layout, &fields, &xc)) return;
+  for (int r = 0; r < n_rows; ++r) {
+    const double* p = rows + (size_t)r * fields + xc;
+    project_point(center, n_center, p[0], p[1], frenet + (size_t)r * kFrenetFields);
+  }
+}
+
+// GetCartesian (cpp:192-196) with the heading of the evaluated point: out[3] = x, y, theta
+inline void cartesian_point(const double* center, int n_center, double station, double lateral, double* out) {
+  const int i = bracket(center, kCenterFields, 0, n_center, station);
+  double ref[kCenterFields];
+  interpolate_center(center + (size_t)(i - 1) * kCenterFields, center + (size_t)i * kCenterFields, station, ref);
+  double sn, cs;
+  sin_cos(ref[3], &sn, &cs);
+  out[0] = ref[1] - lateral * sn;
+  out[1] = ref[2] + lateral * cs;
+  out[2] = ref[3];
 }
 
 }  // namespace trajectory_queries
