@@ -133,6 +133,9 @@ KEY_TIME, KEY_STATION = 0, 1
 ROWS_POINTS = 4
 CENTER_FIELDS, FRENET_FIELDS = 7, 8
 FRENET_ROWS_FIELDS = {**ROWS_FIELDS, ROWS_POINTS: 2}
+# cilqr_clearance_rows / cilqr_clearance_rows_batch: the columns of a knot's row (CILQR_CLEARANCE_FIELDS)
+CLEARANCE_FIELDS = 4
+CLEAR_REAR_STATIC, CLEAR_REAR_DYNAMIC, CLEAR_FRONT_STATIC, CLEAR_FRONT_DYNAMIC = 0, 1, 2, 3
 
 
 class TrackerConfig(C.Structure):
@@ -166,6 +169,7 @@ EXPORTS = [
     "cilqr_default_dp_config", "cilqr_dp_plan", "cilqr_dp_plan_batch", "cilqr_scene_points_batch", "cilqr_plan_scenes_batch",
     "cilqr_check_collisions", "cilqr_check_collisions_batch", "cilqr_resample_rows", "cilqr_resample_rows_batch",
     "cilqr_frenet_rows", "cilqr_cartesian_points", "cilqr_frenet_rows_batch", "cilqr_cartesian_points_batch",
+    "cilqr_clearance_rows", "cilqr_clearance_rows_batch",
     "cilqr_road_barriers", "cilqr_default_tracker_config",
     "cilqr_set_tracker_config",
     "cilqr_solve_batch_warm", "cilqr_submit_warm", "cilqr_stage_load_warm", "cilqr_pool_submit_warm", "cilqr_multi_solve_warm",
@@ -258,6 +262,11 @@ def lib():
                                               C.c_void_p, C.c_int32]
         L.cilqr_cartesian_points_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                    C.c_int32]
+        L.cilqr_clearance_rows.argtypes = [C.POINTER(DpConfig), C.POINTER(SceneStruct), C.c_int32, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        L.cilqr_clearance_rows_batch.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(SceneBatchStruct), C.c_int32,
+                                                 C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_double, C.POINTER(C.c_int32)]
         L.cilqr_default_tracker_config.argtypes = [C.POINTER(TrackerConfig)]
         L.cilqr_default_tracker_config.restype = None
         L.cilqr_set_tracker_config.argtypes = [C.c_void_p, C.POINTER(TrackerConfig)]
@@ -787,6 +796,39 @@ class BatchIlqrOptimizer:
                                                  n_hit_ptr, C.byref(n))
         return rc, int(n.value)
 
+    def clearance(self, packed: dict, rows, layout: int, cfg: "DpConfig | None" = None, threshold: float = 0.0):
+        """How close every knot of a batch of trajectories comes to the obstacles of its scene, on the GPU
+        (cilqr_clearance_rows_batch), host arrays.  `packed` = scene_io.pack_scene_batch(center, scenes), rows [B,K,F] in
+        `layout` (ROWS_TRAJ / ROWS_PLAN / ROWS_COARSE: only time, x, y, theta are read).  Returns dict(clearance [B,K,4] =
+        rear disc / static, rear / dynamic, front / static, front / dynamic (+inf: no obstacle of that kind), nearest [B,K,4]
+        int32 slots (-1: none), min_clearance [B], min_knot [B] int32 (-1: everything +inf), n_below = the scenes with
+        min_clearance < threshold)."""
+        cfg = cfg or default_dp_config()
+        B = int(packed["batch"])
+        rows = _f64(rows)
+        if rows.ndim != 3 or rows.shape[0] != B or rows.shape[2] != ROWS_FIELDS.get(layout, rows.shape[2]):
+            raise ValueError(f"rows must be [{B}, K, {ROWS_FIELDS.get(layout)}]")
+        K = rows.shape[1]
+        keep = {k: np.ascontiguousarray(v) for k, v in packed.items() if isinstance(v, np.ndarray)}
+        sb = scene_batch_struct(packed, MEM_HOST, **{k: _ptr(keep[k]) for k in _SCENE_BATCH_ARRAYS})
+        clearance, nearest = np.zeros((B, K, CLEARANCE_FIELDS)), np.zeros((B, K, CLEARANCE_FIELDS), dtype=np.int32)
+        lowest, knot = np.zeros(B), np.zeros(B, dtype=np.int32)
+        rc, n = self.clearance_raw(cfg, sb, layout, _ptr(rows), K, _ptr(clearance), _ptr(nearest), _ptr(lowest), _ptr(knot),
+                                   threshold)
+        self._chk(rc, "clearance")
+        return dict(clearance=clearance, nearest=nearest, min_clearance=lowest, min_knot=knot, n_below=n)
+
+    def clearance_raw(self, cfg, scene_batch, layout, rows_ptr, n_knots, clearance_ptr, nearest_ptr, min_clearance_ptr,
+                      min_knot_ptr, threshold=0.0):
+        """Pointer-level form (rows / clearance / nearest / min_clearance / min_knot in device or host memory as
+        scene_batch.memory says: the `plan` rows of plan_scenes_raw and the output of resample_raw are measured where they
+        lie; clearance_ptr and nearest_ptr may be None); returns (rc, n_below)."""
+        n = C.c_int32(0)
+        rc = self.L.cilqr_clearance_rows_batch(self.h, C.byref(cfg) if cfg is not None else None, C.byref(scene_batch),
+                                               layout, rows_ptr, n_knots, clearance_ptr, nearest_ptr, min_clearance_ptr,
+                                               min_knot_ptr, C.c_double(threshold), C.byref(n))
+        return rc, int(n.value)
+
     def resample(self, rows, layout: int, queries, key: int = KEY_TIME):
         """DiscretizedTrajectory::EvaluateTime / EvaluateStation for a batch of trajectories on the GPU
         (cilqr_resample_rows_batch).  rows [B,K,F] in `layout` (ROWS_TRAJ / ROWS_PLAN / ROWS_COARSE); queries [M] -- one axis
@@ -949,6 +991,25 @@ def check_collisions(flat: dict, rows, layout: int, cfg: "DpConfig | None" = Non
     if rc != OK:
         raise CilqrError(rc, "in cilqr_check_collisions")
     return mask, int(first.value), int(n_hit.value)
+
+
+def clearance_rows(flat: dict, rows, layout: int, cfg: "DpConfig | None" = None):
+    """Polygon2d::DistanceTo from the two vehicle discs to the obstacles of one scene, for every knot of one trajectory,
+    through the C-ABI (cilqr_clearance_rows, host only).  `flat` = scene_io.flatten_scene(center, scene), rows [K,F] in
+    `layout` (ROWS_*).  Returns (clearance [K,4], nearest [K,4] int32 slots, min_clearance, min_knot)."""
+    cfg = cfg or default_dp_config()
+    rows = _f64(rows)
+    if rows.ndim != 2 or rows.shape[1] != ROWS_FIELDS.get(layout, rows.shape[1]):
+        raise ValueError(f"rows must be [K, {ROWS_FIELDS.get(layout)}]")
+    sc, keep = scene_struct(flat)
+    K = rows.shape[0]
+    clearance, nearest = np.zeros((K, CLEARANCE_FIELDS)), np.zeros((K, CLEARANCE_FIELDS), dtype=np.int32)
+    lowest, knot = C.c_double(0.0), C.c_int32(0)
+    rc = lib().cilqr_clearance_rows(C.byref(cfg), C.byref(sc), layout, rows.ctypes.data, K, clearance.ctypes.data,
+                                    nearest.ctypes.data, C.byref(lowest), C.byref(knot))
+    if rc != OK:
+        raise CilqrError(rc, "in cilqr_clearance_rows")
+    return clearance, nearest, float(lowest.value), int(knot.value)
 
 
 def resample_rows(rows, layout: int, queries, key: int = KEY_TIME) -> np.ndarray:

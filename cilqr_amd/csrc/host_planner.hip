@@ -2,13 +2,81 @@
 // cilqr_dp_plan wraps the header-only planner of include/cilqr/dp_planner.hpp (DpPlanner::Plan,
 // algorithm/planner/dp_planner.cpp:135-281 with ComputePathProfile, discrete_points_math.cc:27-176) for
 // callers that are not C++ (the ctypes tests, the scene generator); cilqr_check_collisions asks DpEnvironment::CollisionMask
-// about every knot of a trajectory (Environment::CheckOptimizationCollision, environment.cpp:92-111).  No device code in
-// this file.
+// about every knot of a trajectory (Environment::CheckOptimizationCollision, environment.cpp:92-111), cilqr_clearance_rows
+// asks DpEnvironment::Clearance (Polygon2d::DistanceTo, polygon2d.cpp:43-52).  No device code in this file.
+#include <limits>
 #include <vector>
 
 #include "../../include/cilqr.h"
 #include "../../include/cilqr/dp_planner.hpp"
 #include "collision.hpp"
+
+namespace {
+
+// what the two audits of one scene (cilqr_check_collisions, cilqr_clearance_rows) check about it, in this order around
+// their own arguments: the shape and the arrays it asks for, then the counts
+int check_scene_shape(const cilqr_scene& scene) {
+  if (scene.n_center < 2 || scene.n_static < 0 || scene.n_dynamic < 0) return CILQR_ERR_ARG;
+  if ((scene.n_static > 0 && (scene.static_points == nullptr || scene.static_counts == nullptr)) ||
+      (scene.n_dynamic > 0 && (scene.dynamic_polygon_points == nullptr || scene.dynamic_polygon_counts == nullptr ||
+                               scene.dynamic_trajectories == nullptr || scene.dynamic_trajectory_counts == nullptr)))
+    return CILQR_ERR_NULL;
+  return CILQR_OK;
+}
+int check_scene_counts(const cilqr_scene& scene) {
+  if (scene.n_static > CILQR_DP_MAX_STATIC || scene.n_dynamic > CILQR_DP_MAX_DYNAMIC) return CILQR_ERR_CAPACITY;
+  for (int o = 0; o < scene.n_static; ++o)
+    if (scene.static_counts[o] < 0) return CILQR_ERR_ARG;
+  for (int o = 0; o < scene.n_dynamic; ++o)
+    if (scene.dynamic_polygon_counts[o] < 0 || scene.dynamic_trajectory_counts[o] < 0) return CILQR_ERR_ARG;
+  for (int o = 0; o < scene.n_static; ++o)
+    if (scene.static_counts[o] > CILQR_DP_MAX_VERTICES) return CILQR_ERR_CAPACITY;
+  for (int o = 0; o < scene.n_dynamic; ++o)
+    if (scene.dynamic_polygon_counts[o] > CILQR_DP_MAX_VERTICES || scene.dynamic_trajectory_counts[o] > CILQR_DP_MAX_SAMPLES)
+      return CILQR_ERR_CAPACITY;
+  return CILQR_OK;
+}
+
+// the environment of a checked scene, and the slot of every obstacle it kept
+struct AuditScene {
+  cilqr::DpEnvironment env;
+  std::vector<int> static_slot, dynamic_slot;
+  AuditScene(const cilqr_dp_config& cfg, const cilqr_scene& scene) {
+    std::vector<std::array<double, 7>> center(scene.n_center);
+    for (int i = 0; i < scene.n_center; ++i)
+      for (int e = 0; e < 7; ++e) center[i][e] = scene.center[(size_t)i * 7 + e];
+    env = cilqr::DpEnvironment(cilqr::dp_config_of(cfg), cilqr::ReferenceLine(center));
+    size_t at = 0;
+    for (int o = 0; o < scene.n_static; ++o) {
+      std::vector<cilqr::DpPoint2> poly(scene.static_counts[o]);
+      for (auto& p : poly) {
+        p = cilqr::DpPoint2{scene.static_points[at * 2], scene.static_points[at * 2 + 1]};
+        ++at;
+      }
+      if (!poly.empty()) {   // no vertices: the slot is unused
+        env.AddStatic(poly);
+        static_slot.push_back(o);
+      }
+    }
+    size_t pa = 0, ta = 0;
+    for (int o = 0; o < scene.n_dynamic; ++o) {
+      const int m = scene.dynamic_polygon_counts[o], T = scene.dynamic_trajectory_counts[o];
+      std::vector<cilqr::DpPoint2> poly(m);
+      for (int k = 0; k < m; ++k) poly[k] = cilqr::DpPoint2{scene.dynamic_polygon_points[(pa + k) * 2], scene.dynamic_polygon_points[(pa + k) * 2 + 1]};
+      std::vector<std::array<double, 4>> traj(T);
+      for (int t = 0; t < T; ++t)
+        for (int e = 0; e < 4; ++e) traj[t][e] = scene.dynamic_trajectories[(ta + t) * 4 + e];
+      if (m > 0 && T > 0) {   // an obstacle without vertices or samples is never there
+        env.AddDynamic(poly, traj);
+        dynamic_slot.push_back(o);
+      }
+      pa += m;
+      ta += T;
+    }
+  }
+};
+
+}  // namespace
 
 extern "C" {
 
@@ -108,54 +176,16 @@ int cilqr_check_collisions(const cilqr_dp_config* cfg, const cilqr_scene* scene,
                            int32_t n_knots, double collision_buffer, uint8_t* mask, int32_t* first_hit, int32_t* n_hit) {
   if (cfg == nullptr || scene == nullptr || rows == nullptr || first_hit == nullptr || scene->center == nullptr)
     return CILQR_ERR_NULL;
-  if (scene->n_center < 2 || scene->n_static < 0 || scene->n_dynamic < 0) return CILQR_ERR_ARG;
-  if ((scene->n_static > 0 && (scene->static_points == nullptr || scene->static_counts == nullptr)) ||
-      (scene->n_dynamic > 0 && (scene->dynamic_polygon_points == nullptr || scene->dynamic_polygon_counts == nullptr ||
-                                scene->dynamic_trajectories == nullptr || scene->dynamic_trajectory_counts == nullptr)))
-    return CILQR_ERR_NULL;
+  if (int rc = check_scene_shape(*scene)) return rc;
   if (int rc = cilqr::check_audit_arguments(layout, n_knots, collision_buffer)) return rc;
-  if (scene->n_static > CILQR_DP_MAX_STATIC || scene->n_dynamic > CILQR_DP_MAX_DYNAMIC) return CILQR_ERR_CAPACITY;
-  for (int o = 0; o < scene->n_static; ++o)
-    if (scene->static_counts[o] < 0) return CILQR_ERR_ARG;
-  for (int o = 0; o < scene->n_dynamic; ++o)
-    if (scene->dynamic_polygon_counts[o] < 0 || scene->dynamic_trajectory_counts[o] < 0) return CILQR_ERR_ARG;
-  for (int o = 0; o < scene->n_static; ++o)
-    if (scene->static_counts[o] > CILQR_DP_MAX_VERTICES) return CILQR_ERR_CAPACITY;
-  for (int o = 0; o < scene->n_dynamic; ++o)
-    if (scene->dynamic_polygon_counts[o] > CILQR_DP_MAX_VERTICES || scene->dynamic_trajectory_counts[o] > CILQR_DP_MAX_SAMPLES)
-      return CILQR_ERR_CAPACITY;
+  if (int rc = check_scene_counts(*scene)) return rc;
 
-  std::vector<std::array<double, 7>> center(scene->n_center);
-  for (int i = 0; i < scene->n_center; ++i)
-    for (int e = 0; e < 7; ++e) center[i][e] = scene->center[(size_t)i * 7 + e];
-  const cilqr::ReferenceLine ref(center);
-  cilqr::DpEnvironment env(cilqr::dp_config_of(*cfg), ref);
-  size_t at = 0;
-  for (int o = 0; o < scene->n_static; ++o) {
-    std::vector<cilqr::DpPoint2> poly(scene->static_counts[o]);
-    for (auto& p : poly) {
-      p = cilqr::DpPoint2{scene->static_points[at * 2], scene->static_points[at * 2 + 1]};
-      ++at;
-    }
-    if (!poly.empty()) env.AddStatic(poly);   // no vertices: the slot is unused
-  }
-  size_t pa = 0, ta = 0;
-  for (int o = 0; o < scene->n_dynamic; ++o) {
-    const int m = scene->dynamic_polygon_counts[o], T = scene->dynamic_trajectory_counts[o];
-    std::vector<cilqr::DpPoint2> poly(m);
-    for (int k = 0; k < m; ++k) poly[k] = cilqr::DpPoint2{scene->dynamic_polygon_points[(pa + k) * 2], scene->dynamic_polygon_points[(pa + k) * 2 + 1]};
-    std::vector<std::array<double, 4>> traj(T);
-    for (int t = 0; t < T; ++t)
-      for (int e = 0; e < 4; ++e) traj[t][e] = scene->dynamic_trajectories[(ta + t) * 4 + e];
-    if (m > 0) env.AddDynamic(poly, traj);    // (an obstacle without samples is dropped there)
-    pa += m;
-    ta += T;
-  }
+  const AuditScene audit(*cfg, *scene);
   const cilqr::RowLayout L = cilqr::row_layout(layout);
   int first = -1, count = 0;
   for (int k = 0; k < n_knots; ++k) {
     const double* r = rows + (size_t)k * L.fields;
-    const unsigned bits = env.CollisionMask(r[L.time], r[L.x], r[L.y], r[L.theta], collision_buffer);
+    const unsigned bits = audit.env.CollisionMask(r[L.time], r[L.x], r[L.y], r[L.theta], collision_buffer);
     if (mask) mask[k] = (uint8_t)bits;
     if (bits != 0u) {
       if (first < 0) first = k;
@@ -164,6 +194,39 @@ int cilqr_check_collisions(const cilqr_dp_config* cfg, const cilqr_scene* scene,
   }
   *first_hit = first;
   if (n_hit) *n_hit = count;
+  return CILQR_OK;
+}
+
+int cilqr_clearance_rows(const cilqr_dp_config* cfg, const cilqr_scene* scene, int32_t layout, const double* rows,
+                         int32_t n_knots, double* clearance, int32_t* nearest, double* min_clearance, int32_t* min_knot) {
+  if (cfg == nullptr || scene == nullptr || rows == nullptr || clearance == nullptr || min_clearance == nullptr ||
+      min_knot == nullptr || scene->center == nullptr)
+    return CILQR_ERR_NULL;
+  if (int rc = check_scene_shape(*scene)) return rc;
+  if (int rc = cilqr::check_audit_arguments(layout, n_knots, 0.0)) return rc;
+  if (int rc = check_scene_counts(*scene)) return rc;
+
+  const AuditScene audit(*cfg, *scene);
+  const cilqr::RowLayout L = cilqr::row_layout(layout);
+  double lowest = std::numeric_limits<double>::infinity();
+  int at = -1;
+  for (int k = 0; k < n_knots; ++k) {
+    const double* r = rows + (size_t)k * L.fields;
+    const cilqr::DpEnvironment::ClearanceRow row = audit.env.Clearance(r[L.time], r[L.x], r[L.y], r[L.theta]);
+    for (int c = 0; c < CILQR_CLEARANCE_FIELDS; ++c) {
+      clearance[(size_t)k * CILQR_CLEARANCE_FIELDS + c] = row.clearance[c];
+      if (nearest) {   // the environment counts the obstacles it kept; the caller counts slots
+        const std::vector<int>& slot_of = (c & 1) ? audit.dynamic_slot : audit.static_slot;
+        nearest[(size_t)k * CILQR_CLEARANCE_FIELDS + c] = row.nearest[c] < 0 ? -1 : slot_of[row.nearest[c]];
+      }
+      if (row.clearance[c] < lowest) {
+        lowest = row.clearance[c];
+        at = k;
+      }
+    }
+  }
+  *min_clearance = lowest;
+  *min_knot = at;
   return CILQR_OK;
 }
 

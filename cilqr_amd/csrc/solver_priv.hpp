@@ -260,6 +260,10 @@ struct cilqr_solver {
   // their way to the device, the staging of HOST rows / pairs and of HOST results
   cilqr::pinned_mem fr_tab_host;
   cilqr::dev_mem fr_tab, fr_in, fr_out;
+  // cilqr_clearance_rows_batch (clearance_batch.hip), grown likewise: the count of scenes below the threshold and its way
+  // back, the staging of HOST scenes and rows, of HOST results
+  cilqr::pinned_mem cl_tab_host;
+  cilqr::dev_mem cl_tab, cl_in, cl_out;
 };
 
 namespace cilqr {

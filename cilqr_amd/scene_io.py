@@ -23,6 +23,8 @@ cilqr_build_corridors / cilqr_lane_constraints.
 from __future__ import annotations
 
 import bisect
+import ctypes
+import ctypes.util
 import dataclasses
 import math
 import struct
@@ -328,6 +330,119 @@ def environment_collisions(center: np.ndarray, scene: Scene, cfg, times, poses, 
                 mask[k] |= 4 << shift
     hit = np.flatnonzero(mask)
     return mask, (int(hit[0]) if len(hit) else -1), int(len(hit))
+
+
+# hypot is the C library's own: math.hypot is Python's algorithm, which is not glibc's in the last bit for every argument
+_LIBM = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+_LIBM.hypot.restype = ctypes.c_double
+_LIBM.hypot.argtypes = [ctypes.c_double] * 2
+_hypot = _LIBM.hypot
+
+
+def _std_min(a: float, b: float) -> float:
+    return b if b < a else a      # std::min: a NaN second argument is never taken
+
+
+def _std_max(a: float, b: float) -> float:
+    return b if a < b else a
+
+
+def _normalised_polygon(q) -> list:
+    """Polygon2d::BuildFromPoints (polygon2d.cpp:206-234) on [n,2] vertices: the list of (x, y), reversed as a whole when
+    the area sum of CrossProd(p0, p[i-1], p[i]) over i = 1 .. n-1 is negative."""
+    pts = [(float(x), float(y)) for x, y in np.asarray(q, float).reshape(-1, 2)]
+    x0, y0 = pts[0]
+    area = 0.0
+    for (ax, ay), (bx, by) in zip(pts[:-1], pts[1:]):
+        area += (ax - x0) * (by - y0) - (ay - y0) * (bx - x0)
+    return pts[::-1] if area < 0 else pts
+
+
+def polygon_distance(q, px: float, py: float, normalise: bool = True) -> float:
+    """Polygon2d::DistanceTo(Vec2d) (polygon2d.cpp:43-52) from (px, py) to the polygon of [n,2] vertices, n >= 1: 0.0
+    inside (bounding box, then the crossing count), else the std::min over the edges, in order, of
+    LineSegment2d::DistanceTo (line_segment2d.cpp:38-75).  Plain Python floats and the C library's hypot, every operation
+    rounded once.  normalise = False measures the vertex array as given (what a test compares the rule against)."""
+    pts = _normalised_polygon(q) if normalise else [(float(x), float(y)) for x, y in np.asarray(q, float).reshape(-1, 2)]
+    n = len(pts)
+    min_x = max_x = pts[0][0]
+    min_y = max_y = pts[0][1]
+    for x, y in pts:      # the box of the reversed array, by std::min / std::max from its first vertex
+        min_x, max_x, min_y, max_y = _std_min(min_x, x), _std_max(max_x, x), _std_min(min_y, y), _std_max(max_y, y)
+    if not (px < min_x or px > max_x or py < min_y or py > max_y):
+        crossings, j = 0, n - 1
+        for i in range(n):
+            (xi, yi), (xj, yj) = pts[i], pts[j]
+            if (yi > py) != (yj > py):
+                side = (xi - px) * (yj - py) - (xj - px) * (yi - py)
+                if (side > 0.0) if yi < yj else (side < 0.0):
+                    crossings += 1
+            j = i
+        if crossings & 1:
+            return 0.0
+    d = math.inf
+    for i in range(n):
+        (sx, sy), (ex, ey) = pts[i], pts[0 if i >= n - 1 else i + 1]
+        dx, dy = ex - sx, ey - sy
+        length = _hypot(dx, dy)
+        ux, uy = (0.0, 0.0) if length <= K_MATH_EPS else (dx / length, dy / length)
+        x0, y0 = px - sx, py - sy
+        if length <= K_MATH_EPS:
+            e = _hypot(x0, y0)
+        else:
+            proj = x0 * ux + y0 * uy
+            if proj <= 0.0:
+                e = _hypot(x0, y0)
+            elif proj >= length:
+                e = _hypot(px - ex, py - ey)
+            else:
+                e = abs(x0 * uy - y0 * ux)
+        d = _std_min(d, e)
+    return d
+
+
+def environment_clearance(center: np.ndarray, scene: Scene, cfg, times, poses, ego_trig=None, obstacle_trig=None) -> tuple:
+    """How far the two vehicle discs stay from the obstacles at every knot (include/cilqr.h, "clearance"): (clearance [K,4]
+    = rear disc / static, rear / dynamic, front / static, front / dynamic; nearest [K,4] int32 = index of the obstacle in
+    scene.static / scene.dynamic, -1: none; min_clearance; min_knot).  times [K], poses [K,3] = x, y, theta; `center` is
+    taken for the sake of the call's shape and not read (the road barriers are no column).  A dynamic obstacle is present
+    and placed as in environment_collisions.  ego_trig / obstacle_trig(angle) -> (cos, sin): the math module's by default;
+    a test hands in another implementation's (the device's) for the vehicle heading / the obstacle placement."""
+    trig = lambda a: (math.cos(a), math.sin(a))
+    ego_trig, obstacle_trig = ego_trig or trig, obstacle_trig or trig
+    radius, r2x, f2x = vehicle_discs(cfg)
+    K = len(times)
+    clearance = np.full((K, 4), math.inf)
+    nearest = np.full((K, 4), -1, dtype=np.int32)
+    lowest, knot = math.inf, -1
+    for k, (t, (x, y, th)) in enumerate(zip(times, poses)):
+        t, x, y, th = float(t), float(x), float(y), float(th)
+        ct, st = ego_trig(th)
+        discs = ((x + r2x * ct, y + r2x * st), (x + f2x * ct, y + f2x * st))
+        kinds = ([(o, np.asarray(p, float).reshape(-1, 2)) for o, p in enumerate(scene.static) if len(p) >= 1], [])
+        for o, d in enumerate(scene.dynamic):
+            tt = d.trajectory[:, 0]
+            if len(d.polygon) < 1 or len(tt) < 1 or tt[0] > t or tt[-1] < t:
+                continue
+            i = 0
+            while i < len(tt) and not (t < tt[i]):      # first sample with t < time; past the end the last
+                i += 1
+            _, ox, oy, oth = (float(v) for v in d.trajectory[min(i, len(tt) - 1)])
+            c, s = obstacle_trig(oth)      # Pose::transform (pose.h:40-46): x + rx cos - ry sin, in that order
+            kinds[1].append((o, [(ox + float(vx) * c - float(vy) * s, oy + float(vx) * s + float(vy) * c) for vx, vy in d.polygon]))
+        for disc, (cx, cy) in enumerate(discs):
+            for kind, polygons in enumerate(kinds):
+                best, slot = math.inf, -1
+                for o, q in polygons:
+                    dist = polygon_distance(q, cx, cy)
+                    if dist < best:
+                        best, slot = dist, o
+                clearance[k, 2 * disc + kind] = best - radius
+                nearest[k, 2 * disc + kind] = slot
+        for v in clearance[k]:
+            if v < lowest:
+                lowest, knot = float(v), k
+    return clearance, nearest, lowest, knot
 
 
 def road_barriers(center: np.ndarray) -> tuple:

@@ -710,6 +710,68 @@ int cilqr_frenet_rows_batch(cilqr_handle h, const double* center, int32_t n_cent
 int cilqr_cartesian_points_batch(cilqr_handle h, const double* center, int32_t n_center, int32_t n, const double* sl,
                                  double* xyt, int32_t memory);
 
+/* ---- clearance: how close every knot of a trajectory comes to the obstacles of its scene (Polygon2d::DistanceTo(Vec2d),
+ * algorithm/math/polygon2d.cpp:43-52, over LineSegment2d::DistanceTo, line_segment2d.cpp:38-75); one scene on the host ----
+ * The audit above answers yes / no at one buffer, and with the reference's HasOverlap(Box2d): a polygon vertex in the disc's
+ * square or a corner of the square in the polygon -- a long edge through the square is not seen.  This is the continuous
+ * counterpart, the number a caller ranks plans by or chooses a collision_buffer from.  Per knot:
+ *   disc centres   the audit's: rear x + r2x cos(theta), y + r2x sin(theta); front the same with f2x; radius, r2x, f2x from
+ *                  cfg as for cilqr_check_collisions.
+ *   polygon        n >= 1 vertices, normalised as Polygon2d::BuildFromPoints does (polygon2d.cpp:206-234):
+ *                  area = sum over i = 1 .. n-1 of CrossProd(p0, p[i-1], p[i]) = (p[i-1] - p0) x (p[i] - p0); if area < 0 the
+ *                  whole vertex array is reversed.  Edge i is (p[i], p[Next(i)]), Next(n-1) = 0: n = 1 gives one degenerate
+ *                  edge, n = 2 two.  An edge carries the constructor's arithmetic: length = hypot(dx, dy), unit vector
+ *                  (dx / length, dy / length), or (0, 0) when length <= 1e-10.
+ *   distance       from a disc centre c to a polygon: d = 0.0 if IsPointIn(c) (the bounding box first, then the crossing
+ *                  count, polygon2d.cpp:120-140).  Otherwise d starts at +inf and is updated edge by edge in order with
+ *                  std::min(d, edge.DistanceTo(c)), that is (e < d) ? e : d -- a NaN is never taken.  edge.DistanceTo: with
+ *                  x0, y0 = c - start: length <= 1e-10: hypot(x0, y0); proj = x0 ux + y0 uy; proj <= 0: hypot(x0, y0);
+ *                  proj >= length: hypot(c - end); else |x0 uy - y0 ux|.  Every operation is rounded once (no fused
+ *                  multiply-add), as the library is built.
+ *   static column  the slots with a count >= 1 in slot order: best = +inf, slot = -1; a slot replaces them only when its
+ *                  d < best (the first of equals wins).  Output: best - radius, one rounded subtraction (+inf stays +inf),
+ *                  and the slot.
+ *   dynamic column the same over the dynamic slots present at the knot's time.  Presence and the choice of the sample are
+ *                  exactly those of cilqr_check_collisions (no epsilon; the first sample with t < time[k]; past the end the
+ *                  last), the placement is in Pose::transform order; the placed polygon is then normalised and measured as
+ *                  above.
+ * Per trajectory: min_clearance = the smallest of the K x 4 values under the same strict `<` from +inf; min_knot = the first
+ * knot whose row attains it, -1 if every value is +inf.  A negative clearance is a disc that reaches into (or, at -radius,
+ * whose centre lies inside) a polygon.
+ * The road barriers are deliberately not a column: they are a sampled point set, not an outline, and the margins to the
+ * road edges are left_bound - lateral and lateral + right_bound of cilqr_frenet_rows[_batch].
+ * Non-finite rows are no error: the arithmetic decides (a NaN centre is in no polygon and no NaN distance is taken, so its
+ * values are +inf; a NaN vertex only ever removes its own polygon's edges from the minimum).
+ *   rows [n_knots][fields] in CILQR_ROWS_TRAJ / _PLAN / _COARSE: only time, x, y, theta are read
+ *   clearance [n_knots][CILQR_CLEARANCE_FIELDS]; nearest [n_knots][CILQR_CLEARANCE_FIELDS] slots, optional (NULL to skip)
+ * CILQR_ERR_NULL; CILQR_ERR_ARG for an unknown layout (CILQR_ROWS_POINTS included: it has no time or heading), n_knots < 1,
+ * n_center < 2, a negative count; CILQR_ERR_CAPACITY beyond the CILQR_DP_MAX_* limits -- the checks of
+ * cilqr_check_collisions.  C++ callers use DpEnvironment::Clearance of include/cilqr/dp_planner.hpp directly. */
+#define CILQR_CLEARANCE_FIELDS 4   /* rear_static, rear_dynamic, front_static, front_dynamic */
+int cilqr_clearance_rows(const cilqr_dp_config* cfg, const cilqr_scene* scene, int32_t layout, const double* rows,
+                         int32_t n_knots, double* clearance /* [K][4] */, int32_t* nearest /* [K][4], optional */,
+                         double* min_clearance, int32_t* min_knot);
+/* ---- the same for B scenes per call, on the GPU (kernels_clearance.hip; additive, ABI 7) ----
+ * One workgroup per scene.  The arithmetic is the host call's except for the vehicle heading, which goes through the DP
+ * kernels' sin / cos, and the obstacle placement, which goes through the device library's cos / sin (cilqr_device_math fn
+ * 7 / 8): a distance differs from the host's by rounding of the centres and the placed vertices only (distance is
+ * 1-Lipschitz in both), hypot follows the C library's evaluation for lengths in metres.  A scene's result does not depend
+ * on the batch around it or on unused slots.
+ *   rows          [B][n_knots][fields]             (memory as scenes->memory, like the four arrays below)
+ *   clearance     [B][n_knots][4], optional;  nearest [B][n_knots][4], optional
+ *   min_clearance [B];  min_knot [B]
+ *   *n_below (HOST, optional): the scenes with min_clearance < threshold
+ * Checked before anything is launched: the checks of cilqr_check_collisions_batch (CILQR_ERR_NULL, _ARG, _CAPACITY, _STATE),
+ * and CILQR_ERR_ARG for a non-finite threshold with n_below given.  With DEVICE arrays the counts are checked in the
+ * kernel: such a scene gets min_knot -2, a NaN min_clearance and NaN rows (nearest -1), the others are unaffected.  Runs on
+ * the handle's stream and waits for that stream only; DEVICE arrays need no work space beyond the count, HOST arrays are
+ * staged in blocks that belong to the handle and grow to the largest call. */
+int cilqr_clearance_rows_batch(cilqr_handle h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes,
+                               int32_t layout, const double* rows, int32_t n_knots,
+                               double* clearance /* [B][K][4], optional */, int32_t* nearest /* [B][K][4], optional */,
+                               double* min_clearance /* [B] */, int32_t* min_knot /* [B] */,
+                               double threshold, int32_t* n_below /* HOST, optional */);
+
 /* ---- TrajectoryPlanner::Plan for B scenes per call (trajectory_planner.cpp:28-162) ----
  * scene batch -> cilqr_dp_plan_batch -> cilqr_scene_points_batch (at the time column the planner produced, with
  * corridor_cfg->is_multiple_sample and the worst-case max_points) -> cilqr_build_corridors (the cmax of the handle's

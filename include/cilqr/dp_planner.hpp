@@ -11,7 +11,8 @@
 //   Environment             algorithm/utils/environment.cpp: set_reference :20-43 (road barriers every 0.1 m),
 //                           CheckStaticCollision :45-80, CheckDynamicCollision :113-130, CheckOptimizationCollision :92-111
 //   geometry                Polygon2d::HasOverlap(Box2d) polygon2d.cpp:150-164, Polygon2d::IsPointIn :120-140,
-//                           Box2d::IsPointIn box2d.cpp:123-129, VehicleParam disc positions vehicle_param.h:76-95
+//                           Box2d::IsPointIn box2d.cpp:123-129, VehicleParam disc positions vehicle_param.h:76-95,
+//                           Polygon2d::DistanceTo(Vec2d) :43-52 over LineSegment2d::DistanceTo line_segment2d.cpp:61-75
 //
 // Every number is produced by the reference's expressions in the reference's order (the DP compares costs with
 // '<', so a different rounding could pick another cell); what differs is the bookkeeping around them: the point count
@@ -204,11 +205,21 @@ class DpEnvironment {
   };
 
   DpEnvironment() = default;
-  DpEnvironment(const DpConfig& cfg, const ReferenceLine& ref) : cfg_(cfg), ref_(ref) {
+  // the two collision discs of the vehicle: their radius and the offsets of the rear / front centre along the heading
+  struct Discs {
+    double radius, rear_x, front_x;
+  };
+  static Discs DiscsOf(const DpConfig& cfg) {
     const double length = cfg.wheel_base + cfg.rear_hang_length + cfg.front_hang_length;   // vehicle_param.h:80-85
-    radius_ = std::hypot(0.25 * length, 0.5 * cfg.width);
-    r2x_ = 0.25 * length - cfg.rear_hang_length;
-    f2x_ = 0.75 * length - cfg.rear_hang_length;
+    return Discs{std::hypot(0.25 * length, 0.5 * cfg.width), 0.25 * length - cfg.rear_hang_length,
+                 0.75 * length - cfg.rear_hang_length};
+  }
+
+  DpEnvironment(const DpConfig& cfg, const ReferenceLine& ref) : cfg_(cfg), ref_(ref) {
+    const Discs discs = DiscsOf(cfg);
+    radius_ = discs.radius;
+    r2x_ = discs.rear_x;
+    f2x_ = discs.front_x;
     // set_reference, environment.cpp:20-43: both road barriers sampled every 0.1 m, sorted by x
     constexpr double kSampleStep = 0.1;
     const double start_s = ref_.points().front().s, back_s = ref_.points().back().s;
@@ -286,7 +297,87 @@ class DpEnvironment {
     return mask;
   }
 
+  // How far each disc stays from the obstacles (include/cilqr.h, "clearance"): Polygon2d::DistanceTo(Vec2d)
+  // (polygon2d.cpp:43-52) from the disc centre to every polygon, minus the disc radius.  Columns: rear disc / static,
+  // rear / dynamic, front / static, front / dynamic.  nearest = the obstacle that decided, counted in the order of the
+  // AddStatic / AddDynamic calls that kept one (-1: no obstacle of that kind, clearance +inf); the first of equals wins.
+  struct ClearanceRow {
+    double clearance[4];
+    int nearest[4];
+  };
+  ClearanceRow Clearance(double time, double x, double y, double theta) const {
+    const double ct = std::cos(theta), st = std::sin(theta);
+    const double cx[2] = {x + r2x_ * ct, x + f2x_ * ct}, cy[2] = {y + r2x_ * st, y + f2x_ * st};   // rear, front
+    const double inf = std::numeric_limits<double>::infinity();
+    double best[4] = {inf, inf, inf, inf};
+    ClearanceRow row;
+    for (int c = 0; c < 4; ++c) row.nearest[c] = -1;
+    auto measure = [&](const Poly& q, int column, int index) {
+      const Outline o(q);
+      for (int disc = 0; disc < 2; ++disc) {
+        const double d = o.DistanceTo(cx[disc], cy[disc]);
+        if (d < best[2 * disc + column]) {
+          best[2 * disc + column] = d;
+          row.nearest[2 * disc + column] = index;
+        }
+      }
+    };
+    for (size_t i = 0; i < statics_.size(); ++i) measure(statics_[i], 0, (int)i);
+    for (size_t i = 0; i < dynamics_.size(); ++i) {
+      const Dynamic& d = dynamics_[i];
+      if (d.time.front() > time || d.time.back() < time) continue;   // the rule of DynamicCollision below
+      size_t s = 0;
+      while (s < d.time.size() && !(time < d.time[s])) ++s;
+      if (s >= d.time.size()) s = d.time.size() - 1;
+      measure(d.poly[s], 1, (int)i);
+    }
+    for (int c = 0; c < 4; ++c) row.clearance[c] = best[c] - radius_;
+    return row;
+  }
+
  private:
+  // A polygon as Polygon2d::BuildFromPoints leaves it (polygon2d.cpp:206-234): the vertices reversed when the area sum
+  // is negative, edge i from vertex i to vertex Next(i) with LineSegment2d's constructor arithmetic
+  // (line_segment2d.cpp:40-49): length = hypot(dx, dy), unit vector (0, 0) when length <= 1e-10.
+  struct Outline {
+    struct Edge {
+      double sx, sy, ux, uy, length, ex, ey;
+    };
+    Poly q;
+    std::vector<Edge> edges;
+    explicit Outline(const Poly& p) {
+      std::vector<DpPoint2> v = p.pts;
+      const int n = (int)v.size();
+      double area = 0.0;
+      for (int i = 1; i < n; ++i)   // CrossProd(p0, p[i-1], p[i]), math_utils.cpp:28-31
+        area += (v[i - 1].x - v[0].x) * (v[i].y - v[0].y) - (v[i - 1].y - v[0].y) * (v[i].x - v[0].x);
+      if (area < 0) std::reverse(v.begin(), v.end());
+      q = MakePoly(v);   // the box is taken after the reversal (polygon2d.cpp:246-256)
+      edges.resize(n);
+      for (int i = 0; i < n; ++i) {
+        const DpPoint2 &a = q.pts[i], &b = q.pts[i >= n - 1 ? 0 : i + 1];
+        const double dx = b.x - a.x, dy = b.y - a.y;
+        const double length = std::hypot(dx, dy);
+        const bool point = length <= dp_detail::kGeomEps;
+        edges[i] = Edge{a.x, a.y, point ? 0.0 : dx / length, point ? 0.0 : dy / length, length, b.x, b.y};
+      }
+    }
+    static double EdgeDistance(const Edge& e, double px, double py) {   // LineSegment2d::DistanceTo, line_segment2d.cpp:61-75
+      const double x0 = px - e.sx, y0 = py - e.sy;
+      if (e.length <= dp_detail::kGeomEps) return std::hypot(x0, y0);
+      const double proj = x0 * e.ux + y0 * e.uy;
+      if (proj <= 0.0) return std::hypot(x0, y0);
+      if (proj >= e.length) return std::hypot(px - e.ex, py - e.ey);
+      return std::abs(x0 * e.uy - y0 * e.ux);
+    }
+    double DistanceTo(double px, double py) const {   // polygon2d.cpp:43-52
+      if (PolyHasPoint(q, px, py)) return 0.0;
+      double d = std::numeric_limits<double>::infinity();
+      for (const Edge& e : edges) d = std::min(d, EdgeDistance(e, px, py));
+      return d;
+    }
+  };
+
   static Poly MakePoly(const std::vector<DpPoint2>& p) {
     Poly q;
     q.pts = p;
