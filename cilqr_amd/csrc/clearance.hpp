@@ -15,11 +15,9 @@ struct ClearanceParams {
   RowLayout rows;
 };
 
-// One workgroup per scene of the batch arrays.  clearance [B][K][4] and nearest [B][K][4] may be null; n_below (one int,
-// zeroed by the caller) += the scenes with min_clearance < threshold.
-void launch_clearance(const ClearanceParams& P, int n_scenes, const double* rows, const double* static_points,
-                      const int* static_counts, const double* dyn_poly, const int* dyn_poly_counts, const double* dyn_traj,
-                      const int* dyn_traj_counts, double* clearance, int* nearest, double* min_clearance, int* min_knot,
-                      int* n_below, hipStream_t st);
+// One workgroup per scene of `dv`, the batch with its arrays on the device.  clearance [B][K][4] and nearest [B][K][4] may
+// be null; n_below (one int, zeroed by the caller) += the scenes with min_clearance < threshold.
+void launch_clearance(const ClearanceParams& P, const cilqr_scene_batch& dv, const double* rows, double* clearance,
+                      int* nearest, double* min_clearance, int* min_knot, int* n_below, hipStream_t st);
 
 }  // namespace cilqr

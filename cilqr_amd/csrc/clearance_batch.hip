@@ -4,8 +4,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "audit_batch.hpp"
 #include "clearance.hpp"
-#include "scene_batch.hpp"
 
 using namespace cilqr;
 
@@ -17,13 +17,10 @@ extern "C" int cilqr_clearance_rows_batch(cilqr_handle h, const cilqr_dp_config*
       min_knot == nullptr || scenes->center == nullptr)
     return CILQR_ERR_NULL;
   const cilqr_scene_batch& sb = *scenes;
-  if (int rc = check_scene_batch(sb)) return rc;
-  if (int rc = check_audit_arguments(layout, n_knots, 0.0)) return rc;
+  if (int rc = check_audit_batch(sb, layout, n_knots, 0.0)) return rc;
   if (n_below != nullptr && !std::isfinite(threshold)) return CILQR_ERR_ARG;
-  if (beyond_limits(sb, n_knots)) return CILQR_ERR_CAPACITY;
-  if (solves_in_flight(h)) return CILQR_ERR_STATE;
+  if (int rc = check_audit_admissible(h, sb, n_knots)) return rc;
   const bool on_host = sb.memory == CILQR_MEM_HOST;
-  if (on_host && !host_counts_valid(sb)) return CILQR_ERR_ARG;
 
   const DpEnvironment::Discs discs = DpEnvironment::DiscsOf(dp_config_of(*cfg));
   ClearanceParams P;
@@ -31,24 +28,23 @@ extern "C" int cilqr_clearance_rows_batch(cilqr_handle h, const cilqr_dp_config*
   P.radius = discs.radius; P.r2x = discs.rear_x; P.f2x = discs.front_x;
   P.threshold = threshold;
   P.n_knots = n_knots;
-  P.max_static = sb.max_static; P.max_dynamic = sb.max_dynamic; P.max_vertices = sb.max_vertices; P.max_samples = sb.max_samples;
+  scene_limits_into(&P, sb);
   P.rows = row_layout(layout);
 
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = h->stream;
   const size_t B = (size_t)sb.batch, K = (size_t)n_knots;
   // ---- work space of the handle (grown, never shrunk): the count; HOST arrays: one block in, one block out
-  block_layout l_tab, l_in, l_out;
+  block_layout l_tab, l_out;
   const slot s_count = l_tab.add(4);
-  const slot s_rows = l_in.add(B * K * (size_t)P.rows.fields * 8);
-  const SceneImage im(l_in, sb);
+  const AuditInput in(sb, n_knots, P.rows);
   const slot s_clear = l_out.add(clearance ? B * K * CILQR_CLEARANCE_FIELDS * 8 : 0);
   const slot s_near = l_out.add(nearest ? B * K * CILQR_CLEARANCE_FIELDS * 4 : 0);
   const slot s_min = l_out.add(B * 8), s_knot = l_out.add(B * 4);
   HIP_TRY(h->cl_tab_host.grow(l_tab.bytes() + 256));
   HIP_TRY(h->cl_tab.grow(l_tab.bytes() + 256, &h->grown_bytes));
   if (on_host) {
-    HIP_TRY(h->cl_in.grow(l_in.bytes() + 256, &h->grown_bytes));
+    HIP_TRY(h->cl_in.grow(in.l.bytes() + 256, &h->grown_bytes));
     HIP_TRY(h->cl_out.grow(l_out.bytes() + 256, &h->grown_bytes));
   }
   int* d_count = s_count.in<int>(h->cl_tab.as<char>());
@@ -60,18 +56,13 @@ extern "C" int cilqr_clearance_rows_batch(cilqr_handle h, const cilqr_dp_config*
   int *d_near = nearest, *d_knot = min_knot;
   char* bo = h->cl_out.as<char>();
   if (on_host) {
-    char* bi = h->cl_in.as<char>();
-    if (int rc = copy_in(bi, s_rows, rows, st)) return rc;
-    if (int rc = im.upload(sb, bi, st, &dv)) return rc;
-    d_rows = s_rows.in<const double>(bi);
+    if (int rc = in.upload(sb, rows, h->cl_in.as<char>(), st, &d_rows, &dv)) return rc;
     if (clearance) d_clear = s_clear.in<double>(bo);
     if (nearest) d_near = s_near.in<int>(bo);
     d_min = s_min.in<double>(bo);
     d_knot = s_knot.in<int>(bo);
   }
-  launch_clearance(P, sb.batch, d_rows, dv.static_points, dv.static_counts, dv.dynamic_polygon_points,
-                   dv.dynamic_polygon_counts, dv.dynamic_trajectories, dv.dynamic_trajectory_counts, d_clear, d_near, d_min,
-                   d_knot, d_count, st);
+  launch_clearance(P, dv, d_rows, d_clear, d_near, d_min, d_knot, d_count, st);
   HIP_TRY(hipGetLastError());
   if (on_host) {
     if (int rc = copy_out(clearance, bo, s_clear, st)) return rc;
@@ -79,9 +70,5 @@ extern "C" int cilqr_clearance_rows_batch(cilqr_handle h, const cilqr_dp_config*
     if (int rc = copy_out(min_clearance, bo, s_min, st)) return rc;
     if (int rc = copy_out(min_knot, bo, s_knot, st)) return rc;
   }
-  int* count_host = s_count.in<int>(h->cl_tab_host.as<char>());
-  HIP_TRY(hipMemcpyAsync(count_host, d_count, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));   // this stream alone: solves on other handles go on
-  if (n_below) *n_below = *count_host;
-  return CILQR_OK;
+  return wait_and_fetch_count(d_count, s_count.in<int>(h->cl_tab_host.as<char>()), st, n_below);
 }

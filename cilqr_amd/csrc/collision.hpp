@@ -1,14 +1,13 @@
-// Private to cilqr_amd/csrc: what the two collision audits (cilqr_check_collisions in host_planner.hip,
-// cilqr_check_collisions_batch in collision_batch.hip) and kernels_collision.hip share -- where a row layout keeps the
-// pose, the checks on the scalar arguments, the parameters of a launch and the launch function.  Every pointer of the
-// launch is device memory; nothing here synchronises.
+// Private to cilqr_amd/csrc: what the audits of one scene (host_planner.hip), the batched ones (collision_batch.hip,
+// clearance_batch.hip) and kernels_collision.hip share -- where a row layout keeps the pose, the checks on the scalar
+// arguments, the parameters of a launch and the launch function.  Every pointer of the launch is device memory; nothing
+// here synchronises.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "../../include/cilqr.h"
-#include "../../include/cilqr/dp_planner.hpp"
 
 namespace cilqr {
 
@@ -33,18 +32,6 @@ inline int check_audit_arguments(int layout, int n_knots, double collision_buffe
   return CILQR_OK;
 }
 
-inline DpConfig dp_config_of(const cilqr_dp_config& c) {
-  DpConfig d;
-  d.tf = c.tf; d.delta_t = c.delta_t; d.dp_nominal_velocity = c.dp_nominal_velocity; d.dp_w_obstacle = c.dp_w_obstacle;
-  d.dp_w_lateral = c.dp_w_lateral; d.dp_w_lateral_change = c.dp_w_lateral_change;
-  d.dp_w_lateral_velocity_change = c.dp_w_lateral_velocity_change;
-  d.dp_w_longitudinal_velocity_bias = c.dp_w_longitudinal_velocity_bias;
-  d.dp_w_longitudinal_velocity_change = c.dp_w_longitudinal_velocity_change;
-  d.front_hang_length = c.front_hang_length; d.wheel_base = c.wheel_base; d.rear_hang_length = c.rear_hang_length;
-  d.width = c.width; d.max_velocity = c.max_velocity;
-  return d;
-}
-
 // what a launch shares between its scenes: the vehicle's discs with the buffer already in the half side (DpEnvironment:
 // disc_radius() + collision_buffer, added on the host as CollisionMask adds it), the x-sorted barrier table, the rows
 struct CollisionParams {
@@ -55,11 +42,9 @@ struct CollisionParams {
   const double* barrier;   // [n_barrier][2], read through L2
 };
 
-// One workgroup per scene of the batch arrays.  mask [B][K] and n_hit [B] may be null; n_colliding (one int, zeroed by
-// the caller) += the scenes with first_hit >= 0.
-void launch_check_collisions(const CollisionParams& P, int n_scenes, const double* rows, const double* static_points,
-                             const int* static_counts, const double* dyn_poly, const int* dyn_poly_counts,
-                             const double* dyn_traj, const int* dyn_traj_counts, uint8_t* mask, int* first_hit, int* n_hit,
-                             int* n_colliding, hipStream_t st);
+// One workgroup per scene of `dv`, the batch with its arrays on the device.  mask [B][K] and n_hit [B] may be null;
+// n_colliding (one int, zeroed by the caller) += the scenes with first_hit >= 0.
+void launch_check_collisions(const CollisionParams& P, const cilqr_scene_batch& dv, const double* rows, uint8_t* mask,
+                             int* first_hit, int* n_hit, int* n_colliding, hipStream_t st);
 
 }  // namespace cilqr

@@ -4,8 +4,7 @@
 #include <cstring>
 #include <vector>
 
-#include "collision.hpp"
-#include "scene_batch.hpp"
+#include "audit_batch.hpp"
 
 using namespace cilqr;
 
@@ -16,19 +15,12 @@ extern "C" int cilqr_check_collisions_batch(cilqr_handle h, const cilqr_dp_confi
       scenes->center == nullptr)
     return CILQR_ERR_NULL;
   const cilqr_scene_batch& sb = *scenes;
-  if (int rc = check_scene_batch(sb)) return rc;
-  if (int rc = check_audit_arguments(layout, n_knots, collision_buffer)) return rc;
-  if (beyond_limits(sb, n_knots)) return CILQR_ERR_CAPACITY;
-  if (solves_in_flight(h)) return CILQR_ERR_STATE;
+  if (int rc = check_audit_batch(sb, layout, n_knots, collision_buffer)) return rc;
+  if (int rc = check_audit_admissible(h, sb, n_knots)) return rc;
   const bool on_host = sb.memory == CILQR_MEM_HOST;
-  if (on_host && !host_counts_valid(sb)) return CILQR_ERR_ARG;
 
   // ---- the road and the vehicle, by the host planner's own constructor
-  std::vector<std::array<double, 7>> center(sb.n_center);
-  for (int i = 0; i < sb.n_center; ++i)
-    for (int e = 0; e < 7; ++e) center[i][e] = sb.center[(size_t)i * 7 + e];
-  const ReferenceLine ref(center);
-  const DpEnvironment env(dp_config_of(*cfg), ref);
+  const DpEnvironment env(dp_config_of(*cfg), reference_line_of(sb.center, sb.n_center));
   const std::vector<DpPoint2>& barrier = env.barrier();
   static_assert(sizeof(DpPoint2) == 16, "the barrier table travels as [n][2] doubles");
   CollisionParams P;
@@ -36,22 +28,21 @@ extern "C" int cilqr_check_collisions_batch(cilqr_handle h, const cilqr_dp_confi
   P.h = env.disc_radius() + collision_buffer;
   P.r2x = env.rear_disc_x(); P.f2x = env.front_disc_x();
   P.n_knots = n_knots; P.n_barrier = (int)barrier.size();
-  P.max_static = sb.max_static; P.max_dynamic = sb.max_dynamic; P.max_vertices = sb.max_vertices; P.max_samples = sb.max_samples;
+  scene_limits_into(&P, sb);
   P.rows = row_layout(layout);
 
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = h->stream;
   const size_t B = (size_t)sb.batch, K = (size_t)n_knots;
   // ---- work space of the handle (grown, never shrunk): the table and the count; HOST arrays: one block in, one block out
-  block_layout l_tab, l_in, l_out;
+  block_layout l_tab, l_out;
   const slot s_barrier = l_tab.add(barrier.size() * 2 * 8), s_count = l_tab.add(4);
-  const slot s_rows = l_in.add(B * K * (size_t)P.rows.fields * 8);
-  const SceneImage im(l_in, sb);
+  const AuditInput in(sb, n_knots, P.rows);
   const slot s_mask = l_out.add(mask ? B * K : 0), s_first = l_out.add(B * 4), s_nhit = l_out.add(n_hit ? B * 4 : 0);
   HIP_TRY(h->cc_tab_host.grow(l_tab.bytes() + 256));
   HIP_TRY(h->cc_tab.grow(l_tab.bytes() + 256, &h->grown_bytes));
   if (on_host) {
-    HIP_TRY(h->cc_in.grow(l_in.bytes() + 256, &h->grown_bytes));
+    HIP_TRY(h->cc_in.grow(in.l.bytes() + 256, &h->grown_bytes));
     HIP_TRY(h->cc_out.grow(l_out.bytes() + 256, &h->grown_bytes));
   }
 
@@ -72,26 +63,17 @@ extern "C" int cilqr_check_collisions_batch(cilqr_handle h, const cilqr_dp_confi
   int *d_first = first_hit, *d_nhit = n_hit;
   char* bo = h->cc_out.as<char>();
   if (on_host) {
-    char* bi = h->cc_in.as<char>();
-    if (int rc = copy_in(bi, s_rows, rows, st)) return rc;
-    if (int rc = im.upload(sb, bi, st, &dv)) return rc;
-    d_rows = s_rows.in<const double>(bi);
+    if (int rc = in.upload(sb, rows, h->cc_in.as<char>(), st, &d_rows, &dv)) return rc;
     if (mask) d_mask = s_mask.in<uint8_t>(bo);
     d_first = s_first.in<int>(bo);
     if (n_hit) d_nhit = s_nhit.in<int>(bo);
   }
-  launch_check_collisions(P, sb.batch, d_rows, dv.static_points, dv.static_counts, dv.dynamic_polygon_points,
-                          dv.dynamic_polygon_counts, dv.dynamic_trajectories, dv.dynamic_trajectory_counts, d_mask, d_first,
-                          d_nhit, d_count, st);
+  launch_check_collisions(P, dv, d_rows, d_mask, d_first, d_nhit, d_count, st);
   HIP_TRY(hipGetLastError());
   if (on_host) {
     if (int rc = copy_out(mask, bo, s_mask, st)) return rc;
     if (int rc = copy_out(first_hit, bo, s_first, st)) return rc;
     if (int rc = copy_out(n_hit, bo, s_nhit, st)) return rc;
   }
-  int* count_host = s_count.in<int>(th);
-  HIP_TRY(hipMemcpyAsync(count_host, d_count, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));   // this stream alone: solves on other handles go on
-  if (n_colliding) *n_colliding = *count_host;
-  return CILQR_OK;
+  return wait_and_fetch_count(d_count, s_count.in<int>(th), st, n_colliding);
 }

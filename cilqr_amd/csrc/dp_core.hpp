@@ -10,7 +10,8 @@
 // NormalizeAngle the exact normalize_angle, so the Frenet coordinates of the start are the host's bits.
 #pragma once
 
-#include "dev_model.hpp"
+#include "../../include/cilqr.h"
+#include "scene_core.hpp"
 
 namespace cilqr {
 
@@ -37,12 +38,17 @@ struct DpParams {
   const double* barrier;      // [n_barrier][2] both road barriers, sorted by x (Environment::set_reference)
 };
 
+// kernels_dp.hip.  `dv`: the batch with its arrays on the device; scenes [first, first + n_scenes) of them, the placed
+// polygons start at the FIRST of these scenes
+void launch_dp_place(const DpParams& P, const cilqr_scene_batch& dv, int first, int n_scenes, double* placed, int* placed_n,
+                     hipStream_t st);
+void launch_dp_plan(const DpParams& P, const cilqr_scene_batch& dv, int first, int n_scenes, const double* start3,
+                    const double* placed, const int* placed_n, double* coarse9, double* coarse6, double* knots3,
+                    double* station, int* found, int* n_not_found, hipStream_t st);
+
 struct DpRef {
   double s, x, y, theta, kappa, left_bound, right_bound;
 };
-
-CILQR_DEV double dp_min(double a, double b) { return (b < a) ? b : a; }   // std::min
-CILQR_DEV double dp_max(double a, double b) { return (a < b) ? b : a; }   // std::max
 
 CILQR_DEV DpRef dp_center_point(const DpParams& P, int i) {
   const double* c = P.center + (size_t)i * 7;
@@ -161,17 +167,6 @@ CILQR_DEV bool dp_overlap(const double* box, const double* pts, int n, const DpS
   return dp_poly_has_point(box, pts, n, b.cx + b.h, b.cy - b.h) || dp_poly_has_point(box, pts, n, b.cx + b.h, b.cy + b.h) ||
          dp_poly_has_point(box, pts, n, b.cx - b.h, b.cy + b.h) || dp_poly_has_point(box, pts, n, b.cx - b.h, b.cy - b.h);
 }
-// bounding box of n >= 1 vertices as Polygon2d::BuildFromPoints takes it (polygon2d.cpp:240-257)
-CILQR_DEV void dp_bounding_box(const double* pts, int n, double* box) {
-  double min_x = pts[0], max_x = pts[0], min_y = pts[1], max_y = pts[1];
-  for (int i = 0; i < n; ++i) {
-    min_x = dp_min(min_x, pts[2 * i]);
-    max_x = dp_max(max_x, pts[2 * i]);
-    min_y = dp_min(min_y, pts[2 * i + 1]);
-    max_y = dp_max(max_y, pts[2 * i + 1]);
-  }
-  box[0] = min_x; box[1] = max_x; box[2] = min_y; box[3] = max_y;
-}
 
 // the obstacles of one scene as a workgroup sees them
 struct DpScene {
@@ -187,6 +182,7 @@ CILQR_DEV bool dp_static_collision(const DpParams& P, const DpScene& S, double c
     const int n = S.static_n[o];
     if (n > 0 && dp_overlap(S.statics + o * kDpRec, S.statics + o * kDpRec + 4, n, b)) return true;
   }
+  // the window of scene_barrier_window (scene_core.hpp), written out: k_dp_plan measured 3 % slower with the call inlined
   const int nb = P.n_barrier;
   if (nb == 0) return false;
   if (b.max_x < P.barrier[0] || b.min_x > P.barrier[(size_t)(nb - 1) * 2]) return false;
@@ -219,12 +215,10 @@ CILQR_DEV bool dp_dynamic_collision(const DpParams& P, const DpScene& S, int q, 
 }
 // environment.cpp:92-111 (collision_buffer = 0) at path sample q, whose time selected the placed polygons
 CILQR_DEV bool dp_check_collision(const DpParams& P, const DpScene& S, int q, double x, double y, double theta) {
-  double st, ct;
-  lean_sincos(theta, &st, &ct);
-  const double ax = x + P.f2x * ct, ay = y + P.f2x * st;   // vehicle_param.h:88-95
-  const double bx = x + P.r2x * ct, by = y + P.r2x * st;
-  return dp_static_collision(P, S, bx, by) || dp_static_collision(P, S, ax, ay) || dp_dynamic_collision(P, S, q, bx, by) ||
-         dp_dynamic_collision(P, S, q, ax, ay);
+  double c[4];   // rear, front
+  scene_discs_of_pose(x, y, theta, P.r2x, P.f2x, c);
+  return dp_static_collision(P, S, c[0], c[1]) || dp_static_collision(P, S, c[2], c[3]) ||
+         dp_dynamic_collision(P, S, q, c[0], c[1]) || dp_dynamic_collision(P, S, q, c[2], c[3]);
 }
 
 // ---- the lattice ----

@@ -7,9 +7,8 @@
 #include <limits>
 #include <vector>
 
-#include "../../include/cilqr.h"
-#include "../../include/cilqr/dp_planner.hpp"
 #include "collision.hpp"
+#include "scene_batch.hpp"
 
 namespace {
 
@@ -42,10 +41,7 @@ struct AuditScene {
   cilqr::DpEnvironment env;
   std::vector<int> static_slot, dynamic_slot;
   AuditScene(const cilqr_dp_config& cfg, const cilqr_scene& scene) {
-    std::vector<std::array<double, 7>> center(scene.n_center);
-    for (int i = 0; i < scene.n_center; ++i)
-      for (int e = 0; e < 7; ++e) center[i][e] = scene.center[(size_t)i * 7 + e];
-    env = cilqr::DpEnvironment(cilqr::dp_config_of(cfg), cilqr::ReferenceLine(center));
+    env = cilqr::DpEnvironment(cilqr::dp_config_of(cfg), cilqr::reference_line_of(scene.center, scene.n_center));
     size_t at = 0;
     for (int o = 0; o < scene.n_static; ++o) {
       std::vector<cilqr::DpPoint2> poly(scene.static_counts[o]);
@@ -95,12 +91,9 @@ void cilqr_default_dp_config(cilqr_dp_config* c) {
 int cilqr_road_barriers(const double* center, int32_t n_center, double* left, double* right, int32_t max_points) {
   if (center == nullptr || left == nullptr || right == nullptr) return CILQR_ERR_NULL;
   if (n_center < 2 || max_points < 1) return CILQR_ERR_ARG;
-  std::vector<std::array<double, 7>> c(n_center);
-  for (int i = 0; i < n_center; ++i)
-    for (int e = 0; e < 7; ++e) c[i][e] = center[(size_t)i * 7 + e];
-  const cilqr::ReferenceLine ref(c);
+  const cilqr::ReferenceLine ref = cilqr::reference_line_of(center, n_center);
   constexpr double kSampleStep = 0.1;                                   // environment.cpp:18
-  const double start_s = c.front()[0], back_s = c.back()[0];
+  const double start_s = center[0], back_s = center[(size_t)(n_center - 1) * 7];
   const int sample_points = int((back_s - start_s) / kSampleStep);      // cpp:29-31
   if (sample_points + 1 > max_points) return CILQR_ERR_CAPACITY;
   for (int i = 0; i <= sample_points; ++i) {
@@ -123,20 +116,9 @@ int cilqr_dp_plan(const cilqr_dp_config* cfg, const cilqr_scene* scene, const do
       (scene->n_dynamic > 0 && (scene->dynamic_polygon_points == nullptr || scene->dynamic_polygon_counts == nullptr ||
                                 scene->dynamic_trajectories == nullptr || scene->dynamic_trajectory_counts == nullptr)))
     return CILQR_ERR_NULL;
-  cilqr::DpConfig d;
-  d.tf = cfg->tf; d.delta_t = cfg->delta_t; d.dp_nominal_velocity = cfg->dp_nominal_velocity; d.dp_w_obstacle = cfg->dp_w_obstacle;
-  d.dp_w_lateral = cfg->dp_w_lateral; d.dp_w_lateral_change = cfg->dp_w_lateral_change;
-  d.dp_w_lateral_velocity_change = cfg->dp_w_lateral_velocity_change;
-  d.dp_w_longitudinal_velocity_bias = cfg->dp_w_longitudinal_velocity_bias;
-  d.dp_w_longitudinal_velocity_change = cfg->dp_w_longitudinal_velocity_change;
-  d.front_hang_length = cfg->front_hang_length; d.wheel_base = cfg->wheel_base; d.rear_hang_length = cfg->rear_hang_length;
-  d.width = cfg->width; d.max_velocity = cfg->max_velocity;
+  const cilqr::DpConfig d = cilqr::dp_config_of(*cfg);
   if ((int32_t)(d.tf / d.delta_t + 1) != n_knots) return CILQR_ERR_KNOTS;
-  std::vector<std::array<double, 7>> center(scene->n_center);
-  for (int i = 0; i < scene->n_center; ++i)
-    for (int e = 0; e < 7; ++e) center[i][e] = scene->center[(size_t)i * 7 + e];
-  const cilqr::ReferenceLine ref(center);
-  cilqr::DpEnvironment env(d, ref);
+  cilqr::DpEnvironment env(d, cilqr::reference_line_of(scene->center, scene->n_center));
   size_t at = 0;
   for (int o = 0; o < scene->n_static; ++o) {
     if (scene->static_counts[o] < 1) return CILQR_ERR_ARG;

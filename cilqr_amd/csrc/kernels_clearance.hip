@@ -2,19 +2,17 @@
 // the rule is stated once, in include/cilqr.h under "clearance"): Polygon2d::DistanceTo(Vec2d) (polygon2d.cpp:43-52) from
 // the two disc centres to every static polygon and to every dynamic polygon present at the knot's time, as
 // DpEnvironment::Clearance (include/cilqr/dp_planner.hpp) states it.  The point-in-polygon test and the bounding box are
-// dp_core.hpp's, hypot is dev_model.hpp's libm-identical hypot_ref, the time rule and the placement are the collision
-// audit's (kernels_collision.hip), the area-sign reversal is Polygon2d::BuildFromPoints' (as in kernels_scene_points.hip).
+// dp_core.hpp's, hypot is dev_model.hpp's libm-identical hypot_ref; the steps on the scene's arrays (counts, staging, sample
+// choice, placement, disc centres, area sign) are scene_core.hpp's.
 //
 // ONE WORKGROUP PER SCENE, and everything a scene's knots share stays in LDS:
 //   * one lane per static slot normalises its polygon once -- reversed if the area sum is negative, boxed after that -- and
 //     leaves box, vertices and the (unit vector, length) of every edge in LDS; the body-frame polygons of the dynamic
 //     obstacles are staged as they are;
-//   * one lane per knot reads the pose from the row (time, x, y, theta), takes the heading through lean_sincos as the DP
-//     kernels do and leaves the time and the two disc centres in LDS;
-//   * the lanes stride over the (knot, dynamic slot) pairs: a pair's lane bisects its time column (on non-decreasing times
-//     the index of the host's scan), places the polygon with the device library's cos / sin in Pose::transform order into
-//     its own record in LDS (so nothing is indexed in registers and nothing goes to scratch), normalises it there, and
-//     measures it against both discs, edge by edge;
+//   * one lane per knot reads the pose from the row (time, x, y, theta) and leaves the time and the two disc centres in LDS;
+//   * the lanes stride over the (knot, dynamic slot) pairs: a pair's lane picks the sample, places the polygon into its own
+//     record in LDS (so nothing is indexed in registers and nothing goes to scratch), normalises it there, and measures it
+//     against both discs, edge by edge;
 //   * the same lanes stride over the (knot, static slot) pairs;
 //   * THE MINIMUM OVER THE SLOTS OF A KNOT uses no atomic and does not depend on the order of the lanes.  The slots are
 //     padded to a power of two G <= 32, pair p = knot * G + slot, so the G lanes of a knot are neighbours in one wavefront
@@ -58,13 +56,10 @@ CILQR_DEV double cl_hypot(double x, double y) {
   return hypot_ref(x, y);
 }
 
-// Polygon2d::BuildFromPoints (polygon2d.cpp:219-226, 246-256) on n >= 1 vertices in place: reversed if the area sum is
-// negative, then boxed
+// Polygon2d::BuildFromPoints (polygon2d.cpp:219-226, 246-256) on n >= 1 vertices in place: reversed if the area sum
+// (scene_core.hpp) is negative, then boxed
 CILQR_DEV void cl_normalise(double* pts, int n, double* box) {
-  double area = 0.0;
-  for (int i = 1; i < n; ++i)   // CrossProd(p0, p[i-1], p[i])
-    area = area + ((pts[2 * (i - 1)] - pts[0]) * (pts[2 * i + 1] - pts[1]) - (pts[2 * (i - 1) + 1] - pts[1]) * (pts[2 * i] - pts[0]));
-  if (area < 0)
+  if (scene_area_negative(ScenePolygon{pts}, n))
     for (int i = 0, j = n - 1; i < j; ++i, --j) {
       const double x = pts[2 * i], y = pts[2 * i + 1];
       pts[2 * i] = pts[2 * j]; pts[2 * i + 1] = pts[2 * j + 1];
@@ -167,18 +162,7 @@ __global__ __launch_bounds__(kClBlock) void k_clearance(ClearanceParams P, const
   __shared__ int s_static_n[kClMaxS], s_m[kClMaxD], s_T[kClMaxD];
   __shared__ int s_ok;
 
-  if (tid == 0) {
-    bool ok = true;
-    for (int o = 0; o < S; ++o) {
-      const int n = static_counts[(size_t)b * S + o];
-      ok = ok && n >= 0 && n <= V;
-    }
-    for (int d = 0; d < D; ++d) {
-      const int m = dyn_poly_counts[(size_t)b * D + d], T = dyn_traj_counts[(size_t)b * D + d];
-      ok = ok && m >= 0 && m <= V && T >= 0 && T <= P.max_samples;
-    }
-    s_ok = ok ? 1 : 0;
-  }
+  if (tid == 0) s_ok = scene_counts_valid(b, S, D, V, P.max_samples, static_counts, dyn_poly_counts, dyn_traj_counts) ? 1 : 0;
   __syncthreads();
   if (s_ok == 0) {   // (uniform)
     for (int i = tid; i < K * 4; i += kClBlock) {
@@ -197,29 +181,19 @@ __global__ __launch_bounds__(kClBlock) void k_clearance(ClearanceParams P, const
     const int n = static_counts[(size_t)b * S + tid];
     s_static_n[tid] = n;
     if (n > 0) {
-      const double* src = static_points + ((size_t)b * S + tid) * V * 2;
       double* rec = s_static + tid * kClStaticRec;
+      const double* src = static_points + ((size_t)b * S + tid) * V * 2;
       for (int v = 0; v < 2 * n; ++v) rec[4 + v] = src[v];
       cl_normalise(rec + 4, n, rec);
       double* edges = rec + 4 + 2 * kDpMaxV;
       for (int i = 0; i < n; ++i) cl_edge(rec + 4, n, i, edges + 3 * i, edges + 3 * i + 1, edges + 3 * i + 2);
     }
   }
-  if (tid < D) {
-    s_m[tid] = dyn_poly_counts[(size_t)b * D + tid];
-    s_T[tid] = dyn_traj_counts[(size_t)b * D + tid];
-  }
-  for (int i = tid; i < D * V * 2; i += kClBlock) s_body[i] = dyn_poly[(size_t)b * D * V * 2 + i];
+  scene_stage_dynamic(b, D, V, kClBlock, dyn_poly, dyn_poly_counts, dyn_traj_counts, s_m, s_T, s_body);
   for (int k = tid; k < K; k += kClBlock) {
     const double* row = rows + ((size_t)b * K + k) * P.rows.fields;
-    const double x = row[P.rows.x], y = row[P.rows.y];
-    double st, ct;
-    lean_sincos(row[P.rows.theta], &st, &ct);
     s_time[k] = row[P.rows.time];
-    s_disc[4 * k] = x + P.r2x * ct;       // vehicle_param.h:88-95
-    s_disc[4 * k + 1] = y + P.r2x * st;
-    s_disc[4 * k + 2] = x + P.f2x * ct;
-    s_disc[4 * k + 3] = y + P.f2x * st;
+    scene_discs_of_pose(row[P.rows.x], row[P.rows.y], row[P.rows.theta], P.r2x, P.f2x, s_disc + 4 * k);
     for (int c = 0; c < 4; ++c) {
       s_best[4 * k + c] = HUGE_VAL;
       s_near[4 * k + c] = -1;
@@ -236,24 +210,13 @@ __global__ __launch_bounds__(kClBlock) void k_clearance(ClearanceParams P, const
       const int k = p / G, d = p - k * G;
       double d_rear = HUGE_VAL, d_front = HUGE_VAL;
       if (k < K && d < D) {
-        const int m = s_m[d], T = s_T[d];
-        const double t = s_time[k];
+        const int m = s_m[d];
         const double* traj = dyn_traj + ((size_t)b * D + d) * P.max_samples * 4;
-        if (m >= 1 && T >= 1 && !(traj[0] > t || traj[(size_t)(T - 1) * 4] < t)) {   // cpp:117, no epsilon
-          int lo = 0, hi = T;   // first sample with t < sample time (std::upper_bound); past the end: the last one
-          while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (t < traj[(size_t)mid * 4]) hi = mid;
-            else lo = mid + 1;
-          }
-          if (lo >= T) lo = T - 1;
-          const double* tp = traj + (size_t)lo * 4;
-          const double c = cos(tp[3]), s = sin(tp[3]);
-          for (int v = 0; v < m; ++v) {   // Pose::transform, pose.h:40-46
-            const double vx = s_body[(d * V + v) * 2], vy = s_body[(d * V + v) * 2 + 1];
-            placed[2 * v] = tp[1] + vx * c - vy * s;
-            placed[2 * v + 1] = tp[2] + vx * s + vy * c;
-          }
+        const int T = s_T[d];
+        const double t = s_time[k];
+        if (m >= 1 && scene_present<false>(traj, T, t)) {
+          const double* tp = traj + (size_t)scene_sample_index<false>(traj, T, t) * 4;
+          scene_place(s_body + d * V * 2, m, tp[1], tp[2], cos(tp[3]), sin(tp[3]), placed);
           double box[4];
           cl_normalise(placed, m, box);
           cl_polygon_distance(box, placed, nullptr, m, s_disc + 4 * k, &d_rear, &d_front);
@@ -334,13 +297,12 @@ __global__ __launch_bounds__(kClBlock) void k_clearance(ClearanceParams P, const
   }
 }
 
-void launch_clearance(const ClearanceParams& P, int n_scenes, const double* rows, const double* static_points,
-                      const int* static_counts, const double* dyn_poly, const int* dyn_poly_counts, const double* dyn_traj,
-                      const int* dyn_traj_counts, double* clearance, int* nearest, double* min_clearance, int* min_knot,
-                      int* n_below, hipStream_t st) {
-  if (n_scenes <= 0) return;
-  hipLaunchKernelGGL(k_clearance, dim3(n_scenes), dim3(kClBlock), 0, st, P, rows, static_points, static_counts, dyn_poly,
-                     dyn_poly_counts, dyn_traj, dyn_traj_counts, clearance, nearest, min_clearance, min_knot, n_below);
+void launch_clearance(const ClearanceParams& P, const cilqr_scene_batch& dv, const double* rows, double* clearance,
+                      int* nearest, double* min_clearance, int* min_knot, int* n_below, hipStream_t st) {
+  if (dv.batch <= 0) return;
+  hipLaunchKernelGGL(k_clearance, dim3(dv.batch), dim3(kClBlock), 0, st, P, rows, dv.static_points, dv.static_counts,
+                     dv.dynamic_polygon_points, dv.dynamic_polygon_counts, dv.dynamic_trajectories,
+                     dv.dynamic_trajectory_counts, clearance, nearest, min_clearance, min_knot, n_below);
 }
 
 }  // namespace cilqr

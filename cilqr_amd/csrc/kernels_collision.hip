@@ -1,19 +1,19 @@
 // Which knots of a batch of trajectories touch their scenes (C-ABI: cilqr_check_collisions_batch):
 // Environment::CheckOptimizationCollision (algorithm/utils/environment.cpp:92-111) with a collision buffer, as
 // DpEnvironment::CollisionMask (include/cilqr/dp_planner.hpp) states it -- every one of the six (disc, kind of obstacle)
-// tests, none short-circuited.  The geometry is dp_core.hpp's, the functions the DP kernels decide with.
+// tests, none short-circuited.  The geometry is dp_core.hpp's, the functions the DP kernels decide with; the steps on the
+// scene's arrays (counts, staging, sample choice, placement, disc centres, barrier window) are scene_core.hpp's.
 //
 // ONE WORKGROUP PER SCENE, and everything a scene's knots share stays in LDS:
 //   * the static polygons with their boxes and the body-frame polygons of the dynamic obstacles are staged once;
-//   * one lane per knot reads the pose from the row (the only columns touched: time, x, y, theta), takes the heading
-//     through lean_sincos as the DP kernels do and leaves the time and the two disc centres in LDS;
-//   * the lanes stride over the (knot, dynamic slot) pairs: a pair's lane searches its time column by bisection (on
-//     non-decreasing times the index of the host's scan), places the polygon with the device library's cos / sin in
-//     Pose::transform order, boxes it, and tests it against both discs of the knot -- the placed polygon lives in the
-//     lane's own record in LDS, so nothing is indexed in registers and nothing goes to scratch;
+//   * one lane per knot reads the pose from the row (the only columns touched: time, x, y, theta) and leaves the time
+//     and the two disc centres in LDS;
+//   * the lanes stride over the (knot, dynamic slot) pairs: a pair's lane picks the sample, places and boxes the polygon
+//     and tests it against both discs of the knot -- the placed polygon lives in the lane's own record in LDS, so
+//     nothing is indexed in registers and nothing goes to scratch;
 //   * the same lanes stride over the (knot, static slot) pairs;
-//   * one lane per disc finds its barrier window (two upper_bounds on x and the one predecessor), then every wavefront
-//     takes discs in turn and its 64 lanes stride over the window's points;
+//   * one lane per disc finds its barrier window, then every wavefront takes discs in turn and its 64 lanes stride over
+//     the window's points;
 //   * bits are OR-ed into one LDS word per knot; after the last pass the row is written with consecutive addresses and
 //     first_hit / n_hit are reduced with LDS atomics.
 // Every index is bounded by the max_* of the call and by n_knots <= CILQR_DP_MAX_KNOTS; a scene whose counts leave them gets
@@ -65,16 +65,7 @@ __global__ __launch_bounds__(kCcBlock) void k_check_collisions(CollisionParams P
   __shared__ int s_ok, s_first, s_count;
 
   if (tid == 0) {
-    bool ok = true;
-    for (int o = 0; o < S; ++o) {
-      const int n = static_counts[(size_t)b * S + o];
-      ok = ok && n >= 0 && n <= V;
-    }
-    for (int d = 0; d < D; ++d) {
-      const int m = dyn_poly_counts[(size_t)b * D + d], T = dyn_traj_counts[(size_t)b * D + d];
-      ok = ok && m >= 0 && m <= V && T >= 0 && T <= P.max_samples;
-    }
-    s_ok = ok ? 1 : 0;
+    s_ok = scene_counts_valid(b, S, D, V, P.max_samples, static_counts, dyn_poly_counts, dyn_traj_counts) ? 1 : 0;
     s_first = K;
     s_count = 0;
   }
@@ -93,28 +84,13 @@ __global__ __launch_bounds__(kCcBlock) void k_check_collisions(CollisionParams P
   if (tid < S) {
     const int n = static_counts[(size_t)b * S + tid];
     s_static_n[tid] = n;
-    if (n > 0) {
-      const double* src = static_points + ((size_t)b * S + tid) * V * 2;
-      double* rec = s_static + tid * kDpRec;
-      for (int v = 0; v < 2 * n; ++v) rec[4 + v] = src[v];
-      dp_bounding_box(rec + 4, n, rec);
-    }
+    if (n > 0) scene_stage_static(static_points + ((size_t)b * S + tid) * V * 2, n, s_static + tid * kDpRec);
   }
-  if (tid < D) {
-    s_m[tid] = dyn_poly_counts[(size_t)b * D + tid];
-    s_T[tid] = dyn_traj_counts[(size_t)b * D + tid];
-  }
-  for (int i = tid; i < D * V * 2; i += kCcBlock) s_body[i] = dyn_poly[(size_t)b * D * V * 2 + i];
+  scene_stage_dynamic(b, D, V, kCcBlock, dyn_poly, dyn_poly_counts, dyn_traj_counts, s_m, s_T, s_body);
   for (int k = tid; k < K; k += kCcBlock) {
     const double* row = rows + ((size_t)b * K + k) * P.rows.fields;
-    const double x = row[P.rows.x], y = row[P.rows.y];
-    double st, ct;
-    lean_sincos(row[P.rows.theta], &st, &ct);
     s_time[k] = row[P.rows.time];
-    s_disc[4 * k] = x + P.r2x * ct;       // vehicle_param.h:88-95
-    s_disc[4 * k + 1] = y + P.r2x * st;
-    s_disc[4 * k + 2] = x + P.f2x * ct;
-    s_disc[4 * k + 3] = y + P.f2x * st;
+    scene_discs_of_pose(row[P.rows.x], row[P.rows.y], row[P.rows.theta], P.r2x, P.f2x, s_disc + 4 * k);
     s_mask[k] = 0u;
   }
   __syncthreads();
@@ -123,25 +99,14 @@ __global__ __launch_bounds__(kCcBlock) void k_check_collisions(CollisionParams P
   double* placed = s_placed + tid * kCcLaneRec;
   for (int p = tid; p < K * D; p += kCcBlock) {
     const int k = p / D, d = p - k * D;
-    const int m = s_m[d], T = s_T[d];
-    if (m < 1 || T < 1) continue;
-    const double t = s_time[k];
+    const int m = s_m[d];
+    if (m < 1) continue;
     const double* traj = dyn_traj + ((size_t)b * D + d) * P.max_samples * 4;
-    if (traj[0] > t || traj[(size_t)(T - 1) * 4] < t) continue;   // cpp:117, no epsilon
-    int lo = 0, hi = T;   // first sample with t < sample time (std::upper_bound); past the end: the last one
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (t < traj[(size_t)mid * 4]) hi = mid;
-      else lo = mid + 1;
-    }
-    if (lo >= T) lo = T - 1;
-    const double* tp = traj + (size_t)lo * 4;
-    const double c = cos(tp[3]), s = sin(tp[3]);
-    for (int v = 0; v < m; ++v) {   // Pose::transform, pose.h:40-46
-      const double vx = s_body[(d * V + v) * 2], vy = s_body[(d * V + v) * 2 + 1];
-      placed[4 + 2 * v] = tp[1] + vx * c - vy * s;
-      placed[4 + 2 * v + 1] = tp[2] + vx * s + vy * c;
-    }
+    const int T = s_T[d];
+    const double t = s_time[k];
+    if (!scene_present<false>(traj, T, t)) continue;
+    const double* tp = traj + (size_t)scene_sample_index<false>(traj, T, t) * 4;
+    scene_place(s_body + d * V * 2, m, tp[1], tp[2], cos(tp[3]), sin(tp[3]), placed + 4);
     dp_bounding_box(placed + 4, m, placed);
     unsigned bits = 0u;
     if (dp_overlap(placed, placed + 4, m, dp_square_of(P.h, s_disc[4 * k], s_disc[4 * k + 1]))) bits |= kRearDynamic;
@@ -162,24 +127,10 @@ __global__ __launch_bounds__(kCcBlock) void k_check_collisions(CollisionParams P
   }
 
   // ---- the road barriers, environment.cpp:54-80: the window of every disc, then the points of the windows
-  const int nb = P.n_barrier;
   for (int p = tid; p < 2 * K; p += kCcBlock) {
     const DpSquare sq = dp_square_of(P.h, s_disc[2 * p], s_disc[2 * p + 1]);   // disc p & 1 of knot p >> 1
-    int first = 0, last = 0;
-    if (nb > 0 && !(sq.max_x < P.barrier[0] || sq.min_x > P.barrier[(size_t)(nb - 1) * 2])) {
-      auto upper = [&](double val) {   // first barrier point with val < point.x
-        int lo = 0, hi = nb;
-        while (lo < hi) {
-          const int mid = (lo + hi) / 2;
-          if (val < P.barrier[(size_t)mid * 2]) hi = mid;
-          else lo = mid + 1;
-        }
-        return lo;
-      };
-      first = upper(sq.min_x);
-      last = upper(sq.max_x);
-      if (first > 0) --first;
-    }
+    int first, last;
+    scene_barrier_window(P.barrier, P.n_barrier, sq.min_x, sq.max_x, &first, &last);
     s_window[p][0] = first;
     s_window[p][1] = last;
   }
@@ -213,13 +164,12 @@ __global__ __launch_bounds__(kCcBlock) void k_check_collisions(CollisionParams P
   }
 }
 
-void launch_check_collisions(const CollisionParams& P, int n_scenes, const double* rows, const double* static_points,
-                             const int* static_counts, const double* dyn_poly, const int* dyn_poly_counts,
-                             const double* dyn_traj, const int* dyn_traj_counts, uint8_t* mask, int* first_hit, int* n_hit,
-                             int* n_colliding, hipStream_t st) {
-  if (n_scenes <= 0) return;
-  hipLaunchKernelGGL(k_check_collisions, dim3(n_scenes), dim3(kCcBlock), 0, st, P, rows, static_points, static_counts,
-                     dyn_poly, dyn_poly_counts, dyn_traj, dyn_traj_counts, mask, first_hit, n_hit, n_colliding);
+void launch_check_collisions(const CollisionParams& P, const cilqr_scene_batch& dv, const double* rows, uint8_t* mask,
+                             int* first_hit, int* n_hit, int* n_colliding, hipStream_t st) {
+  if (dv.batch <= 0) return;
+  hipLaunchKernelGGL(k_check_collisions, dim3(dv.batch), dim3(kCcBlock), 0, st, P, rows, dv.static_points, dv.static_counts,
+                     dv.dynamic_polygon_points, dv.dynamic_polygon_counts, dv.dynamic_trajectories,
+                     dv.dynamic_trajectory_counts, mask, first_hit, n_hit, n_colliding);
 }
 
 }  // namespace cilqr

@@ -14,15 +14,14 @@
 //
 //   k_dp_place   pre-pass, one lane per (scene, path sample, dynamic obstacle): the time of a path sample depends on
 //                (layer, i) alone, so the polygon a dynamic obstacle shows to ANY transition at that sample is one
-//                polygon -- picked (std::upper_bound on the sample times), placed (Pose::transform order
-//                x + rx c - ry s) and boxed once, instead of once per collision test.
+//                polygon -- picked, placed and boxed (scene_core.hpp) once, instead of once per collision test.  The
+//                pick is a bisection: on the non-decreasing sample times cilqr.h declares, the index of the host's scan.
 //   k_dp_plan    the planner.
 // The centre line and the x-sorted road-barrier table are built on the host once per call by the host planner's own
 // code and read by all workgroups through L2.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/cilqr.h"
 #include "dp_core.hpp"
 
 namespace cilqr {
@@ -31,21 +30,6 @@ namespace {
 
 constexpr int kDpBlock = 256;
 constexpr int kDpMaxQ = 256;   // CILQR_DP_MAX_KNOTS: path samples of the five layers together
-
-// counts a scene may carry: anything else marks it invalid (DEVICE arrays; HOST arrays are checked before the launch)
-__device__ __forceinline__ bool dp_counts_valid(const DpParams& P, const int* static_counts, const int* dyn_poly_counts,
-                                                const int* dyn_traj_counts, int b) {
-  bool ok = true;
-  for (int o = 0; o < P.max_static; ++o) {
-    const int n = static_counts[(size_t)b * P.max_static + o];
-    ok = ok && n >= 0 && n <= P.max_vertices;
-  }
-  for (int d = 0; d < P.max_dynamic; ++d) {
-    const int m = dyn_poly_counts[(size_t)b * P.max_dynamic + d], T = dyn_traj_counts[(size_t)b * P.max_dynamic + d];
-    ok = ok && m >= 0 && m <= P.max_vertices && T >= 0 && T <= P.max_samples;
-  }
-  return ok;
-}
 
 }  // namespace
 
@@ -77,21 +61,13 @@ __global__ __launch_bounds__(kDpBlock) void k_dp_place(DpParams P, int first, in
   const double from_time = layer == 0 ? 0.0 : P.time[layer - 1];
   const double when = from_time + i * (P.unit_time / P.nseg[layer]);
   const double* traj = dyn_traj + ((size_t)b * P.max_dynamic + d) * P.max_samples * 4;
-  if (traj[0] > when || traj[(size_t)(T - 1) * 4] < when) {   // environment.cpp:117
+  const int k = scene_sample<false>(traj, T, when);
+  if (k < 0) {
     placed_n[t] = 0;
     return;
   }
-  int k = 0;   // first sample with when < sample time (std::upper_bound); past the end: the last one
-  while (k < T && !(when < traj[(size_t)k * 4])) ++k;
-  if (k >= T) k = T - 1;
   const double* tp = traj + (size_t)k * 4;
-  const double c = cos(tp[3]), s = sin(tp[3]);
-  const double* body = dyn_poly + ((size_t)b * P.max_dynamic + d) * P.max_vertices * 2;
-  for (int v = 0; v < m; ++v) {   // Pose::transform, pose.h:40-46
-    const double vx = body[2 * v], vy = body[2 * v + 1];
-    out[4 + 2 * v] = tp[1] + vx * c - vy * s;
-    out[4 + 2 * v + 1] = tp[2] + vx * s + vy * c;
-  }
+  scene_place(dyn_poly + ((size_t)b * P.max_dynamic + d) * P.max_vertices * 2, m, tp[1], tp[2], cos(tp[3]), sin(tp[3]), out + 4);
   dp_bounding_box(out + 4, m, out);
   placed_n[t] = m;
 }
@@ -122,7 +98,9 @@ __global__ __launch_bounds__(kDpBlock) void k_dp_plan(DpParams P, int first, con
   __shared__ int s_flag[2];       // counts valid, found
 
   // ---- the scene: counts, static polygons with their boxes
-  if (tid == 0) s_flag[0] = dp_counts_valid(P, static_counts, dyn_poly_counts, dyn_traj_counts, b) ? 1 : 0;
+  if (tid == 0)
+    s_flag[0] = scene_counts_valid(b, P.max_static, P.max_dynamic, P.max_vertices, P.max_samples, static_counts,
+                                   dyn_poly_counts, dyn_traj_counts) ? 1 : 0;
   __syncthreads();
   if (s_flag[0] == 0) {   // (uniform) rows of zeros, not found
     for (int k = tid; k < K; k += kDpBlock) {
@@ -141,12 +119,7 @@ __global__ __launch_bounds__(kDpBlock) void k_dp_plan(DpParams P, int first, con
   if (tid < P.max_static) {
     const int n = static_counts[(size_t)b * P.max_static + tid];
     s_static_n[tid] = n;
-    if (n > 0) {
-      const double* src = static_points + ((size_t)b * P.max_static + tid) * P.max_vertices * 2;
-      double* rec = s_static + tid * kDpRec;
-      for (int v = 0; v < 2 * n; ++v) rec[4 + v] = src[v];
-      dp_bounding_box(rec + 4, n, rec);
-    }
+    if (n > 0) scene_stage_static(static_points + ((size_t)b * P.max_static + tid) * P.max_vertices * 2, n, s_static + tid * kDpRec);
   }
   DpScene S;
   S.statics = s_static;
@@ -395,21 +368,21 @@ __global__ __launch_bounds__(kDpBlock) void k_dp_plan(DpParams P, int first, con
   }
 }
 
-void launch_dp_place(const DpParams& P, int first, int n_scenes, const double* dyn_poly, const int* dyn_poly_counts,
-                     const double* dyn_traj, const int* dyn_traj_counts, double* placed, int* placed_n, hipStream_t st) {
+void launch_dp_place(const DpParams& P, const cilqr_scene_batch& dv, int first, int n_scenes, double* placed, int* placed_n,
+                     hipStream_t st) {
   const long long total = (long long)n_scenes * P.nq * P.max_dynamic;
   if (total <= 0) return;
   hipLaunchKernelGGL(k_dp_place, dim3((unsigned)((total + kDpBlock - 1) / kDpBlock)), dim3(kDpBlock), 0, st, P, first,
-                     n_scenes, dyn_poly, dyn_poly_counts, dyn_traj, dyn_traj_counts, placed, placed_n);
+                     n_scenes, dv.dynamic_polygon_points, dv.dynamic_polygon_counts, dv.dynamic_trajectories,
+                     dv.dynamic_trajectory_counts, placed, placed_n);
 }
 
-void launch_dp_plan(const DpParams& P, int first, int n_scenes, const double* start3, const double* static_points,
-                    const int* static_counts, const int* dyn_poly_counts, const int* dyn_traj_counts, const double* placed,
-                    const int* placed_n, double* coarse9, double* coarse6, double* knots3, double* station, int* found,
-                    int* n_not_found, hipStream_t st) {
-  hipLaunchKernelGGL(k_dp_plan, dim3(n_scenes), dim3(kDpBlock), 0, st, P, first, start3, static_points, static_counts,
-                     dyn_poly_counts, dyn_traj_counts, placed, placed_n, coarse9, coarse6, knots3, station, found,
-                     n_not_found);
+void launch_dp_plan(const DpParams& P, const cilqr_scene_batch& dv, int first, int n_scenes, const double* start3,
+                    const double* placed, const int* placed_n, double* coarse9, double* coarse6, double* knots3,
+                    double* station, int* found, int* n_not_found, hipStream_t st) {
+  hipLaunchKernelGGL(k_dp_plan, dim3(n_scenes), dim3(kDpBlock), 0, st, P, first, start3, dv.static_points, dv.static_counts,
+                     dv.dynamic_polygon_counts, dv.dynamic_trajectory_counts, placed, placed_n, coarse9, coarse6, knots3,
+                     station, found, n_not_found);
 }
 
 }  // namespace cilqr

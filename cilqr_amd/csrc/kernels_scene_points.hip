@@ -9,7 +9,7 @@
 //   * the static points are the same at every knot: they are produced once (corners, or the six samples per edge) and
 //     kept in LDS as the packed front of a row; the body-frame polygons of the dynamic obstacles are staged beside them;
 //   * the knots are taken eight at a time: 8 knots x 32 obstacle slots = one (knot, obstacle) pair per lane, which does
-//     the one search (bisection on the time column: trajectories have up to 1024 samples of 32 B), the one cos / sin and,
+//     the one search (scene_core.hpp's, with the 1e-10 of the Query...Points rule), the one cos / sin and,
 //     with is_multiple_sample, the one orientation test of the pair, and leaves pose and point count in LDS;
 //   * eight lanes turn the counts of their knot into offsets (a 32-entry running sum) and write point_count;
 //   * then the lanes stride over the live points of the eight rows together: lane i builds point i from LDS and stores
@@ -20,14 +20,14 @@
 // scene_ok 0 (DEVICE arrays; HOST arrays are refused before the launch).
 //
 // The arithmetic is environment_points' in its order, with the device library's cos / sin (what k_dp_place calls and
-// cilqr_device_math fn 7 / 8 exposes); built with -ffp-contract=off like every other file.
+// cilqr_device_math fn 7 / 8 exposes); counts, staging, sample choice, placement and area sign are scene_core.hpp's.
 //
 // Behind it, three small kernels of the batched TrajectoryPlanner::Plan (cilqr_plan_scenes_batch).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/cilqr.h"
-#include "dev_model.hpp"
+#include "scene_core.hpp"
 #include "scene_points.hpp"
 
 namespace cilqr {
@@ -41,24 +41,6 @@ constexpr int kSpMaxS = CILQR_DP_MAX_STATIC;
 constexpr int kSpMaxD = CILQR_DP_MAX_DYNAMIC;
 constexpr int kSpSamples = 6;                       // ratio = 0, 0.2, ... while ratio < 1 + 1e-10
 static_assert(kSpTile * kSpMaxD == kSpBlock, "one (knot, obstacle) pair per lane");
-
-// BuildFromPoints (polygon2d.cpp:212-220): the polygon is stored clockwise when this sum of cross products is negative
-template <class Vertex>
-__device__ __forceinline__ bool sp_clockwise(Vertex vertex, int m) {
-  double x0, y0, px, py;
-  vertex(0, &x0, &y0);
-  px = x0;
-  py = y0;
-  double area = 0.0;
-  for (int i = 1; i < m; ++i) {
-    double cx, cy;
-    vertex(i, &cx, &cy);
-    area = area + ((px - x0) * (cy - y0) - (py - y0) * (cx - x0));
-    px = cx;
-    py = cy;
-  }
-  return area < 0.0;
-}
 
 // point q of the polygon's contribution: corner q, or sample q % 6 of edge q / 6 of the counter-clockwise polygon
 template <class Vertex>
@@ -118,16 +100,7 @@ __global__ __launch_bounds__(kSpBlock) void k_scene_points(ScenePointsParams P, 
   __shared__ int s_ok;
 
   if (tid == 0) {
-    bool ok = true;
-    for (int o = 0; o < S; ++o) {
-      const int n = static_counts[(size_t)b * S + o];
-      ok = ok && n >= 0 && n <= V;
-    }
-    for (int d = 0; d < D; ++d) {
-      const int m = dyn_poly_counts[(size_t)b * D + d], T = dyn_traj_counts[(size_t)b * D + d];
-      ok = ok && m >= 0 && m <= V && T >= 0 && T <= P.max_samples;
-    }
-    s_ok = ok ? 1 : 0;
+    s_ok = scene_counts_valid(b, S, D, V, P.max_samples, static_counts, dyn_poly_counts, dyn_traj_counts) ? 1 : 0;
     double ratio = 0.0;   // polygon2d.cpp:264-268: accumulated, not i / 5
     for (int j = 0; j < kSpSamples; ++j) {
       s_ratio[j] = ratio;
@@ -145,11 +118,7 @@ __global__ __launch_bounds__(kSpBlock) void k_scene_points(ScenePointsParams P, 
   const double* st_pts = static_points + (size_t)b * S * V * 2;
   if (tid < S) {
     const int n = static_counts[(size_t)b * S + tid];
-    auto vertex = [&](int i, double* x, double* y) {
-      *x = st_pts[((size_t)tid * V + i) * 2];
-      *y = st_pts[((size_t)tid * V + i) * 2 + 1];
-    };
-    s_static_reversed[tid] = (per != 1 && n > 0 && sp_clockwise(vertex, n)) ? 1 : 0;
+    s_static_reversed[tid] = (per != 1 && n > 0 && scene_area_negative(ScenePolygon{st_pts + (size_t)tid * V * 2}, n)) ? 1 : 0;
     s_static_n[tid] = n;
   }
   __syncthreads();
@@ -174,47 +143,32 @@ __global__ __launch_bounds__(kSpBlock) void k_scene_points(ScenePointsParams P, 
     sp_point(vertex, n, s_static_reversed[o] != 0, per, p - s_static_offset[o], s_ratio, &s_static[2 * p], &s_static[2 * p + 1]);
   }
   __syncthreads();
-  if (tid < D) {
-    s_m[tid] = dyn_poly_counts[(size_t)b * D + tid];
-    s_T[tid] = dyn_traj_counts[(size_t)b * D + tid];
-  }
-  for (int i = tid; i < D * V * 2; i += kSpBlock) s_body[i] = dyn_poly[(size_t)b * D * V * 2 + i];
+  scene_stage_dynamic(b, D, V, kSpBlock, dyn_poly, dyn_poly_counts, dyn_traj_counts, s_m, s_T, s_body);
   __syncthreads();
 
   // ---- eight knots at a time
   const int kk_own = D > 0 ? tid / D : kSpTile, d_own = D > 0 ? tid - kk_own * D : 0;
   for (int k0 = 0; k0 < K; k0 += kSpTile) {
     if (kk_own < kSpTile && k0 + kk_own < K) {   // one (knot, obstacle) pair
-      const int m = s_m[d_own], T = s_T[d_own];
+      const int m = s_m[d_own];
       int count = 0;
       bool reversed = false;
-      if (m >= 1 && T >= 1) {
-        const double t = times[k0 + kk_own];
+      if (m >= 1) {
         const double* traj = dyn_traj + ((size_t)b * D + d_own) * P.max_samples * 4;
-        if (!(traj[0] > t + kMathEps || traj[(size_t)(T - 1) * 4] < t - kMathEps)) {   // environment.cpp:137-141
-          int lo = 0, hi = T;   // first sample with t < time + eps (std::upper_bound, cpp:143-146); past the end: the last
-          while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (t < traj[(size_t)mid * 4] + kMathEps) hi = mid;
-            else lo = mid + 1;
-          }
-          if (lo >= T) lo = T - 1;
-          const double* tp = traj + (size_t)lo * 4;
-          const double c = cos(tp[3]), s = sin(tp[3]);
+        const int at = scene_sample<true>(traj, s_T[d_own], times[k0 + kk_own]);
+        if (at >= 0) {
+          const double* tp = traj + (size_t)at * 4;
+          const double x = tp[1], y = tp[2], c = cos(tp[3]), s = sin(tp[3]);
           double* pose = s_pose + (size_t)(kk_own * kSpMaxD + d_own) * 4;
-          pose[0] = tp[1];
-          pose[1] = tp[2];
+          pose[0] = x;
+          pose[1] = y;
           pose[2] = c;
           pose[3] = s;
           count = m * per;
           if (per != 1) {
-            const double x = tp[1], y = tp[2];
-            auto vertex = [&](int i, double* ox, double* oy) {   // Pose::transform, pose.h:40-46
-              const double rx = s_body[(d_own * V + i) * 2], ry = s_body[(d_own * V + i) * 2 + 1];
-              *ox = x + rx * c - ry * s;
-              *oy = y + rx * s + ry * c;
-            };
-            reversed = sp_clockwise(vertex, m);
+            const double* body = s_body + d_own * V * 2;
+            auto vertex = [&](int i, double* ox, double* oy) { scene_place_vertex(body, i, x, y, c, s, ox, oy); };
+            reversed = scene_area_negative(vertex, m);
           }
         }
       }
@@ -258,11 +212,8 @@ __global__ __launch_bounds__(kSpBlock) void k_scene_points(ScenePointsParams P, 
         while (d + 1 < D && p >= s_offset[kk][d + 1]) ++d;
         const double* pose = s_pose + (size_t)(kk * kSpMaxD + d) * 4;
         const double ox = pose[0], oy = pose[1], c = pose[2], s = pose[3];
-        auto vertex = [&](int v, double* vx, double* vy) {   // Pose::transform, pose.h:40-46
-          const double rx = s_body[(d * V + v) * 2], ry = s_body[(d * V + v) * 2 + 1];
-          *vx = ox + rx * c - ry * s;
-          *vy = oy + rx * s + ry * c;
-        };
+        const double* body = s_body + d * V * 2;
+        auto vertex = [&](int v, double* vx, double* vy) { scene_place_vertex(body, v, ox, oy, c, s, vx, vy); };
         sp_point(vertex, s_m[d], s_reversed[kk * kSpMaxD + d] != 0, per, p - s_offset[kk][d], s_ratio, &x, &y);
       }
       if (p < P.max_points)
@@ -272,17 +223,13 @@ __global__ __launch_bounds__(kSpBlock) void k_scene_points(ScenePointsParams P, 
   }
 }
 
-void launch_scene_points(const ScenePointsParams& P, int first, int n_scenes, const double* times,
-                         const double* static_points, const int* static_counts, const double* dyn_poly,
-                         const int* dyn_poly_counts, const double* dyn_traj, const int* dyn_traj_counts, double* points,
-                         int* point_count, int* scene_ok, hipStream_t st) {
+void launch_scene_points(const ScenePointsParams& P, const cilqr_scene_batch& dv, int first, int n_scenes,
+                         const double* times, double* points, int* point_count, int* scene_ok, hipStream_t st) {
   if (n_scenes <= 0) return;
-  if ((reinterpret_cast<uintptr_t>(points) & 15) == 0)
-    hipLaunchKernelGGL(k_scene_points<true>, dim3(n_scenes), dim3(kSpBlock), 0, st, P, first, times, static_points,
-                       static_counts, dyn_poly, dyn_poly_counts, dyn_traj, dyn_traj_counts, points, point_count, scene_ok);
-  else
-    hipLaunchKernelGGL(k_scene_points<false>, dim3(n_scenes), dim3(kSpBlock), 0, st, P, first, times, static_points,
-                       static_counts, dyn_poly, dyn_poly_counts, dyn_traj, dyn_traj_counts, points, point_count, scene_ok);
+  const auto kernel = (reinterpret_cast<uintptr_t>(points) & 15) == 0 ? k_scene_points<true> : k_scene_points<false>;
+  hipLaunchKernelGGL(kernel, dim3(n_scenes), dim3(kSpBlock), 0, st, P, first, times, dv.static_points, dv.static_counts,
+                     dv.dynamic_polygon_points, dv.dynamic_polygon_counts, dv.dynamic_trajectories,
+                     dv.dynamic_trajectory_counts, points, point_count, scene_ok);
 }
 
 // ------------------------------------------------------------------------------------------

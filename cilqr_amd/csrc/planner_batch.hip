@@ -5,7 +5,6 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/cilqr/dp_planner.hpp"
 #include "dp_core.hpp"
 #include "scene_batch.hpp"
 
@@ -37,19 +36,8 @@ int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const 
   if (on_host && !cilqr::host_counts_valid(sb)) return CILQR_ERR_ARG;
 
   // ---- the lattice and the road, by the host planner's own constructors
-  cilqr::DpConfig d;
-  d.tf = cfg->tf; d.delta_t = cfg->delta_t; d.dp_nominal_velocity = cfg->dp_nominal_velocity; d.dp_w_obstacle = cfg->dp_w_obstacle;
-  d.dp_w_lateral = cfg->dp_w_lateral; d.dp_w_lateral_change = cfg->dp_w_lateral_change;
-  d.dp_w_lateral_velocity_change = cfg->dp_w_lateral_velocity_change;
-  d.dp_w_longitudinal_velocity_bias = cfg->dp_w_longitudinal_velocity_bias;
-  d.dp_w_longitudinal_velocity_change = cfg->dp_w_longitudinal_velocity_change;
-  d.front_hang_length = cfg->front_hang_length; d.wheel_base = cfg->wheel_base; d.rear_hang_length = cfg->rear_hang_length;
-  d.width = cfg->width; d.max_velocity = cfg->max_velocity;
-  std::vector<std::array<double, 7>> center(sb.n_center);
-  for (int i = 0; i < sb.n_center; ++i)
-    for (int e = 0; e < 7; ++e) center[i][e] = sb.center[(size_t)i * 7 + e];
-  const cilqr::ReferenceLine ref(center);
-  const cilqr::DpEnvironment env(d, ref);
+  const cilqr::DpConfig d = cilqr::dp_config_of(*cfg);
+  const cilqr::DpEnvironment env(d, cilqr::reference_line_of(sb.center, sb.n_center));
   const cilqr::DpPlanner dp(d, &env);
   DpParams P;
   std::memset(&P, 0, sizeof(P));
@@ -133,10 +121,8 @@ int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const 
   int* placed_n = s_placed_n.in<int>(h->dp_placed.get());
   for (size_t first = 0; first < B; first += chunk) {
     const int n = (int)std::min(chunk, B - first);
-    cilqr::launch_dp_place(P, (int)first, n, dv.dynamic_polygon_points, dv.dynamic_polygon_counts, dv.dynamic_trajectories,
-                           dv.dynamic_trajectory_counts, placed, placed_n, st);
-    cilqr::launch_dp_plan(P, (int)first, n, d_start, dv.static_points, dv.static_counts, dv.dynamic_polygon_counts,
-                          dv.dynamic_trajectory_counts, placed, placed_n, d_c9, d_c6, d_k3, d_stn, d_found, d_fail, st);
+    cilqr::launch_dp_place(P, dv, (int)first, n, placed, placed_n, st);
+    cilqr::launch_dp_plan(P, dv, (int)first, n, d_start, placed, placed_n, d_c9, d_c6, d_k3, d_stn, d_found, d_fail, st);
   }
   HIP_TRY(hipGetLastError());
   if (on_host) {

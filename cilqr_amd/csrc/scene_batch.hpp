@@ -1,9 +1,35 @@
-// Private to cilqr_amd/csrc: what the entry points that take a cilqr_scene_batch (planner_batch.hip, scene_pipeline.hip)
-// share -- the checks on the batch, in the order every one of them makes them, and the device image of a HOST batch.
+// Private to cilqr_amd/csrc: what the entry points that take a cilqr_scene_batch (planner_batch.hip, scene_pipeline.hip,
+// collision_batch.hip, clearance_batch.hip; frenet_batch.hip and resample_batch.hip for the checks on the handle) share --
+// the checks on the batch, in the order every one of them makes them, and the device image of a HOST batch -- and what
+// they and the calls on one scene (host_planner.hip) hand to the host planner's classes: its configuration and its road.
 #pragma once
+#include <array>
+#include <vector>
+
+#include "../../include/cilqr/dp_planner.hpp"
 #include "staging.hpp"
 
 namespace cilqr {
+
+inline DpConfig dp_config_of(const cilqr_dp_config& c) {
+  DpConfig d;
+  d.tf = c.tf; d.delta_t = c.delta_t; d.dp_nominal_velocity = c.dp_nominal_velocity; d.dp_w_obstacle = c.dp_w_obstacle;
+  d.dp_w_lateral = c.dp_w_lateral; d.dp_w_lateral_change = c.dp_w_lateral_change;
+  d.dp_w_lateral_velocity_change = c.dp_w_lateral_velocity_change;
+  d.dp_w_longitudinal_velocity_bias = c.dp_w_longitudinal_velocity_bias;
+  d.dp_w_longitudinal_velocity_change = c.dp_w_longitudinal_velocity_change;
+  d.front_hang_length = c.front_hang_length; d.wheel_base = c.wheel_base; d.rear_hang_length = c.rear_hang_length;
+  d.width = c.width; d.max_velocity = c.max_velocity;
+  return d;
+}
+
+// center [n][7]: s x y theta kappa left_bound right_bound
+inline ReferenceLine reference_line_of(const double* center, int n) {
+  std::vector<std::array<double, 7>> rows(n);
+  for (int i = 0; i < n; ++i)
+    for (int e = 0; e < 7; ++e) rows[i][e] = center[(size_t)i * 7 + e];
+  return ReferenceLine(rows);
+}
 
 // shape, memory kind, the arrays the shape asks for
 inline int check_scene_batch(const cilqr_scene_batch& sb) {

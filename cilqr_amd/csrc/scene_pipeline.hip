@@ -24,13 +24,6 @@ ScenePointsParams points_params(const cilqr_scene_batch& sb, int n_knots, int ma
   return ScenePointsParams{n_knots, sb.max_static, sb.max_dynamic, sb.max_vertices, sb.max_samples, max_points, per_vertex};
 }
 
-void launch_points(const ScenePointsParams& P, const cilqr_scene_batch& dv, int first, int n, const double* d_times,
-                   double* points, int* point_count, int* scene_ok, hipStream_t st) {
-  launch_scene_points(P, first, n, d_times, dv.static_points, dv.static_counts, dv.dynamic_polygon_points,
-                      dv.dynamic_polygon_counts, dv.dynamic_trajectories, dv.dynamic_trajectory_counts, points, point_count,
-                      scene_ok, st);
-}
-
 // the pinned block sp_host: the knot times of the longest trajectory, then the pipeline's two outcome counts
 struct HostBlock {
   block_layout l;
@@ -71,7 +64,7 @@ extern "C" int cilqr_scene_points_batch(cilqr_handle h, const cilqr_scene_batch*
   const ScenePointsParams P = points_params(sb, n_knots, max_points, per_vertex);
   const double* d_times = h->sp_tab.as<double>();
   if (!on_host) {
-    launch_points(P, sb, 0, sb.batch, d_times, points, point_count, scene_ok, st);
+    launch_scene_points(P, sb, 0, sb.batch, d_times, points, point_count, scene_ok, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));   // this stream alone: solves on other handles go on
     return CILQR_OK;
@@ -86,7 +79,7 @@ extern "C" int cilqr_scene_points_batch(cilqr_handle h, const cilqr_scene_batch*
   if (int rc = im.upload(sb, h->sp_in.as<char>(), st, &dv)) return rc;
   char* bo = h->sp_out.as<char>();
   if (int rc = copy_in(bo, s_pts, points, st)) return rc;
-  launch_points(P, dv, 0, sb.batch, d_times, s_pts.in<double>(bo), s_cnt.in<int>(bo), s_ok.in<int>(bo), st);
+  launch_scene_points(P, dv, 0, sb.batch, d_times, s_pts.in<double>(bo), s_cnt.in<int>(bo), s_ok.in<int>(bo), st);
   HIP_TRY(hipGetLastError());
   if (int rc = copy_out(points, bo, s_pts, st)) return rc;
   if (int rc = copy_out(point_count, bo, s_cnt, st)) return rc;
@@ -183,7 +176,7 @@ extern "C" int cilqr_plan_scenes_batch(cilqr_handle h, const cilqr_dp_config* dp
   int* d_pcnt = s_pcnt.in<int>(h->ps_points.get());
   for (size_t first = 0; first < B; first += chunk) {
     const int n = (int)std::min(chunk, B - first);
-    launch_points(P, dv, (int)first, n, h->sp_tab.as<double>(), d_pts, d_pcnt, nullptr, st);
+    launch_scene_points(P, dv, (int)first, n, h->sp_tab.as<double>(), d_pts, d_pcnt, nullptr, st);
     HIP_TRY(hipGetLastError());
     if (int rc = cilqr_build_corridors(h, corridor_cfg, n, n_knots, d_k3 + first * K * 3, d_pts, d_pcnt, max_points,
                                        d_cor + first * K * cmax * 3, d_ccnt + first * K, (int32_t)cmax, CILQR_MEM_DEVICE,

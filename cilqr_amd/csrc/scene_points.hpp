@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/cilqr.h"
+
 namespace cilqr {
 
 struct ScenePointsParams {
@@ -13,12 +15,10 @@ struct ScenePointsParams {
   int per_vertex;                                           // 1: the polygons' corners; 6: Polygon2d::sample_points
 };
 
-// Scenes [first, first + n_scenes) of the batch arrays; the outputs start at the FIRST of these scenes:
-// points [n_scenes][K][max_points][2], point_count [n_scenes][K], scene_ok [n_scenes] (may be null).
-void launch_scene_points(const ScenePointsParams& P, int first, int n_scenes, const double* times,
-                         const double* static_points, const int* static_counts, const double* dyn_poly,
-                         const int* dyn_poly_counts, const double* dyn_traj, const int* dyn_traj_counts, double* points,
-                         int* point_count, int* scene_ok, hipStream_t st);
+// Scenes [first, first + n_scenes) of `dv`, the batch with its arrays on the device; the outputs start at the FIRST of
+// these scenes: points [n_scenes][K][max_points][2], point_count [n_scenes][K], scene_ok [n_scenes] (may be null).
+void launch_scene_points(const ScenePointsParams& P, const cilqr_scene_batch& dv, int first, int n_scenes,
+                         const double* times, double* points, int* point_count, int* scene_ok, hipStream_t st);
 
 // start4 [B][4] x y theta v  ->  start3 [B][3] x y theta (the start of cilqr_dp_plan_batch)
 void launch_plan_start3(int B, const double* start4, double* start3, hipStream_t st);

@@ -270,14 +270,6 @@ struct CorridorParams {
 void launch_build_corridors(int n, const CorridorParams& cp, const double* knots, const double* points,
                             const int* count, int pmax, double* corridor, int* ccount, int cmax, int* n_failed,
                             double* polygons, hipStream_t st);
-// batched DP coarse planner (kernels_dp.hip; DpParams: dp_core.hpp)
-struct DpParams;
-void launch_dp_place(const DpParams& P, int first, int n_scenes, const double* dyn_poly, const int* dyn_poly_counts,
-                     const double* dyn_traj, const int* dyn_traj_counts, double* placed, int* placed_n, hipStream_t st);
-void launch_dp_plan(const DpParams& P, int first, int n_scenes, const double* start3, const double* static_points,
-                    const int* static_counts, const int* dyn_poly_counts, const int* dyn_traj_counts, const double* placed,
-                    const int* placed_n, double* coarse9, double* coarse6, double* knots3, double* station, int* found,
-                    int* n_not_found, hipStream_t st);
 void launch_device_math(int fn, int n, const double* in, double* out, hipStream_t st);
 void launch_rollout(const Params& p, int B, const double* x0, const double* U, double* X, hipStream_t st);
 // stage_read helpers: gather a batch-fastest tensor into problem-major order

@@ -22,6 +22,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import limit_scenes
 from cilqr_amd import api, scenario, scene_io
 from oracle import oracle as orc
 
@@ -242,6 +243,69 @@ def test_a_blocked_road_inside_a_batch():
     ok, co = api.dp_plan(scene_io.flatten_scene(sf.center, scenes[5]), sc["start"][5, :3], cfg)
     assert not ok and np.array_equal(walled["dp"][5][:, :2], co[:, :2])
     assert np.abs(walled["dp"][5][:, 2:5] - co[:, 2:5]).max() < 1e-9
+
+
+def _sample_pick_scenes(cfg):
+    """Four scenes for the pick of a dynamic obstacle's sample (k_dp_place bisects, the host planner scans): each keeps
+    its start and carries ONE dynamic obstacle, 8 m long and 4 m wide, with T = 1, 2, 3 and 1024 samples, that stands on
+    the path the host planner takes through the empty scene, where the ego is at a time the sample is shown.
+    Neighbouring samples stand at different places, so another index is another obstacle.  ts: the planner's own
+    path-sample times.  Returns (generator dict, the scenes, the plans through the empty scenes)."""
+    sc, sf = _scenes("mix11", 4, 57)
+    ts = limit_scenes.dp_sample_times(5.0)
+    road = sc["road"]
+    body = np.array([[4.0, 2.0], [-4.0, 2.0], [-4.0, -2.0], [4.0, -2.0]])   # wider than a collision square: none passes through unseen
+    bare = scene_io.SceneFile(sf.dt, sf.center, [scene_io.Scene(s.start.copy(), s.coarse.copy(), [], []) for s in sf.scenes])
+    b_found, b_dp = _host_plan(bare, sc["start"], cfg, workers=4)
+    assert b_found.all()
+
+    def on_path(b, times, ego_times):
+        """samples at `times` that stand where the ego of the empty scene b is at `ego_times`"""
+        x, y, th = (np.interp(ego_times, b_dp[b][:, 0], b_dp[b][:, c]) for c in (2, 3, 4))
+        return np.ascontiguousarray(np.stack([np.asarray(times, dtype=float), x, y, th], axis=1))
+
+    # T = 1: there at one path-sample time alone; the sample behind the end is the last (and only) one
+    t1 = on_path(0, [ts[12]], [ts[12]])
+    # T = 2: from a path-sample time to the LAST path-sample time, both exactly; sample 0 is never the first behind a time
+    t2 = on_path(1, [ts[4], ts[-1]], [1.0, 3.0])
+    # T = 3: the run of two equal times IS a path-sample time: before it sample 1, at it the clamp to sample 2
+    t3 = on_path(2, [ts[2], ts[20], ts[20]], [0.5, 1.5, ts[20]])
+    # T = 1024: ascending to the last path-sample time exactly, with a run of five equal times on a path-sample time, four
+    # more samples on path-sample times; the obstacle drives ahead of the ego on the centre line at 5 m/s, and every sample
+    # from the run's end on stands 1.5 m further to the right
+    tt = np.empty(1024)
+    tt[:500] = np.linspace(-0.5, np.nextafter(ts[24], 0.0), 500)
+    tt[500:505] = ts[24]
+    tt[505:] = np.linspace(np.nextafter(ts[24], 9.0), ts[-1], 519)
+    for j in (7, 15, 33, 41):
+        tt[np.searchsorted(tt, ts[j])] = ts[j]
+    assert np.all(np.diff(tt) >= 0) and tt[-1] == ts[-1] and (tt == ts[24]).sum() == 5 and all((tt == ts[j]).any() for j in (7, 15, 33, 41))
+    s0 = float(road.s[np.argmin((road.x - sf.scenes[3].start[0]) ** 2 + (road.y - sf.scenes[3].start[1]) ** 2)])
+    x, y, th, _ = road.eval(s0 + 10.0 + 5.0 * (tt + 0.5))
+    lateral = np.where(np.arange(1024) >= 504, -1.5, 0.0)
+    t1024 = np.ascontiguousarray(np.stack([tt, x - lateral * np.sin(th), y + lateral * np.cos(th), th], axis=1))
+    scenes = [scene_io.Scene(sf.scenes[b].start.copy(), sf.scenes[b].coarse.copy(), [], [scene_io.DynamicObstacle(body, t)])
+              for b, t in enumerate((t1, t2, t3, t1024))]
+    return sc, scene_io.SceneFile(sf.dt, sf.center, scenes), b_dp
+
+
+def test_the_bisected_sample_is_the_scanned_one_at_ties_runs_and_the_clamp():
+    """k_dp_place picks a dynamic obstacle's sample by bisection, cilqr_dp_plan by a scan from the front: on T = 1, 2, 3 and
+    1024 non-decreasing sample times -- sample times equal to path-sample times, a run of equal times on one, the last
+    sample time equal to the last path-sample time -- the same plan, bit for bit in the time and station columns (rules 3
+    and 4, no scene excepted).  Preconditions, asserted: the host planner finds a path in every scene, and the obstacle
+    moves that path (by more than 0.5 m somewhere), so the sample that is picked matters."""
+    cfg = api.default_dp_config(tf=5.0)
+    sc, sf, b_dp = _sample_pick_scenes(cfg)
+    assert [len(s.dynamic[0].trajectory) for s in sf.scenes] == [1, 2, 3, 1024]
+    h_found, h_dp = _host_plan(sf, sc["start"], cfg, workers=4)
+    assert h_found.all()
+    moved = [float(np.abs(h_dp[b][:, 2:4] - b_dp[b][:, 2:4]).max()) for b in range(4)]
+    assert min(moved) > 0.5, moved
+    with api.BatchIlqrOptimizer(n_steps=50, batch_capacity=1, cmax=16) as opt:
+        r = opt.dp_plan_batch(scene_io.pack_scene_batch(sf.center, sf.scenes), sc["start"], cfg)
+    rec = _compare(r["found"], r["dp"], h_found, h_dp, sf.scenes, sc["start"], 0.1, "sample pick: T = 1, 2, 3, 1024")
+    assert rec["other_plan"] == [] and r["found"].all()
 
 
 def test_non_default_weights_and_vehicle_reach_the_kernel():
