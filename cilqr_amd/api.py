@@ -136,6 +136,14 @@ FRENET_ROWS_FIELDS = {**ROWS_FIELDS, ROWS_POINTS: 2}
 # cilqr_clearance_rows / cilqr_clearance_rows_batch: the columns of a knot's row (CILQR_CLEARANCE_FIELDS)
 CLEARANCE_FIELDS = 4
 CLEAR_REAR_STATIC, CLEAR_REAR_DYNAMIC, CLEAR_FRONT_STATIC, CLEAR_FRONT_DYNAMIC = 0, 1, 2, 3
+# cilqr_constraint_margins / cilqr_constraint_margins_batch: the columns of a knot's row (CILQR_MARGIN_FIELDS), of its
+# deciders (CILQR_MARGIN_WHICH_FIELDS) and the bits of a problem's mask (CILQR_MARGIN_BIT_*, bit f = column f)
+MARGIN_FIELDS, MARGIN_WHICH_FIELDS = 8, 6
+MARGIN_CORRIDOR, MARGIN_LEFT_LANE, MARGIN_RIGHT_LANE, MARGIN_VELOCITY, MARGIN_ACCELERATION, MARGIN_STEERING, MARGIN_JERK, \
+    MARGIN_STEERING_RATE = range(8)
+MARGIN_NAMES = ("corridor", "left_lane", "right_lane", "velocity", "acceleration", "steering", "jerk", "steering_rate")
+MARGIN_BIT_CORRIDOR, MARGIN_BIT_LEFT_LANE, MARGIN_BIT_RIGHT_LANE, MARGIN_BIT_VELOCITY, MARGIN_BIT_ACCELERATION, \
+    MARGIN_BIT_STEERING, MARGIN_BIT_JERK, MARGIN_BIT_STEERING_RATE = (1 << f for f in range(8))
 
 
 class TrackerConfig(C.Structure):
@@ -170,6 +178,7 @@ EXPORTS = [
     "cilqr_check_collisions", "cilqr_check_collisions_batch", "cilqr_resample_rows", "cilqr_resample_rows_batch",
     "cilqr_frenet_rows", "cilqr_cartesian_points", "cilqr_frenet_rows_batch", "cilqr_cartesian_points_batch",
     "cilqr_clearance_rows", "cilqr_clearance_rows_batch",
+    "cilqr_constraint_margins", "cilqr_constraint_margins_batch",
     "cilqr_road_barriers", "cilqr_default_tracker_config",
     "cilqr_set_tracker_config",
     "cilqr_solve_batch_warm", "cilqr_submit_warm", "cilqr_stage_load_warm", "cilqr_pool_submit_warm", "cilqr_multi_solve_warm",
@@ -267,6 +276,12 @@ def lib():
         L.cilqr_clearance_rows_batch.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(SceneBatchStruct), C.c_int32,
                                                  C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_double, C.POINTER(C.c_int32)]
+        L.cilqr_constraint_margins.argtypes = [C.POINTER(Config), C.c_int32, C.POINTER(ProblemBatch), C.c_int32, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(C.c_int32)]
+        L.cilqr_constraint_margins_batch.argtypes = [C.c_void_p, C.POINTER(ProblemBatch), C.c_int32, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(C.c_int32)]
         L.cilqr_default_tracker_config.argtypes = [C.POINTER(TrackerConfig)]
         L.cilqr_default_tracker_config.restype = None
         L.cilqr_set_tracker_config.argtypes = [C.c_void_p, C.POINTER(TrackerConfig)]
@@ -829,6 +844,37 @@ class BatchIlqrOptimizer:
                                                min_knot_ptr, C.c_double(threshold), C.byref(n))
         return rc, int(n.value)
 
+    def constraint_margins(self, scene_or_problem, rows, layout: int, tol=None, per_knot: bool = True):
+        """How far every knot of a batch of trajectories stays inside the constraints of its own solve -- corridor planes,
+        left / right lane, velocity, acceleration, steering, jerk, steering rate -- on the GPU
+        (cilqr_constraint_margins_batch), host arrays.  scene_or_problem: the dict a plan() takes (corridor, ccount, left,
+        right, optionally lane_groups; start and coarse are not read), rows [B,K,F] in `layout` (ROWS_TRAJ / ROWS_PLAN /
+        ROWS_COARSE), tol: None or 8 non-negative values.  Returns dict(margins [B,K,8] and which [B,K,6] int32 (with
+        per_knot), min_margin [B,8], min_knot [B,8] int32 (-1: +inf throughout), violated [B] uint32 (bit f: min_margin[f] <
+        -tol[f]), n_violating)."""
+        rows = _f64(rows)
+        if rows.ndim != 3 or rows.shape[2] != ROWS_FIELDS.get(layout, rows.shape[2]):
+            raise ValueError(f"rows must be [B, K, {ROWS_FIELDS.get(layout)}]")
+        B, K = rows.shape[:2]
+        prob, keep = margin_problem(scene_or_problem, B, K)
+        out = _margin_outputs(B, K, per_knot)
+        tol = None if tol is None else _f64(tol).ravel()
+        rc, n = self.constraint_margins_raw(prob, layout, _ptr(rows), _ptr(out.get("margins")), _ptr(out.get("which")),
+                                            _ptr(out["min_margin"]), _ptr(out["min_knot"]), _ptr(tol), _ptr(out["violated"]))
+        self._chk(rc, "constraint_margins")
+        return dict(out, n_violating=n)
+
+    def constraint_margins_raw(self, prob: ProblemBatch, layout, rows_ptr, margins_ptr, which_ptr, min_margin_ptr, min_knot_ptr,
+                               tol_ptr, violated_ptr):
+        """Pointer-level form: rows and the five outputs in device or host memory as prob.memory says (a solve's traj is
+        measured where it lies; margins_ptr and which_ptr may be None), tol_ptr host memory or None; returns
+        (rc, n_violating)."""
+        n = C.c_int32(0)
+        rc = self.L.cilqr_constraint_margins_batch(self.h, C.byref(prob) if prob is not None else None, layout, rows_ptr,
+                                                   margins_ptr, which_ptr, min_margin_ptr, min_knot_ptr, tol_ptr, violated_ptr,
+                                                   C.byref(n))
+        return rc, int(n.value)
+
     def resample(self, rows, layout: int, queries, key: int = KEY_TIME):
         """DiscretizedTrajectory::EvaluateTime / EvaluateStation for a batch of trajectories on the GPU
         (cilqr_resample_rows_batch).  rows [B,K,F] in `layout` (ROWS_TRAJ / ROWS_PLAN / ROWS_COARSE); queries [M] -- one axis
@@ -1010,6 +1056,59 @@ def clearance_rows(flat: dict, rows, layout: int, cfg: "DpConfig | None" = None)
     if rc != OK:
         raise CilqrError(rc, "in cilqr_clearance_rows")
     return clearance, nearest, float(lowest.value), int(knot.value)
+
+
+def margin_problem(scene: dict, B: int, K: int):
+    """The ProblemBatch the margin calls read, from the dict a plan() takes: corridor [B,K,cmax,3], ccount [B,K], left / right
+    [n,7] and optionally lane_groups [(first problem, left rows, right rows), ...].  Returns (ProblemBatch, what must stay
+    alive while it is used)."""
+    a = dict(corridor=_f64(scene["corridor"]), ccount=np.ascontiguousarray(scene["ccount"], dtype=np.int32),
+             left=_f64(scene["left"]), right=_f64(scene["right"]))
+    if a["corridor"].ndim != 4 or a["corridor"].shape[:2] != (B, K) or a["corridor"].shape[3] != 3 or a["ccount"].shape != (B, K):
+        raise ValueError(f"corridor must be [{B}, {K}, cmax, 3] and ccount [{B}, {K}]")
+    cmax = a["corridor"].shape[2]
+    prob = ProblemBatch(B, K, cmax, MEM_HOST, None, None, _ptr(a["corridor"]) if a["corridor"].size else None,
+                        _ptr(a["ccount"]), a["left"].shape[0], a["right"].shape[0],
+                        _ptr(a["left"]) if a["left"].size else None, _ptr(a["right"]) if a["right"].size else None)
+    groups = scene.get("lane_groups")
+    if groups is not None:
+        a["g_start"] = np.asarray([g[0] for g in groups] + [B], dtype=np.int32)
+        a["g_left"] = np.asarray([g[1] for g in groups], dtype=np.int32)
+        a["g_right"] = np.asarray([g[2] for g in groups], dtype=np.int32)
+        prob.n_lane_groups = len(groups)
+        prob.lane_group_start = a["g_start"].ctypes.data
+        prob.lane_group_left = a["g_left"].ctypes.data
+        prob.lane_group_right = a["g_right"].ctypes.data
+    return prob, a
+
+
+def _margin_outputs(B: int, K: int, per_knot: bool) -> dict:
+    out = dict(min_margin=np.zeros((B, MARGIN_FIELDS)), min_knot=np.zeros((B, MARGIN_FIELDS), dtype=np.int32),
+               violated=np.zeros(B, dtype=np.uint32))
+    if per_knot:
+        out["margins"] = np.zeros((B, K, MARGIN_FIELDS))
+        out["which"] = np.zeros((B, K, MARGIN_WHICH_FIELDS), dtype=np.int32)
+    return out
+
+
+def constraint_margins(cfg: Config, scene_or_problem, rows, layout: int, tol=None, exact_ties: bool = True,
+                       per_knot: bool = True) -> dict:
+    """BatchIlqrOptimizer.constraint_margins through the host call (cilqr_constraint_margins; no device): the same
+    arguments and the same dict, with the configuration and the lane-tie rule given instead of a handle's."""
+    rows = _f64(rows)
+    if rows.ndim != 3 or rows.shape[2] != ROWS_FIELDS.get(layout, rows.shape[2]):
+        raise ValueError(f"rows must be [B, K, {ROWS_FIELDS.get(layout)}]")
+    B, K = rows.shape[:2]
+    prob, keep = margin_problem(scene_or_problem, B, K)
+    out = _margin_outputs(B, K, per_knot)
+    tol = None if tol is None else _f64(tol).ravel()
+    n = C.c_int32(0)
+    rc = lib().cilqr_constraint_margins(C.byref(cfg), int(bool(exact_ties)), C.byref(prob), layout, _ptr(rows),
+                                        _ptr(out.get("margins")), _ptr(out.get("which")), _ptr(out["min_margin"]),
+                                        _ptr(out["min_knot"]), _ptr(tol), _ptr(out["violated"]), C.byref(n))
+    if rc != OK:
+        raise CilqrError(rc, "in cilqr_constraint_margins")
+    return dict(out, n_violating=int(n.value))
 
 
 def resample_rows(rows, layout: int, queries, key: int = KEY_TIME) -> np.ndarray:

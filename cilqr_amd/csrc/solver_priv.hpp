@@ -264,6 +264,11 @@ struct cilqr_solver {
   // back, the staging of HOST scenes and rows, of HOST results
   cilqr::pinned_mem cl_tab_host;
   cilqr::dev_mem cl_tab, cl_in, cl_out;
+  // cilqr_constraint_margins_batch (margins_batch.hip), grown likewise: the count of violating problems and the raw lane
+  // tables on their way to the device (the prepared lane rows behind them), the staging of HOST rows, planes and counts,
+  // of HOST results.  Nothing of the staged or solver state is read or written by that call.
+  cilqr::pinned_mem mg_tab_host;
+  cilqr::dev_mem mg_tab, mg_in, mg_out;
 };
 
 namespace cilqr {

@@ -772,6 +772,82 @@ int cilqr_clearance_rows_batch(cilqr_handle h, const cilqr_dp_config* cfg, const
                                double* min_clearance /* [B] */, int32_t* min_knot /* [B] */,
                                double threshold, int32_t* n_below /* HOST, optional */);
 
+/* ---- constraint margins: how far a trajectory stays inside the constraints of its own solve (additive, ABI 7) ----
+ * The solver enforces the corridor half-planes, the two lane tables and the state / control bounds as relaxed-log barriers
+ * (quadratic for g > -barrier_eps, finite for g > 0), so a returned trajectory -- status 1 and 2 included, 4 and 5 the more
+ * so -- may sit on the wrong side of a constraint.  These calls evaluate every constraint the solve was given on rows in
+ * one of the CILQR_ROWS_TRAJ / _PLAN / _COARSE layouts (CILQR_ROWS_POINTS is refused) and reduce them per problem.
+ * Every value is a MARGIN in physical units: >= 0 satisfied, < 0 violated.  Per knot i, D = cfg.num_of_disc; every
+ * operation is rounded once (no fused multiply-add); hypot is the C library's evaluation for lengths in metres:
+ *   disc centres   p_j = (x, y) + disc_off[j] (cos theta, sin theta), disc_off[j] = L (j - 0.5) - rear_hang,
+ *                  L = (rear_hang + wheel_base + front_hang) / D   (cc:556-565).
+ *   corridor plane the first n = max(0, min(corridor_count[i], in->cmax)) planes of the knot.  Each is shrunk and normalised
+ *                  as the solver does it (cc:448, 479): c' = c - (disc_radius + safe_margin) (a a + b b) / hypot(a, b),
+ *                  nrm = hypot(hypot(a, b), c'), (a_n, b_n, c_n) = (a, b, c') / nrm; if one of the three is not finite the
+ *                  plane is (0, 0, -inf).  g = a_n px + b_n py - c_n, m = -g / hypot(a_n, b_n): metres, with exactly the
+ *                  sign of the -g the cost sees.  A degenerate plane gives -inf.
+ *   column 0       corridor: the minimum of m over the discs (outer loop) and the planes (inner loop), strict `<` from +inf:
+ *                  the first of equals wins.  n = 0 gives +inf.
+ *   columns 1, 2   left and right lane.  For every disc the segment FindNeastLaneSegment returns (cc:605-618:
+ *                  LineSegment2d::DistanceTo, strict `<`, the first index; with exact lane ties off, the same cases compared
+ *                  on squared distances alone, see CILQR_OPT_EXACT_LANE_TIES); its plane shrunk by disc_radius and
+ *                  normalised in the same way (no rule for a non-finite result), the same m.  The column is the minimum
+ *                  over the discs, the first of equals.
+ *   columns 3 .. 7 velocity, acceleration, steering, jerk, steering rate: m = -g for the two g of the family as
+ *                  DynamicsCost writes them (cc:523-528, 543-546): (-v, v - max_velocity), (a - max_acceleration,
+ *                  min_acceleration - a), (delta - delta_max, delta_min - delta), (jerk - jerk_max, jerk_min - jerk),
+ *                  (rate - delta_rate_max, delta_rate_min - rate); the smaller of the two, the first of equals.  Jerk and
+ *                  steering rate are +inf at the last knot, and at every knot of a layout without control columns.
+ *   NaN            a NaN margin is replaced by -inf before any comparison: a NaN pose never passes as feasible.
+ *   columns read   CILQR_ROWS_TRAJ x 1 y 2 theta 3 v 4 a 5 delta 6 jerk 8 rate 9;  CILQR_ROWS_PLAN x 2 y 3 theta 4 v 6 a 7
+ *                  delta 8 jerk 9 rate 10;  CILQR_ROWS_COARSE x 2 y 3 theta 4 v 6 a 7 delta 8, no controls.
+ *   which          (optional) [K][CILQR_MARGIN_WHICH_FIELDS]: the deciders -- corridor disc, corridor plane, left disc, left
+ *                  segment, right disc, right segment (segments counted within the side's table of the problem's lane
+ *                  group); -1 where the column is +inf.
+ * Per problem: min_margin [8] = each column's minimum over the knots under the same strict `<`; min_knot [8] = the first
+ * knot attaining it, -1 if the column is +inf throughout; violated = a bit mask, bit f (CILQR_MARGIN_BIT_*) set when
+ * min_margin[f] < -tol[f].  tol [8]: HOST memory, optional (NULL: zeros), every entry finite and >= 0.  Per call:
+ * *n_violating (HOST, optional) = the problems with a non-zero mask.
+ * Of `in` the calls read batch, n_knots, cmax, memory, corridor, corridor_count and the lane tables with their groups (as
+ * cilqr_solve_batch reads them); start, coarse and coarse_station are ignored and may be NULL.
+ * cilqr_constraint_margins: the host call, in->memory == CILQR_MEM_HOST, any batch and any n_knots >= 1; the C library's cos
+ * and sin; exact_lane_ties as CILQR_OPT_EXACT_LANE_TIES.  CILQR_ERR_NULL; CILQR_ERR_ARG for batch / n_knots < 1, an unknown
+ * layout or memory flag, DEVICE memory, a tol entry that is negative or not finite, num_of_disc outside 1 .. CILQR_MAX_DISCS,
+ * inconsistent lane groups; CILQR_ERR_CONSTRAINTS for missing corridor / lane arrays, cmax < 1 or an empty lane table, as a
+ * solve.  C++ callers use include/cilqr/constraint_margins.hpp directly. */
+#define CILQR_MARGIN_FIELDS 8
+#define CILQR_MARGIN_WHICH_FIELDS 6
+#define CILQR_MARGIN_BIT_CORRIDOR 0x01u
+#define CILQR_MARGIN_BIT_LEFT_LANE 0x02u
+#define CILQR_MARGIN_BIT_RIGHT_LANE 0x04u
+#define CILQR_MARGIN_BIT_VELOCITY 0x08u
+#define CILQR_MARGIN_BIT_ACCELERATION 0x10u
+#define CILQR_MARGIN_BIT_STEERING 0x20u
+#define CILQR_MARGIN_BIT_JERK 0x40u
+#define CILQR_MARGIN_BIT_STEERING_RATE 0x80u
+int cilqr_constraint_margins(const cilqr_config* cfg, int32_t exact_lane_ties, const cilqr_problem_batch* in, int32_t layout,
+                             const double* rows, double* margins /* [B][K][8], optional */,
+                             int32_t* which /* [B][K][6], optional */, double* min_margin /* [B][8] */,
+                             int32_t* min_knot /* [B][8] */, const double* tol /* [8], optional */,
+                             uint32_t* violated /* [B] */, int32_t* n_violating /* optional */);
+/* ---- the same on the GPU (kernels_margins.hip) ----
+ * One workgroup per problem reads the raw problem-major corridor where it lies.  rows and every per-problem output live in
+ * in->memory.  The configuration, disc_off, the two shrink distances and the lane-tie rule are the handle's
+ * (CILQR_OPT_EXACT_LANE_TIES as in force); in->n_knots and in->batch are NOT tied to the handle's n_steps or batch_capacity.
+ * in->cmax above the handle's cmax, or a lane table above its max_lane_segments: CILQR_ERR_CAPACITY, as a solve.  The
+ * arithmetic is the host call's except for the heading, which goes through the cost kernels' sin / cos (cilqr_device_math fn
+ * 3 / 4): the bound columns are the host call's bits, the plane columns differ by the rounding of the disc centres only.
+ * A problem's result does not depend on the batch around it.
+ * Checked before anything is launched: the checks of the host call, and CILQR_ERR_STATE while solves are submitted on the
+ * handle.  The call works in blocks of its own that belong to the handle and grow to the largest call; it touches neither
+ * the staged nor the solver state (a cilqr_stage_* sequence around it sees nothing), runs on the handle's stream and waits for
+ * that stream only. */
+int cilqr_constraint_margins_batch(cilqr_handle h, const cilqr_problem_batch* in, int32_t layout, const double* rows,
+                                   double* margins /* [B][K][8], optional */, int32_t* which /* [B][K][6], optional */,
+                                   double* min_margin /* [B][8] */, int32_t* min_knot /* [B][8] */,
+                                   const double* tol /* HOST [8], optional */, uint32_t* violated /* [B] */,
+                                   int32_t* n_violating /* HOST, optional */);
+
 /* ---- TrajectoryPlanner::Plan for B scenes per call (trajectory_planner.cpp:28-162) ----
  * scene batch -> cilqr_dp_plan_batch -> cilqr_scene_points_batch (at the time column the planner produced, with
  * corridor_cfg->is_multiple_sample and the worst-case max_points) -> cilqr_build_corridors (the cmax of the handle's
