@@ -179,6 +179,7 @@ EXPORTS = [
     "cilqr_frenet_rows", "cilqr_cartesian_points", "cilqr_frenet_rows_batch", "cilqr_cartesian_points_batch",
     "cilqr_clearance_rows", "cilqr_clearance_rows_batch",
     "cilqr_constraint_margins", "cilqr_constraint_margins_batch",
+    "cilqr_track_rows", "cilqr_track_rows_batch",
     "cilqr_road_barriers", "cilqr_default_tracker_config",
     "cilqr_set_tracker_config",
     "cilqr_solve_batch_warm", "cilqr_submit_warm", "cilqr_stage_load_warm", "cilqr_pool_submit_warm", "cilqr_multi_solve_warm",
@@ -282,6 +283,10 @@ def lib():
         L.cilqr_constraint_margins_batch.argtypes = [C.c_void_p, C.POINTER(ProblemBatch), C.c_int32, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.POINTER(C.c_int32)]
+        L.cilqr_track_rows.argtypes = [C.POINTER(Config), C.POINTER(TrackerConfig), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_int32, C.c_void_p]
+        L.cilqr_track_rows_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
         L.cilqr_default_tracker_config.argtypes = [C.POINTER(TrackerConfig)]
         L.cilqr_default_tracker_config.restype = None
         L.cilqr_set_tracker_config.argtypes = [C.c_void_p, C.POINTER(TrackerConfig)]
@@ -913,6 +918,49 @@ class BatchIlqrOptimizer:
         return self.L.cilqr_resample_rows_batch(self.h, batch, layout, rows_ptr, n_knots, key, queries_ptr, n_queries,
                                                 int(per_problem), out_ptr, memory)
 
+    def track(self, rows, layout: int, start6=None, n_drive: int | None = None):
+        """Drive a vehicle along every trajectory of a batch with the closed-loop Tracker, on the GPU
+        (cilqr_track_rows_batch): rows [B,K,F] in `layout` (ROWS_TRAJ / ROWS_PLAN / ROWS_COARSE), each with its own time
+        column; start6 [B,6] = x y theta v a delta (None: row 0 of each trajectory); n_drive (None: K) rows are recorded.
+        The tracker configuration is set_tracker_config's, the vehicle the handle's.  NumPy arrays, or contiguous float64
+        device tensors (both of the same kind).  Returns (driven [B,n_drive,10] in ROWS_TRAJ layout, ok [B] int32) of that
+        kind: a failed problem (ok = 0) has all-zero rows (track_raw also returns their number)."""
+        on_device = _is_device_tensor(rows)
+        if start6 is not None and on_device != _is_device_tensor(start6):
+            raise ValueError("rows and start6 must both be NumPy arrays or both device tensors")
+        if on_device:
+            for t in (rows, start6):
+                if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64"):
+                    raise ValueError("rows / start6 on the device: contiguous float64 tensors")
+        else:
+            rows, start6 = _f64(rows), (None if start6 is None else _f64(start6))
+        if rows.ndim != 3 or rows.shape[2] != ROWS_FIELDS.get(layout, rows.shape[2]):
+            raise ValueError(f"rows must be [B, K, {ROWS_FIELDS.get(layout)}]")
+        B, K = int(rows.shape[0]), int(rows.shape[1])
+        if start6 is not None and tuple(start6.shape) != (B, 6):
+            raise ValueError(f"start6 must be [{B}, 6]")
+        D = K if n_drive is None else int(n_drive)
+        if on_device:
+            import torch
+            driven = torch.empty((B, max(D, 0), 10), dtype=torch.float64, device=rows.device)
+            ok = torch.empty((B,), dtype=torch.int32, device=rows.device)
+            ptrs = (rows.data_ptr(), None if start6 is None else start6.data_ptr(), driven.data_ptr(), ok.data_ptr())
+        else:
+            driven, ok = np.empty((B, max(D, 0), 10)), np.empty(B, np.int32)
+            ptrs = (rows.ctypes.data, None if start6 is None else start6.ctypes.data, driven.ctypes.data, ok.ctypes.data)
+        rc, _ = self.track_raw(B, layout, ptrs[0], K, ptrs[1], D, ptrs[2], ptrs[3], MEM_DEVICE if on_device else MEM_HOST)
+        self._chk(rc, "track")
+        return driven, ok
+
+    def track_raw(self, batch, layout, rows_ptr, n_knots, start6_ptr, n_drive, driven_ptr, ok_ptr, memory):
+        """Pointer-level form (rows / start6 / driven / ok in device or host memory as `memory` says: the `plan` rows of
+        plan_scenes_raw are followed where they lie, the driven rows feed check_collisions_raw, clearance_raw,
+        constraint_margins_raw, resample_raw and a warm start likewise); returns (code, number of failed problems)."""
+        n = C.c_int32(0)
+        rc = self.L.cilqr_track_rows_batch(self.h, batch, layout, rows_ptr, n_knots, start6_ptr, n_drive, driven_ptr, ok_ptr,
+                                           C.byref(n), memory)
+        return rc, int(n.value)
+
     def frenet(self, center, rows, layout: int = ROWS_POINTS):
         """DiscretizedTrajectory::GetProjection of every row of a batch of trajectories onto the centre line, on the GPU
         (cilqr_frenet_rows_batch).  center [n,7] (NumPy, host memory); rows [B,K,F] in `layout` (ROWS_TRAJ / ROWS_PLAN /
@@ -1123,6 +1171,29 @@ def resample_rows(rows, layout: int, queries, key: int = KEY_TIME) -> np.ndarray
     if rc != OK:
         raise CilqrError(rc, "in cilqr_resample_rows")
     return out
+
+
+def track_rows(cfg: Config, tracker_cfg: "TrackerConfig | None", rows, layout: int, start6=None, n_drive: int | None = None):
+    """The closed-loop Tracker for one trajectory through the C-ABI (cilqr_track_rows, host only): rows [K,F] in `layout`
+    (ROWS_*), start6 [6] = x y theta v a delta (None: row 0), n_drive (None: K) -> (driven [n_drive,10] in ROWS_TRAJ layout,
+    ok).  ok = False is the reference's "tacker failed": the rows are zero.  tracker_cfg None: the reference's defaults."""
+    rows = _f64(rows)
+    if rows.ndim != 2 or rows.shape[1] != ROWS_FIELDS.get(layout, rows.shape[1]):
+        raise ValueError(f"rows must be [K, {ROWS_FIELDS.get(layout)}]")
+    if tracker_cfg is None:
+        tracker_cfg = TrackerConfig()
+        lib().cilqr_default_tracker_config(C.byref(tracker_cfg))
+    start6 = None if start6 is None else _f64(start6).ravel()
+    if start6 is not None and start6.shape != (6,):
+        raise ValueError("start6 must be [6]")
+    K = rows.shape[0]
+    D = K if n_drive is None else int(n_drive)
+    driven = np.zeros((max(D, 0), 10))
+    rc = lib().cilqr_track_rows(C.byref(cfg), C.byref(tracker_cfg), layout, rows.ctypes.data, K, _ptr(start6), D,
+                                driven.ctypes.data)
+    if rc not in (OK, ERR_STATE):
+        raise CilqrError(rc, "in cilqr_track_rows")
+    return driven, rc == OK
 
 
 def _center_line(center) -> np.ndarray:

@@ -269,6 +269,10 @@ struct cilqr_solver {
   // of HOST results.  Nothing of the staged or solver state is read or written by that call.
   cilqr::pinned_mem mg_tab_host;
   cilqr::dev_mem mg_tab, mg_in, mg_out;
+  // cilqr_track_rows_batch (track_batch.hip), grown likewise: the count of failed problems and its way back, the follow
+  // table of the call (track.hpp), the staging of HOST rows and start states, of HOST driven rows and flags
+  cilqr::pinned_mem tk_tab_host;
+  cilqr::dev_mem tk_tab, tk_work, tk_in, tk_out;
 };
 
 namespace cilqr {

@@ -1,0 +1,275 @@
+// Private to cilqr_amd/csrc: the steps of the closed-loop tracker (Tracker::lqr, algorithm/ilqr/tracker.cc:169-215), stated
+// once for the two kernels that run them -- k_init_guess_tracker (kernels_tracker.hip: the init guess of a solve, which
+// follows the coarse trajectory of a loaded problem on the time axis i dt) and k_track_rows (kernels_track.hip:
+// cilqr_track_rows_batch, which follows caller's rows on their own time column).
+//
+// Reference behaviour: every step, CalcaulateInitState cc:19-55 projects a previewed point on the followed trajectory
+// (DiscretizedTrajectory::GetProjection / EvaluateTime) and two 3-state LQR controllers give delta_rate and jerk
+// (LateralControl cc:57-72, LongitudinalControl cc:74-81) from gains of the iterative DARE solver math::SolveLQRProblem
+// (algorithm/math/linear_quadratic_regulator.cc:30-78), re-solved every step for the lateral model (it depends on the
+// speed); VehicleDynamic cc:83-135 advances the vehicle one RK4 step.  The state is kept whenever the clock passes a knot
+// of the followed trajectory.  Products accumulate k = 0, 1, 2 like Eigen's coefficient-based product of small dynamic
+// matrices; the DARE loop's stopping test is the reference's (fabs of the max coefficient of P_next - P against the
+// tolerance).  The longitudinal gains do not depend on the state and are solved once.
+//
+// tracker_drive is a template on
+//   Follow   the followed trajectory of one lane:  int K;  void xy(int i, double& x, double& y);  FollowPt pt(int i);
+//            double time(int i);  int locate(double time) -- the first knot whose time is not below `time` (K - 1 at or
+//            beyond the last, 0 before the first): QueryLowerBoundTimePoint, discretized_trajectory.cpp:130-141
+//   Sink     void keep(int i, const double* x6, const double* u2, double time): knot i = x y theta v a delta was recorded at
+//            clock `time` under the controls u2 = jerk, delta_rate, which knot i - 1 carries
+// Both are inlined: the arithmetic below is the same sequence of IEEE operations whatever they are (-ffp-contract=off).
+#pragma once
+#include "dev_model.hpp"
+
+namespace cilqr {
+namespace tracker_core {
+
+struct M3 {
+  double m[9];
+};
+CILQR_DEV void mul33(const M3& a, const M3& b, M3& r) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      double s = a.m[i * 3 + 0] * b.m[0 * 3 + j];
+      s += a.m[i * 3 + 1] * b.m[1 * 3 + j];
+      s += a.m[i * 3 + 2] * b.m[2 * 3 + j];
+      r.m[i * 3 + j] = s;
+    }
+}
+CILQR_DEV void row33(const double* v, const M3& m, double* out) {   // (1x3) (3x3)
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    double s = v[0] * m.m[0 * 3 + j];
+    s += v[1] * m.m[1 * 3 + j];
+    s += v[2] * m.m[2 * 3 + j];
+    out[j] = s;
+  }
+}
+
+// math::SolveLQRProblem, linear_quadratic_regulator.cc:30-78, with B 3x1, R 1x1, M = 0 -> K (1x3)
+CILQR_DEV void solve_lqr(const M3& A, const double* B, const M3& Q, double R, double tolerance, int max_iter, double* K) {
+  M3 AT;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) AT.m[i * 3 + j] = A.m[j * 3 + i];
+  M3 P = Q;
+  int num_iteration = 0;
+  double diff = DBL_MAX;
+#pragma unroll 1
+  while (num_iteration++ < max_iter && diff > tolerance) {
+    M3 ATP, ATPA;
+    mul33(AT, P, ATP);
+    mul33(ATP, A, ATPA);
+    double ATPB[3], BTP[3], BTPA[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      double s = ATP.m[i * 3 + 0] * B[0];
+      s += ATP.m[i * 3 + 1] * B[1];
+      s += ATP.m[i * 3 + 2] * B[2];
+      ATPB[i] = s + 0.0;
+    }
+    row33(B, P, BTP);
+    double BTPB = BTP[0] * B[0];
+    BTPB += BTP[1] * B[1];
+    BTPB += BTP[2] * B[2];
+    const double inv = 1.0 / (R + BTPB);
+    row33(BTP, A, BTPA);
+    double maxc = -DBL_MAX;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const double left = ATPB[i] * inv;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const double pn = (ATPA.m[i * 3 + j] - left * (BTPA[j] + 0.0)) + Q.m[i * 3 + j];
+        maxc = fmax(maxc, pn - P.m[i * 3 + j]);
+        ATP.m[i * 3 + j] = pn;   // ATP is dead: reuse it for P_next
+      }
+    }
+    diff = fabs(maxc);
+    P = ATP;
+  }
+  double BTP[3], BTPA[3];
+  row33(B, P, BTP);
+  double BTPB = BTP[0] * B[0];
+  BTPB += BTP[1] * B[1];
+  BTPB += BTP[2] * B[2];
+  const double inv = 1.0 / (R + BTPB);
+  row33(BTP, A, BTPA);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) K[j] = inv * (BTPA[j] + 0.0);
+}
+
+CILQR_DEV double slerp(double a0, double t0, double a1, double t1, double t) {   // math_utils.h:208-225
+  if (fabs(t1 - t0) <= kMathEps) return normalize_angle(a0);
+  const double a0_n = normalize_angle(a0), a1_n = normalize_angle(a1);
+  double d = a1_n - a0_n;
+  if (d > kPi) d = d - 2 * kPi;
+  else if (d < -kPi) d = d + 2 * kPi;
+  const double r = (t - t0) / (t1 - t0);
+  return normalize_angle(a0_n + d * r);
+}
+
+struct FollowPt {
+  double s, x, y, theta, v;
+};
+
+// The simulation from the state x6 = x y theta v a delta (updated in place) at the clock of F's first knot, until
+// `n_record` knots (knot 0, the start, included; 1 <= n_record <= F.K) are recorded, the clock has passed the last knot's
+// time or `max_steps` steps are done.  Returns the number of knots recorded: n_record, or fewer -- the reference's "tacker
+// failed" (cc:205-208).
+template <class Follow, class Sink>
+CILQR_DEV int tracker_drive(const Follow& F, const Params& p, const TrackerParams& tp, double* x6, int n_record, int max_steps,
+                            Sink& sink) {
+  const int K = F.K;
+  // InitMatrix tracker.cc:137-167
+  M3 latA, latQ, lonA, lonQ;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) latA.m[e] = latQ.m[e] = lonA.m[e] = lonQ.m[e] = 0.0;
+  latA.m[0] = 1.0; latA.m[4] = 1.0; latA.m[8] = 1.0;
+  const double latB[3] = {0.0, 0.0, 1.0 * tp.dt};
+  latQ.m[0] = tp.weight_l; latQ.m[4] = tp.weight_theta; latQ.m[8] = tp.weight_delta;
+  lonA.m[0] = 1.0; lonA.m[4] = 1.0; lonA.m[8] = 1.0;
+  lonA.m[1] = tp.dt;
+  lonA.m[5] = -tp.dt;
+  const double lonB[3] = {0.0, 0.0, 1.0 * tp.dt};
+  lonQ.m[0] = tp.weight_s; lonQ.m[4] = tp.weight_v; lonQ.m[8] = tp.weight_a;
+  double Klon[3];
+  solve_lqr(lonA, lonB, lonQ, tp.weight_j, tp.tolerance, tp.max_num_iteration, Klon);   // constant over the simulation
+
+  double cx = x6[0], cy = x6[1], cth = x6[2], cv = x6[3], ca = x6[4], cdl = x6[5];
+  const double start_time = F.time(0), end_time = F.time(K - 1);
+  double ctime = start_time;
+  int i = 1, steps = 0;
+  double next_time = F.time(1);   // of knot i (K >= 2)
+#pragma unroll 1
+  for (double t = start_time; t < end_time + kMathEps && i < n_record && steps < max_steps; t += tp.sim_dt, ++steps) {
+    // ---- CalcaulateInitState cc:19-55 ----
+    double sn, cs;
+    lean_sincos(cth, &sn, &cs);
+    const double pvx = cx + cs * cv * tp.preview_time;
+    const double pvy = cy + sn * cv * tp.preview_time;
+    // GetProjection discretized_trajectory.cpp:165-197: nearest knot (first minimum), then the point at station
+    // s_start + (v0 . v1) / |v1| between its two neighbours
+    int idx = 0;
+    {
+      double nearest = DBL_MAX;
+#pragma unroll 4
+      for (int k = 0; k < K; ++k) {
+        double fx, fy;
+        F.xy(k, fx, fy);
+        const double dx = fx - pvx, dy = fy - pvy;
+        const double d = dx * dx + dy * dy;
+        if (d < nearest) {
+          nearest = d;
+          idx = k;
+        }
+      }
+    }
+    FollowPt proj = F.pt(idx);
+    {
+      const int i0 = max(0, idx - 1), i1 = min(K - 1, idx + 1);
+      if (i0 < i1) {
+        const FollowPt p0 = F.pt(i0), p1 = F.pt(i1);
+        const double v0x = pvx - p0.x, v0y = pvy - p0.y;
+        const double v1x = p1.x - p0.x, v1y = p1.y - p0.y;
+        const double v1_norm = sqrt(v1x * v1x + v1y * v1y);
+        const double dot = v0x * v1x + v0y * v1y;
+        const double st = p0.s + dot / v1_norm;
+        if (fabs(p1.s - p0.s) < kMathEps) {   // LinearInterpolateTrajectory cpp:66-89
+          proj = p0;
+        } else {
+          const double w = (st - p0.s) / (p1.s - p0.s);
+          proj.s = st;
+          proj.x = (1 - w) * p0.x + w * p1.x;
+          proj.y = (1 - w) * p0.y + w * p1.y;
+          proj.theta = slerp(p0.theta, p0.s, p1.theta, p1.s, st);
+          proj.v = (1 - w) * p0.v + w * p1.v;
+        }
+      }
+    }
+    double psn, pcs;
+    lean_sincos(proj.theta, &psn, &pcs);
+    const double ddx = cx - proj.x, ddy = cy - proj.y;
+    const double lat0 = psn * ddx - pcs * ddy;
+    const double lat1 = normalize_angle(proj.theta - cth);
+    const double lat2 = cdl;
+    // EvaluateTime(cur.time) cpp:130-141: first knot whose time is not below, interpolated from its predecessor
+    double match_s, match_v;
+    {
+      const double time = ctime + 0.0;
+      int it = F.locate(time);
+      if (it == 0) it = 1;
+      const FollowPt p0 = F.pt(it - 1), p1 = F.pt(it);
+      const double t0 = F.time(it - 1), t1 = F.time(it);
+      if (fabs(t1 - t0) < kMathEps) {
+        match_s = p0.s;
+        match_v = p0.v;
+      } else {
+        const double w = (time - t0) / (t1 - t0);
+        match_s = (1 - w) * p0.s + w * p1.s;
+        match_v = (1 - w) * p0.v + w * p1.v;
+      }
+    }
+    const double lon0 = match_s - proj.s, lon1 = match_v - cv, lon2 = ca;
+    // ---- LateralControl cc:57-72 ----
+    const double v_amend = fmax(2.0, cv);
+    latA.m[1] = v_amend * 0.1;
+    latA.m[5] = -v_amend / p.wheel_base * 0.1;
+    double Klat[3];
+    solve_lqr(latA, latB, latQ, tp.weight_delta_rate, tp.tolerance, tp.max_num_iteration, Klat);
+    double delta_rate, jerk;
+    {
+      double a = Klat[0] * lat0;
+      a += Klat[1] * lat1;
+      a += Klat[2] * lat2;
+      delta_rate = -a;
+      double b = Klon[0] * lon0;   // LongitudinalControl cc:74-81
+      b += Klon[1] * lon1;
+      b += Klon[2] * lon2;
+      jerk = -b;
+    }
+    delta_rate = fmax(p.delta_rate_min, fmin(p.delta_rate_max, delta_rate));
+    jerk = fmax(p.jerk_min, fmin(p.jerk_max, jerk));
+    // ---- VehicleDynamic cc:83-135: RK4 of (x, y, theta, v, delta, a) ----
+    {
+      const double h = tp.sim_dt, h2 = h / 2.0;
+      double k1[4], k2[4], k3[4], k4[4];   // x', y', theta', (v' = a; delta' = delta_rate; a' = jerk)
+      auto mode = [&](double th, double v, double dl, double* o) {   // vehicle_mode tracker.h:72-87
+        double sn_, cs_;
+        lean_sincos(th, &sn_, &cs_);
+        o[0] = v * cs_;
+        o[1] = v * sn_;
+        o[2] = CILQR_OVER_L(p, v * lean_tan(dl));
+      };
+      mode(cth, cv, cdl, k1);
+      const double a1 = ca, a2 = ca + jerk * h2, a3 = ca + jerk * h2, a4 = ca + jerk * h;
+      mode(cth + k1[2] * h2, cv + a1 * h2, cdl + delta_rate * h2, k2);
+      mode(cth + k2[2] * h2, cv + a2 * h2, cdl + delta_rate * h2, k3);
+      mode(cth + k3[2] * h, cv + a3 * h, cdl + delta_rate * h, k4);
+      const double nx = cx + (k1[0] + k2[0] * 2.0 + k3[0] * 2.0 + k4[0]) / 6.0 * h;
+      const double ny = cy + (k1[1] + k2[1] * 2.0 + k3[1] * 2.0 + k4[1]) / 6.0 * h;
+      const double nth = normalize_angle(cth + (k1[2] + k2[2] * 2.0 + k3[2] * 2.0 + k4[2]) / 6.0 * h);
+      const double nv = fmax(0.0, cv + (a1 + a2 * 2.0 + a3 * 2.0 + a4) / 6.0 * h);
+      const double ndl = normalize_angle(fmin(p.delta_max, fmax(p.delta_min, cdl + (delta_rate + delta_rate * 2.0 + delta_rate * 2.0 + delta_rate) / 6.0 * h)));
+      const double na = fmin(p.max_acc, fmax(p.min_acc, ca + (jerk + jerk * 2.0 + jerk * 2.0 + jerk) / 6.0 * h));
+      cx = nx; cy = ny; cth = nth; cv = nv; cdl = ndl; ca = na;
+    }
+    ctime = t;
+    if (ctime > next_time - kMathEps) {   // cc:199-202 (i < K holds: i < n_record <= K)
+      const double u[2] = {jerk, delta_rate};   // what trajectory.back() carries when the next knot is pushed
+      const double x[6] = {cx, cy, cth, cv, ca, cdl};
+      sink.keep(i, x, u, ctime);
+      ++i;
+      if (i < K) next_time = F.time(i);
+    }
+  }
+  x6[0] = cx; x6[1] = cy; x6[2] = cth; x6[3] = cv; x6[4] = ca; x6[5] = cdl;
+  return i;
+}
+
+}  // namespace tracker_core
+}  // namespace cilqr

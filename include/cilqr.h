@@ -301,7 +301,8 @@ typedef struct cilqr_tracker_config {
 /* Limits of one tracker launch (every problem runs n_steps * dt / sumulation_dt simulation steps, each with a DARE loop of up
  * to max_num_iteration rounds; the reference's defaults are 150 iterations and 10 steps per knot). */
 #define CILQR_TRACKER_MAX_ITERATIONS 1000  /* largest max_num_iteration */
-#define CILQR_TRACKER_MAX_SIM_STEPS 32768  /* largest n_steps * dt / sumulation_dt (n_steps, dt of cilqr_create) */
+#define CILQR_TRACKER_MAX_SIM_STEPS 32768  /* largest n_steps * dt / sumulation_dt (n_steps, dt of cilqr_create); also the
+                                              most simulation rounds of one "track" call below, whatever its time column */
 void cilqr_default_tracker_config(cilqr_tracker_config* cfg);
 /* CILQR_ERR_NULL: null handle.  CILQR_ERR_ARG, the handle keeping the configuration it had: a null config; a field that is
  * not finite; sumulation_dt <= 0, dt <= 0, tolerance < 0; max_num_iteration outside 1 ... CILQR_TRACKER_MAX_ITERATIONS; more
@@ -847,6 +848,76 @@ int cilqr_constraint_margins_batch(cilqr_handle h, const cilqr_problem_batch* in
                                    double* min_margin /* [B][8] */, int32_t* min_knot /* [B][8] */,
                                    const double* tol /* HOST [8], optional */, uint32_t* violated /* [B] */,
                                    int32_t* n_violating /* HOST, optional */);
+
+/* ---- track: drive a vehicle along trajectory rows with the closed-loop Tracker (Tracker::Plan, algorithm/ilqr/tracker.cc:
+ * 12-215); one trajectory on the host, no handle ----
+ * The vehicle is simulated at sumulation_dt with RK4 under a lateral and a longitudinal LQR controller; it follows `rows`
+ * from `start6`, which need not lie on them.  What CILQR_INIT_TRACKER runs inside a solve (kernels_tracker.hip), as a call of
+ * its own: any time column, a full six-state start, any number of knots.
+ *   followed   K = n_knots >= 2 rows in CILQR_ROWS_TRAJ / _PLAN / _COARSE; read: time, x, y, theta, v (and a, delta of row 0
+ *              when start6 is NULL).  time is taken as non-decreasing; start_time = time[0], end_time = time[K-1].  station =
+ *              the layout's station column (_PLAN, _COARSE); for _TRAJ the accumulated chord length s[0] = 0, s[k] = s[k-1] +
+ *              hypot(x[k] - x[k-1], y[k] - y[k-1]), hypot as glibc 2.35 evaluates it without fused multiply-add.
+ *   start      start6 = x y theta v a delta; NULL: x, y, theta, v, a, delta of row 0.
+ *   gains      K = (R + B'PB)^-1 B'PA, P from P <- A'PA - A'PB (R + B'PB)^-1 B'PA + Q started at Q, while fewer than
+ *              max_num_iteration rounds are done and |max coefficient of (P_next - P)| > tolerance; products accumulate in
+ *              index order.  Longitudinal (once): A = I + [[0, dt, 0], [0, 0, -dt], 0], B = (0, 0, dt), Q = diag(weight_s,
+ *              weight_v, weight_a), R = weight_j.  Lateral (every step): A = I + [[0, vm 0.1, 0], [0, 0, -vm / wheel_base 0.1],
+ *              0] with vm = max(2, v) and 0.1 a literal, B = (0, 0, dt), Q = diag(weight_l, weight_theta, weight_delta), R =
+ *              weight_delta_rate.
+ *   clock      cur_time = start_time, i = 1; for (t = start_time; t < end_time + 1e-10; t += sumulation_dt), at most
+ *              CILQR_TRACKER_MAX_SIM_STEPS rounds whatever the time column holds, and no further round once n_drive knots are
+ *              recorded.  One round:
+ *     preview     (x + cos(theta) v preview_time, y + sin(theta) v preview_time)
+ *     projection  nearest followed point (first minimum of the squared distance over all K), its neighbours i0 = max(0, at -
+ *                 1), i1 = min(K - 1, at + 1): st = s[i0] + (w . d) / |d| with d = p[i1] - p[i0], w = preview - p[i0]; if
+ *                 |s[i1] - s[i0]| < 1e-10 the point is row i0, else x, y, v linear in station at st and theta by slerp
+ *                 ("resample" above).
+ *     lateral     (sin(pth) (x - px) - cos(pth) (y - py), NormalizeAngle(pth - theta), delta)
+ *     match       the bracket of "resample" on the time column at cur_time: rows it - 1, it; if |t1 - t0| < 1e-10 station and
+ *                 v of row it - 1, else linear in time
+ *     longitud.   (match.s - st, match.v - v, a)
+ *     controls    delta_rate = -K_lat . lateral, jerk = -K_lon . longitudinal, clamped to the vehicle's bounds
+ *     RK4         one step of (x, y, theta, v, delta, a)' = (v cos theta, v sin theta, v tan(delta) / wheel_base, a,
+ *                 delta_rate, jerk); then theta wrapped, v = max(0, v), delta clamped then wrapped, a clamped
+ *     keep        cur_time = t (the clock BEFORE the step, as the reference has it); if i < K and cur_time > time[i] - 1e-10:
+ *                 row i - 1 receives (jerk, delta_rate), the state is recorded as row i, i += 1
+ *   n_drive    1 ... n_knots rows are recorded (row 0 is the start).  The projection still scans all n_knots and end_time is
+ *              the last row's: rows 0 ... n_drive - 1 of a run with a larger n_drive are these rows bit for bit -- except the
+ *              two control columns of row n_drive - 1, which belong to a step this run does not take and are 0.
+ *   driven     [n_drive][CILQR_TRAJ_FIELDS]: time = cur_time when the row was recorded (row 0: start_time), x y theta v a
+ *              delta, kappa = tan(delta) / wheel_base, jerk and delta_rate = the controls in force when the NEXT row was
+ *              recorded; the last row's are 0, as the solver's export has them at its last knot.
+ *   failure    fewer than n_drive rows recorded when the clock ends or the round limit is reached -- the reference's "tacker
+ *              failed" (cc:205-208): CILQR_ERR_STATE, every row of `driven` zero.
+ * Non-finite rows are no error: the arithmetic decides.  Every operation is rounded once; sin / cos (one sincos call where
+ * the C library has it) and tan are the C library's.  CILQR_ERR_NULL; CILQR_ERR_ARG for an unknown layout (CILQR_ROWS_POINTS
+ * included), n_knots < 2, n_drive outside 1 ... n_knots, a tracker configuration cilqr_set_tracker_config would refuse for
+ * its values alone (non-finite, sumulation_dt or dt <= 0, tolerance < 0, max_num_iteration outside 1 ...
+ * CILQR_TRACKER_MAX_ITERATIONS).  Of cfg only wheel_base and the five pairs of bounds are read.  C++ callers with the
+ * reference's types use include/cilqr/tracker.hpp. */
+int cilqr_track_rows(const cilqr_config* cfg, const cilqr_tracker_config* tcfg, int32_t layout, const double* rows,
+                     int32_t n_knots, const double* start6 /* [6], optional */, int32_t n_drive,
+                     double* driven /* [n_drive][CILQR_TRAJ_FIELDS] */);
+/* ---- the same for B trajectories per call, on the GPU (kernels_track.hip; ABI 7) ----
+ *   rows [B][n_knots][fields], start6 [B][6] (optional), driven [B][n_drive][CILQR_TRAJ_FIELDS], ok [B]: in `memory`;
+ *   n_failed: HOST, optional.
+ * The tracker configuration is the handle's (cilqr_set_tracker_config), wheel base and bounds those of cilqr_create; batch
+ * and n_knots are not tied to the handle's, and no problem needs to be loaded.  ok[b] = 1: n_drive rows were recorded; 0:
+ * the failure above, that problem's rows are all zero, the others are unaffected; *n_failed counts them.  A problem's rows do
+ * not depend on the batch around it.  One lane per problem; sin, cos and tan are the device's (cilqr_device_math), so the
+ * rows follow the host call closely but not bit for bit.  A pre-pass gathers the columns the rule reads into a
+ * batch-fastest table in work space that belongs to the handle and grows to the largest call (48 bytes per followed row);
+ * HOST arrays are staged in blocks of the handle likewise.  Driven rows in this layout feed cilqr_check_collisions_batch,
+ * cilqr_clearance_rows_batch, cilqr_constraint_margins_batch, cilqr_resample_rows_batch and cilqr_solve_batch_warm where they
+ * lie.  Runs on the handle's stream and waits for that stream only.  Checked before anything is launched, the handle staying
+ * usable: CILQR_ERR_NULL (handle, rows, driven, ok); CILQR_ERR_ARG for batch < 1, an unknown layout, CILQR_ROWS_POINTS,
+ * n_knots < 2, n_drive outside 1 ... n_knots, an unknown memory flag; CILQR_ERR_STATE while solves are submitted on the
+ * handle. */
+int cilqr_track_rows_batch(cilqr_handle h, int32_t batch, int32_t layout, const double* rows, int32_t n_knots,
+                           const double* start6 /* [B][6], optional */, int32_t n_drive,
+                           double* driven /* [B][n_drive][CILQR_TRAJ_FIELDS] */, int32_t* ok /* [B] */,
+                           int32_t* n_failed /* HOST, optional */, int32_t memory);
 
 /* ---- TrajectoryPlanner::Plan for B scenes per call (trajectory_planner.cpp:28-162) ----
  * scene batch -> cilqr_dp_plan_batch -> cilqr_scene_points_batch (at the time column the planner produced, with
