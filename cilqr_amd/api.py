@@ -28,6 +28,8 @@ OPT_ROUND_GROUP = 7
 OPT_FINISH_THRESHOLD = 8
 OPT_EXACT_LANE_TIES = 9
 OPT_SCENE_CHUNK = 10
+OPT_TAIL_LDS_LIMIT = 11
+OPT_TAIL_PLAN = 12
 ST_RUNNING, ST_CONVERGED_ABS, ST_CONVERGED_REL, ST_GNORM, ST_UNSOLVED, ST_MAX_ITER, ST_NO_CORRIDOR = range(7)
 ABI_VERSION = 7
 

@@ -438,20 +438,11 @@ static size_t tail_fixed_lds(const DeviceState& g) {
 // lane tables + the backward pass's operands and per-step rows + the view: within the 64 KiB no attribute has to grant
 bool tail_supported(const DeviceState& g) { return tail_fixed_lds(g) <= 62 * 1024; }
 
-// g.act / g.n_dev: the active list the tail takes over (n_max bounds its length and sizes the grid)
-void launch_tail(const DeviceState& g, void* workspace, int n_max, double* traj, double* iter_trajs,
-                 int max_iter_trajs, int* max_iter_dev, hipStream_t st) {
-  if (n_max <= 0) return;
-  TailArgs a;
-  a.ws = static_cast<char*>(workspace);
-  a.L = tail_layout(g);
-  a.traj = traj;
-  a.iter_trajs = iter_trajs;
-  a.it_cap = max_iter_trajs;
-  a.max_iter = max_iter_dev;
-  const size_t fixed = tail_fixed_lds(g);
+// Dynamic LDS a tail launch on the current device may plan with: what the device grants, capped by `limit` (the handle's
+// CILQR_OPT_TAIL_LDS_LIMIT; 0 = no cap).
+size_t tail_lds_in_force(size_t limit) {
   // Dynamic shared memory beyond the default has to be asked for, once per kernel and device; what the device grants
-  // (160 KiB per workgroup on gfx950, 64 KiB on older CDNA) sizes the budget below.  One-time, guarded: several handles'
+  // (160 KiB per workgroup on gfx950, 64 KiB on older CDNA) sizes the budget of tail_plan.  One-time, guarded: several handles'
   // worker threads come through here.
   struct DeviceLds { std::once_flag once; size_t bytes = 0; };
   static DeviceLds lds_of[64];
@@ -471,8 +462,26 @@ void launch_tail(const DeviceState& g, void* workspace, int n_max, double* traj,
     }
     dl.bytes = (size_t)max_lds;
   });
+  return limit > 0 ? std::min(dl.bytes, limit) : dl.bytes;
+}
+
+// Where a launch puts the problem's working set, and which form of every phase follows from it.  The ONE place that decides
+// either: launch_tail launches from it, CILQR_OPT_TAIL_PLAN reports it (tail_plan_report).
+struct TailPlan {
+  TailLayout S;      // byte offsets of the tensors in the block's LDS (kNotInLds: in the private arena), stride unused
+  int bwd_in_lds, fwd_in_lds, fwd_src_in_lds, quad_in_lds, quad_scr, cost_in_lds;   // as in TailArgs
+  size_t fixed;      // the fixed block in front (TailArgs::lds_base)
+  size_t lds;        // dynamic LDS bytes of the launch: fixed block + the tensors placed
+  bool supported;    // tail_supported
+};
+// lds_bytes: dynamic LDS the launch may plan with (tail_lds_in_force)
+static TailPlan tail_plan(const DeviceState& g, size_t lds_bytes) {
+  TailPlan a;
+  const size_t fixed = tail_fixed_lds(g);
+  a.fixed = fixed;
+  a.supported = tail_supported(g);
   // tensors into LDS by priority until the workgroup's share (one workgroup per CU: all of its LDS less a margin) is used up
-  const size_t budget = dl.bytes > fixed + 2048 ? dl.bytes - 2048 - fixed : 0;
+  const size_t budget = lds_bytes > fixed + 2048 ? lds_bytes - 2048 - fixed : 0;
   const size_t K = g.p.K, N = g.p.N;
   struct Item { size_t TailLayout::*field; size_t bytes; };
   const Item items[] = {
@@ -483,13 +492,12 @@ void launch_tail(const DeviceState& g, void* workspace, int n_max, double* traj,
       {&TailLayout::Xs, (size_t)kNumAlpha * K * 3 * sizeof(double2)}, {&TailLayout::Us, (size_t)kNumAlpha * N * sizeof(double2)},
       {&TailLayout::goals, K * 3 * sizeof(double2)}, {&TailLayout::ccnt, K * sizeof(int)}, {&TailLayout::cor, K * tail_cmax(g.cmax) * 3 * sizeof(double)}};
   size_t used = 0;
-  a.S = a.L;
+  a.S = tail_layout(g);
   for (const Item& it : items) {
     const size_t b = (it.bytes + 15) / 16 * 16;
     if (used + b <= budget) { a.S.*(it.field) = used; used += b; }
     else a.S.*(it.field) = kNotInLds;
   }
-  a.lds_base = (int)fixed;
   auto in_lds = [&](size_t TailLayout::*f) { return a.S.*f != kNotInLds; };
   a.bwd_in_lds = in_lds(&TailLayout::lin) && in_lds(&TailLayout::term) && in_lds(&TailLayout::gains) && in_lds(&TailLayout::U) &&
                  in_lds(&TailLayout::dbl);
@@ -511,7 +519,50 @@ void launch_tail(const DeviceState& g, void* workspace, int n_max, double* traj,
     a.quad_scr = (!off && g.p.num_of_disc == 5 && a.quad_in_lds && one_piece && need <= b_parts + b_xs + b_us && kTailThreads == 256)
                      ? (int)a.S.parts : -1;
   }
-  const size_t lds = fixed + used;
+  a.lds = fixed + used;
+  return a;
+}
+
+// CILQR_OPT_TAIL_PLAN (include/cilqr.h): bits 0..13 = the tensor is in LDS, in TailLayout's order; 16..20 = bwd_in_lds,
+// fwd_src_in_lds, fwd_in_lds, quad_in_lds, cost_in_lds; 21 = split quadratisation; 24 = tail_supported
+void tail_plan_report(const DeviceState& g, size_t lds_limit, long long* bits, long long* lds_bytes) {
+  const TailPlan pl = tail_plan(g, tail_lds_in_force(lds_limit));
+  size_t TailLayout::*const order[14] = {&TailLayout::X, &TailLayout::U, &TailLayout::goals, &TailLayout::cor, &TailLayout::ccnt,
+                                         &TailLayout::lin, &TailLayout::term, &TailLayout::gains, &TailLayout::Xs, &TailLayout::Us,
+                                         &TailLayout::parts, &TailLayout::spec_tot, &TailLayout::dbl, &TailLayout::ints};
+  long long v = 0;
+  for (int k = 0; k < 14; ++k)
+    if (pl.S.*order[k] != kNotInLds) v |= 1ll << k;
+  const int flags[6] = {pl.bwd_in_lds, pl.fwd_src_in_lds, pl.fwd_in_lds, pl.quad_in_lds, pl.cost_in_lds, pl.quad_scr >= 0};
+  for (int k = 0; k < 6; ++k)
+    if (flags[k]) v |= 1ll << (16 + k);
+  if (pl.supported) v |= 1ll << 24;
+  *bits = v;
+  *lds_bytes = (long long)pl.lds;
+}
+
+// g.act / g.n_dev: the active list the tail takes over (n_max bounds its length and sizes the grid); lds_limit: the handle's
+// CILQR_OPT_TAIL_LDS_LIMIT
+void launch_tail(const DeviceState& g, void* workspace, int n_max, double* traj, double* iter_trajs,
+                 int max_iter_trajs, int* max_iter_dev, size_t lds_limit, hipStream_t st) {
+  if (n_max <= 0) return;
+  const TailPlan pl = tail_plan(g, tail_lds_in_force(lds_limit));
+  TailArgs a;
+  a.ws = static_cast<char*>(workspace);
+  a.L = tail_layout(g);
+  a.S = pl.S;
+  a.lds_base = (int)pl.fixed;
+  a.traj = traj;
+  a.iter_trajs = iter_trajs;
+  a.it_cap = max_iter_trajs;
+  a.max_iter = max_iter_dev;
+  a.bwd_in_lds = pl.bwd_in_lds;
+  a.fwd_in_lds = pl.fwd_in_lds;
+  a.fwd_src_in_lds = pl.fwd_src_in_lds;
+  a.quad_in_lds = pl.quad_in_lds;
+  a.quad_scr = pl.quad_scr;
+  a.cost_in_lds = pl.cost_in_lds;
+  const size_t lds = pl.lds;
   if (g.p.num_of_disc == 5) {
     if (g.exact_ties) hipLaunchKernelGGL((k_tail<5, true>), dim3(n_max >= 64 ? (n_max + 63) / 64 * 64 : n_max), dim3(kTailThreads), lds, st, g, a, n_max);
     else hipLaunchKernelGGL((k_tail<5, false>), dim3(n_max >= 64 ? (n_max + 63) / 64 * 64 : n_max), dim3(kTailThreads), lds, st, g, a, n_max);

@@ -813,6 +813,12 @@ int cilqr_set_option(cilqr_handle h, int32_t option, int64_t value) {
       if (value < 0) return CILQR_ERR_ARG;
       h->scene_chunk = (int)(value > 0x7fffffff ? 0x7fffffff : value);
       return CILQR_OK;
+    case CILQR_OPT_TAIL_LDS_LIMIT:
+      if (value < 0) return CILQR_ERR_ARG;
+      h->tail_lds_limit = (size_t)value;
+      return CILQR_OK;
+    case CILQR_OPT_TAIL_PLAN:   // read-only
+      return CILQR_ERR_ARG;
     default:
       return CILQR_ERR_ARG;
   }
@@ -832,6 +838,16 @@ int cilqr_get_option(cilqr_handle h, int32_t option, int64_t* value, int64_t* va
     case CILQR_OPT_EXACT_LANE_TIES: v = vs = h->ds.exact_ties; break;
     case CILQR_OPT_FINISH_THRESHOLD: v = vs = h->fin_threshold; break;
     case CILQR_OPT_SCENE_CHUNK: v = vs = h->scene_chunk; break;
+    case CILQR_OPT_TAIL_LDS_LIMIT: v = vs = (int64_t)h->tail_lds_limit; break;
+    case CILQR_OPT_TAIL_PLAN: {   // of the problem cilqr_stage_load left in the main arena: its horizon, plane capacity and lane tables
+      if (!(h->stage & 1)) return CILQR_ERR_STATE;
+      HIP_TRY(hipSetDevice(h->device));
+      long long bits = 0, lds = 0;
+      tail_plan_report(h->ds, h->tail_lds_limit, &bits, &lds);
+      v = bits;
+      vs = lds;
+      break;
+    }
     default: return CILQR_ERR_ARG;
   }
   *value = v;
@@ -933,6 +949,7 @@ static int solve_sync(cilqr_solver* h, const cilqr_problem_batch* in, const cilq
   j.set = 0;
   j.spec_threshold = h->spec_threshold;
   j.tail_threshold = h->tail_threshold;
+  j.tail_lds_limit = h->tail_lds_limit;
   j.st1 = h->stream;
   j.st2 = h->stream;
   j.relaxed_wait = false;    // the caller's own thread waits, and the call's latency is what it is measured by (wait_event)
@@ -1272,7 +1289,7 @@ int job_iterate(cilqr_solver* h, cilqr_job& j, int stage) {
       void* ws = (stage == 1 && !j.handed) ? h->tail_ws1.get() : h->tail_ws.get();
       if (j.tm.begin(4)) return CILQR_ERR_DEVICE;
       HIP_TRY(hipMemsetAsync(js.tail_iter_dev, 0, sizeof(int), st));
-      launch_tail(d, ws, n_hint, j.o_traj, j.o_it, j.out.max_iter_trajs, js.tail_iter_dev, st);
+      launch_tail(d, ws, n_hint, j.o_traj, j.o_it, j.out.max_iter_trajs, js.tail_iter_dev, j.tail_lds_limit, st);
       HIP_TRY(hipMemcpyAsync(h_count + M + 32, js.tail_iter_dev, sizeof(int), hipMemcpyDeviceToHost, st));
       if (j.tm.end()) return CILQR_ERR_DEVICE;
       j.tail_used = true;
@@ -1666,6 +1683,7 @@ int cilqr_submit_warm(cilqr_handle h, const cilqr_problem_batch* in, const cilqr
   j.past_load = false;
   j.spec_threshold = h->alone_on_device ? h->spec_threshold : h->spec_threshold_submit;
   j.tail_threshold = h->alone_on_device ? h->tail_threshold : h->tail_threshold_submit;
+  j.tail_lds_limit = h->tail_lds_limit;
   j.st1 = h->stream;
   j.st2 = h->stream2.get();
   j.relaxed_wait = true;     // a worker thread waits for this solve, and other solves want the cores (wait_event)

@@ -115,6 +115,7 @@ struct cilqr_job {
   int set = 0;              // the cilqr_job_set it runs on: taken when its first stage starts, given back when it is done
   int spec_threshold = 0;   // the threshold of this solve (cilqr_solver::spec_threshold or spec_threshold_submit)
   int tail_threshold = 0;   // likewise (cilqr_solver::tail_threshold or tail_threshold_submit)
+  size_t tail_lds_limit = 0;   // cilqr_solver::tail_lds_limit when the solve was handed in
   int phase = 0;            // 0 free, 1 queued, 2 first stage, 3 waiting for the finishing stage, 4 finishing, 5 done
   int rc = CILQR_OK;
   char err_text[256] = "";  // what the worker thread's g_last_hip_error held when rc was set (that variable is thread-local)
@@ -217,6 +218,7 @@ struct cilqr_solver {
   // fewer: 256 until round 5, 128 since (profiles/r05_cost_kernel_experiments.txt 6)
   int tail_threshold = 1024;
   int tail_threshold_submit = 128;
+  size_t tail_lds_limit = 0;  // CILQR_OPT_TAIL_LDS_LIMIT: dynamic LDS a tail launch may plan with (0 = what the device grants; a test hook)
   cilqr::dev_mem tail_ws;     // private arenas of the tail's problems (lazily grown)
   cilqr::dev_mem tail_ws1;    // the same for a solve that reaches the tail without having been handed over (first stage)
   // asynchronous submit / wait: two jobs in flight, one worker thread per stage

@@ -246,8 +246,12 @@ void launch_init_counters(const DeviceState& s, int first_n, hipStream_t st);
 // kernels_tail.hip: one workgroup per problem finishes every problem of the active list (all remaining iterations)
 size_t tail_workspace_bytes(const DeviceState& s);   // private arena of one problem
 bool tail_supported(const DeviceState& s);           // the kernel's fixed LDS block fits what every device grants
+// lds_limit: CILQR_OPT_TAIL_LDS_LIMIT of the handle (0 = what the device grants)
 void launch_tail(const DeviceState& s, void* workspace, int n_max, double* traj, double* iter_trajs,
-                 int max_iter_trajs, int* max_iter_dev, hipStream_t st);
+                 int max_iter_trajs, int* max_iter_dev, size_t lds_limit, hipStream_t st);
+// CILQR_OPT_TAIL_PLAN: the placement launch_tail takes for this state under that limit on the current device (the bits of
+// include/cilqr.h) and the launch's dynamic LDS bytes
+void tail_plan_report(const DeviceState& s, size_t lds_limit, long long* bits, long long* lds_bytes);
 void launch_update(const DeviceState& s, int n_act, hipStream_t st);
 // trajectories of the slots that finished in the last update -> traj[pid]
 void launch_export_done(const DeviceState& s, int n_act, double* traj, hipStream_t st);

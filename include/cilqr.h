@@ -240,6 +240,26 @@ int cilqr_set_stream(cilqr_handle h, void* hip_stream);
  * as fit into 1 GiB of points; a positive value = that many (a test hook: a scene's result does not depend on the chunk
  * it falls into).  Bit-identical results. */
 #define CILQR_OPT_SCENE_CHUNK 10
+/* CILQR_OPT_TAIL_LDS_LIMIT (default 0): dynamic LDS, in bytes, that a tail launch of this handle may plan with.  The tail
+ * kernel keeps as many of a problem's 14 tensors in LDS as fit beside its fixed block (lane tables, the backward pass's
+ * operands) and leaves the rest in a private arena in global memory; which ones fit depends on the horizon, the plane
+ * capacity, the lane tables and on what the device grants a workgroup.  0 = what the device grants; a positive value =
+ * min(grant, value) in its place (it never raises anything above the grant, and it does not touch the fixed block: a limit
+ * too small for that block and its margin leaves every tensor in the arena).  65536 gives the placement of a device that
+ * grants no more than the default 64 KiB.  A test hook, like CILQR_OPT_SCENE_CHUNK: every placement computes the same
+ * numbers.  Bit-identical results. */
+#define CILQR_OPT_TAIL_LDS_LIMIT 11
+/* CILQR_OPT_TAIL_PLAN (read-only: cilqr_set_option returns CILQR_ERR_ARG; cilqr_get_option returns CILQR_ERR_STATE unless
+ * cilqr_stage_load has loaded a problem batch): the placement a tail launch takes for the loaded problem under the limit in
+ * force, from the function the launch itself calls.  *value:
+ *   bits 0..13   the tensor is in LDS: X, U, goals, corridor planes, plane counts, lin, term, gains, Xs, Us, parts,
+ *                candidate totals, the scalars, the integers (bit 0 = X ... bit 13 = the integers)
+ *   bits 16..20  the phases that address their tensors as LDS: backward pass, the rollouts' loads, the rollouts' stores,
+ *                quadratisation, knot costs
+ *   bit 21       the quadratisation runs in its split form
+ *   bit 24       the tail kernel is available for this problem (its fixed block fits); otherwise solves stay in lockstep
+ * *value_submitted: dynamic LDS bytes of the launch. */
+#define CILQR_OPT_TAIL_PLAN 12
 int cilqr_set_option(cilqr_handle h, int32_t option, int64_t value);
 /* the value in force (for the options with two defaults -- CILQR_OPT_SPEC_THRESHOLD, CILQR_OPT_TAIL_THRESHOLD -- the one of
  * cilqr_solve_batch in *value and, if value_submitted is not NULL, the one of submitted solves there) */
