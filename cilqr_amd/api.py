@@ -190,6 +190,7 @@ EXPORTS = [
     "cilqr_pool_create", "cilqr_pool_destroy", "cilqr_pool_submit", "cilqr_pool_wait", "cilqr_pool_depth", "cilqr_pool_handle_at",
     "cilqr_pool_set_option", "cilqr_pool_get_profile", "cilqr_pool_device_bytes",
     "cilqr_comm_unique_id", "cilqr_comm_create", "cilqr_comm_destroy", "cilqr_comm_info", "cilqr_gather_results",
+    "cilqr_comm_create_loopback",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -316,6 +317,7 @@ def lib():
         L.cilqr_pool_device_bytes.restype = C.c_int64
         L.cilqr_comm_unique_id.argtypes = [C.c_void_p]
         L.cilqr_comm_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+        L.cilqr_comm_create_loopback.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32]
         L.cilqr_comm_destroy.argtypes = [C.c_void_p]
         L.cilqr_comm_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.cilqr_gather_results.argtypes = [C.c_void_p, C.c_int32, C.POINTER(SolutionBatch), C.c_int32,
@@ -498,6 +500,10 @@ class BatchIlqrOptimizer:
     def comm_create(self, unique_id: bytes, rank: int, world: int):
         buf = (C.c_uint8 * UNIQUE_ID_BYTES).from_buffer_copy(unique_id)
         self._chk(self.L.cilqr_comm_create(self.h, buf, rank, world), "comm_create")
+
+    def comm_create_loopback(self, group: int, rank: int, world: int, timeout_ms: int = 20000):
+        """Test hook: a communicator of `world` handles of this process on one device (include/cilqr.h, test hooks)."""
+        self._chk(self.L.cilqr_comm_create_loopback(self.h, group, rank, world, timeout_ms), "comm_create_loopback")
 
     def comm_destroy(self):
         self._chk(self.L.cilqr_comm_destroy(self.h), "comm_destroy")

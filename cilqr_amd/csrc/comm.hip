@@ -13,10 +13,18 @@
 //   exchange and one host synchronisation per gather.  (More than 32 live rows per problem on average: the rest
 //   follows in a second exchange both sides know about from the header.  The first gather of a communicator, and
 //   any gather whose batch differs from the last one's, is preceded by a 16-byte exchange in which the root checks
-//   that every rank holds the same batch: a mismatch is an error on every rank, not a hang.)
+//   that every rank holds the same batch.  A rank takes part in that exchange when ITS batch differs from the last one
+//   it agreed on, so the check is complete exactly when every rank takes part: at a communicator's first gather, and
+//   at any gather for which every rank's batch differs from the batch last agreed on -- a mismatch there is
+//   CILQR_ERR_ARG on every rank, not a hang.  Beyond that, equal batches are a precondition: a rank that alone moves
+//   to another batch posts the 16-byte exchange against its peers' full messages, which is undefined under RCCL.)
 //
-// RCCL is loaded with dlopen on the first cilqr_comm_* call: libcilqr_hip.so has no link-time
-// dependency on it, and a process that already holds an RCCL (PyTorch bundles one) keeps using that one.
+// The exchange goes through a table of the six calls it needs (struct Transport); a communicator keeps the table it was
+// created with.  RCCL is the product transport: loaded with dlopen on the first cilqr_comm_unique_id / cilqr_comm_create
+// call -- libcilqr_hip.so has no link-time dependency on it, and a process that already holds an RCCL (PyTorch bundles
+// one) keeps using that one.  The second table is the loopback (loopback.hpp, cilqr_comm_create_loopback): a TEST hook
+// in which W handles of one process on one device form a communicator, host-synchronously, so that the W > 1 paths
+// below run where RCCL cannot (it refuses two ranks on one device).
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
@@ -26,14 +34,15 @@
 #include <vector>
 
 #include "dev_model.hpp"
+#include "loopback.hpp"
 #include "solver_priv.hpp"
 
 using namespace cilqr;
 
 namespace {
 
-struct Rccl {
-  void* lib = nullptr;
+struct Transport {
+  void* lib = nullptr;      // (RCCL only)
   decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
   decltype(&ncclCommInitRank) CommInitRank = nullptr;
   decltype(&ncclCommDestroy) CommDestroy = nullptr;
@@ -44,8 +53,8 @@ struct Rccl {
   decltype(&ncclGetErrorString) GetErrorString = nullptr;
 };
 
-Rccl* rccl() {
-  static Rccl r;
+Transport* rccl() {
+  static Transport r;
   static bool tried = false;
   if (tried) return r.lib ? &r : nullptr;
   tried = true;
@@ -89,6 +98,90 @@ Rccl* rccl() {
       return CILQR_ERR_DEVICE;                                                                      \
     }                                                                                               \
   } while (0)
+
+// ---- the loopback table: the same six signatures over loopback::Endpoint.  ncclGroupStart / ncclGroupEnd carry no
+// communicator, so the open group is the calling thread's (one communicator and one stream per group: all the gather needs)
+struct LoopComm {
+  std::unique_ptr<loopback::Endpoint> ep;
+};
+struct LoopGroup {
+  bool open = false;
+  LoopComm* lc = nullptr;
+  hipStream_t st = nullptr;
+};
+thread_local LoopGroup t_loop;
+
+ncclResult_t lb_result(loopback::Status s) {
+  switch (s) {
+    case loopback::Status::ok: return ncclSuccess;
+    case loopback::Status::mismatch: return ncclInvalidArgument;
+    case loopback::Status::timeout: return ncclSystemError;
+    case loopback::Status::copy_failed: return ncclUnhandledCudaError;
+    default: return ncclInvalidUsage;
+  }
+}
+const char* lb_GetErrorString(ncclResult_t r) {
+  switch (r) {
+    case ncclSuccess: return loopback::status_string(loopback::Status::ok);
+    case ncclInvalidArgument: return loopback::status_string(loopback::Status::mismatch);
+    case ncclSystemError: return loopback::status_string(loopback::Status::timeout);
+    case ncclUnhandledCudaError: return loopback::status_string(loopback::Status::copy_failed);
+    default: return loopback::status_string(loopback::Status::usage);
+  }
+}
+ncclResult_t lb_GroupStart() {
+  if (t_loop.open) return ncclInvalidUsage;
+  t_loop = LoopGroup{true, nullptr, nullptr};
+  return ncclSuccess;
+}
+ncclResult_t lb_record(bool is_send, void* buf, size_t count, ncclDataType_t type, int peer, ncclComm_t comm, hipStream_t st) {
+  LoopComm* lc = reinterpret_cast<LoopComm*>(comm);
+  if (!t_loop.open || lc == nullptr || (type != ncclInt64 && type != ncclFloat64)) return ncclInvalidUsage;
+  if (t_loop.lc == nullptr) {
+    t_loop.lc = lc;
+    t_loop.st = st;
+    (void)lc->ep->group_start();
+  } else if (t_loop.lc != lc || t_loop.st != st) {
+    return ncclInvalidUsage;
+  }
+  return lb_result(is_send ? lc->ep->send(buf, count, (int)type, 8, peer) : lc->ep->recv(buf, count, (int)type, 8, peer));
+}
+ncclResult_t lb_Send(const void* buf, size_t count, ncclDataType_t type, int peer, ncclComm_t comm, hipStream_t st) {
+  return lb_record(true, const_cast<void*>(buf), count, type, peer, comm, st);
+}
+ncclResult_t lb_Recv(void* buf, size_t count, ncclDataType_t type, int peer, ncclComm_t comm, hipStream_t st) {
+  return lb_record(false, buf, count, type, peer, comm, st);
+}
+ncclResult_t lb_GroupEnd() {
+  if (!t_loop.open) return ncclInvalidUsage;
+  const LoopGroup g = t_loop;
+  t_loop = LoopGroup{};
+  if (g.lc == nullptr) return ncclSuccess;
+  hipStream_t st = g.st;
+  // the sender completes its own stream; the receiver copies on its own stream and completes it: no stream waits for another
+  return lb_result(g.lc->ep->group_end(
+      [st] { return hipStreamSynchronize(st) == hipSuccess; },
+      [st](void* dst, const void* src, size_t bytes) {
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+      }));
+}
+ncclResult_t lb_CommDestroy(ncclComm_t comm) {
+  delete reinterpret_cast<LoopComm*>(comm);
+  return ncclSuccess;
+}
+Transport* loopback_table() {
+  static Transport t = [] {
+    Transport l;
+    l.CommDestroy = lb_CommDestroy;
+    l.Send = lb_Send;
+    l.Recv = lb_Recv;
+    l.GroupStart = lb_GroupStart;
+    l.GroupEnd = lb_GroupEnd;
+    l.GetErrorString = lb_GetErrorString;
+    return l;
+  }();
+  return &t;
+}
 
 constexpr int kTravelCols = 8;   // x y theta v a delta jerk delta_rate
 
@@ -211,6 +304,7 @@ __global__ void k_unpack_rows(const double* __restrict__ rows, const int* __rest
 }  // namespace
 
 struct cilqr_comm {
+  const Transport* transport = nullptr;   // the table this communicator was created with (RCCL, or the loopback test hook)
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1;
   dev_mem send;             // this rank's payload
@@ -221,8 +315,7 @@ struct cilqr_comm {
   pinned_mem h_totals;      // its host copy
   int agreed_batch = -1;    // the batch every rank was seen to hold (first use, and whenever this rank's changes)
   ~cilqr_comm() {           // (the communicator goes before the buffers it may still use)
-    Rccl* R = rccl();
-    if (comm && R) (void)R->CommDestroy(comm);
+    if (comm && transport) (void)transport->CommDestroy(comm);
   }
 };
 
@@ -235,7 +328,7 @@ extern "C" {
 
 int cilqr_comm_unique_id(uint8_t* id) {
   if (id == nullptr) return CILQR_ERR_NULL;
-  Rccl* R = rccl();
+  Transport* R = rccl();
   if (R == nullptr) {
     std::snprintf(g_last_hip_error, sizeof(g_last_hip_error), "librccl.so.1 could not be loaded: %s", dlerror());
     return CILQR_ERR_DEVICE;
@@ -251,7 +344,7 @@ int cilqr_comm_create(cilqr_handle h, const uint8_t* id, int32_t rank, int32_t w
   if (h == nullptr || id == nullptr) return CILQR_ERR_NULL;
   if (world < 1 || rank < 0 || rank >= world) return CILQR_ERR_ARG;
   if (h->comm != nullptr) return CILQR_ERR_STATE;
-  Rccl* R = rccl();
+  Transport* R = rccl();
   if (R == nullptr) {
     std::snprintf(g_last_hip_error, sizeof(g_last_hip_error), "librccl.so.1 could not be loaded: %s", dlerror());
     return CILQR_ERR_DEVICE;
@@ -259,6 +352,7 @@ int cilqr_comm_create(cilqr_handle h, const uint8_t* id, int32_t rank, int32_t w
   HIP_TRY(hipSetDevice(h->device));
   std::unique_ptr<cilqr_comm> c(new (std::nothrow) cilqr_comm());
   if (c == nullptr) return CILQR_ERR_DEVICE;
+  c->transport = R;
   c->rank = rank;
   c->world = world;
   ncclUniqueId u;
@@ -270,6 +364,30 @@ int cilqr_comm_create(cilqr_handle h, const uint8_t* id, int32_t rank, int32_t w
                   (r_ != ncclSuccess && R->GetErrorString) ? R->GetErrorString(r_) : "allocation failed");
     return CILQR_ERR_DEVICE;
   }
+  h->comm = c.release();
+  return CILQR_OK;
+}
+
+int cilqr_comm_create_loopback(cilqr_handle h, uint64_t group, int32_t rank, int32_t world, int32_t timeout_ms) {
+  if (h == nullptr) return CILQR_ERR_NULL;
+  if (world < 1 || rank < 0 || rank >= world || timeout_ms <= 0) return CILQR_ERR_ARG;
+  if (h->comm != nullptr) return CILQR_ERR_STATE;
+  HIP_TRY(hipSetDevice(h->device));
+  std::unique_ptr<cilqr_comm> c(new (std::nothrow) cilqr_comm());
+  std::unique_ptr<LoopComm> lc(new (std::nothrow) LoopComm());
+  if (c == nullptr || lc == nullptr) return CILQR_ERR_DEVICE;
+  const loopback::Status s = loopback::Endpoint::create(group, rank, world, timeout_ms, &lc->ep);
+  if (s != loopback::Status::ok) {
+    std::snprintf(g_last_hip_error, sizeof(g_last_hip_error), "cilqr_comm_create_loopback(rank %d of %d) -> %s", rank, world,
+                  loopback::status_string(s));
+    return CILQR_ERR_ARG;
+  }
+  c->transport = loopback_table();
+  c->rank = rank;
+  c->world = world;
+  c->comm = reinterpret_cast<ncclComm_t>(lc.release());
+  const size_t n_totals = (size_t)(4 * world + 8) * sizeof(long long);
+  if (c->totals.alloc(n_totals) != hipSuccess || c->h_totals.alloc(n_totals) != hipSuccess) return CILQR_ERR_DEVICE;
   h->comm = c.release();
   return CILQR_OK;
 }
@@ -308,8 +426,7 @@ int cilqr_gather_results(cilqr_handle h, int32_t batch, const cilqr_solution_bat
         gathered->status == nullptr)
       return CILQR_ERR_NULL;
   }
-  Rccl* R = rccl();
-  if (R == nullptr) return CILQR_ERR_DEVICE;
+  const Transport* R = c->transport;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = h->stream;
   const int B = batch, K = h->cfg.n_steps + 1, M1 = h->cfg.max_iter + 1, W = c->world;

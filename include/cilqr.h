@@ -398,6 +398,18 @@ int cilqr_stage_read(cilqr_handle h, int32_t tensor, double* dst, int32_t memory
 int cilqr_stage_nearest_lane(cilqr_handle h, int32_t n, const double* xy, int32_t* left, int32_t* right,
                              int32_t use_grid, int32_t memory);
 
+/* ---- test hooks (no product path calls these) ----
+ * cilqr_comm_create_loopback: a communicator for cilqr_gather_results whose `world` ranks are handles of ONE process on
+ * ONE device, so that the paths of the gather that need more than one rank run on a machine with one GPU (RCCL refuses
+ * two ranks on one device).  Handles that name the same `group` (any number; process-wide) form the communicator; every
+ * rank is driven by a thread of its own.  The exchange is host-synchronous: a sender completes its stream and publishes
+ * its buffer, the receiver copies it device-to-device on its own stream and completes that -- no stream waits for
+ * another, so the order of work between streams that RCCL relies on is NOT exercised.  Every wait for a peer ends after
+ * `timeout_ms` with CILQR_ERR_DEVICE; a send and a receive whose counts differ fail on both sides at once, also with
+ * CILQR_ERR_DEVICE.  CILQR_ERR_ARG when the rank is taken or the group exists with another world.  Destroyed with
+ * cilqr_comm_destroy, like any communicator. */
+int cilqr_comm_create_loopback(cilqr_handle h, uint64_t group, int32_t rank, int32_t world, int32_t timeout_ms);
+
 /* ---- corridor producer: the inputs of cilqr_problem_batch from obstacle points ---- */
 
 /* CorridorConfig, algorithm/params/planner_config.h:75-86 */
@@ -1035,7 +1047,12 @@ int64_t cilqr_pool_device_bytes(cilqr_pool_handle p);
  * the LIVE Cost rows only (n_cost[b] of the max_iter + 1), n_cost, status, n_iter.
  * `local` and `gathered` must be CILQR_MEM_DEVICE; `gathered` (root only, NULL elsewhere) holds
  * world * batch problems in rank order: traj [world*batch][K][10], cost_hist [world*batch][max_iter+1][5]
- * (rows >= n_cost untouched), n_cost, status, n_iter (optional).  iter_trajs / alpha_trace do not travel. */
+ * (rows >= n_cost untouched), n_cost, status, n_iter (optional).  iter_trajs / alpha_trace do not travel.
+ * Every rank passes the same `batch` and `root`.  The library checks the batch where every rank takes part in the
+ * check: at a communicator's first gather, and at any gather for which every rank's batch differs from the batch last
+ * agreed on (all ranks moving to another batch together) -- ranks that disagree there get CILQR_ERR_ARG on every rank,
+ * nothing is written to `gathered`, and the communicator stays usable.  Beyond that, equal batches are a precondition:
+ * one rank that alone changes its batch between gathers breaks it, and the outcome under RCCL is undefined. */
 #define CILQR_UNIQUE_ID_BYTES 128
 int cilqr_comm_unique_id(uint8_t* id /* [CILQR_UNIQUE_ID_BYTES] */);
 int cilqr_comm_create(cilqr_handle h, const uint8_t* id, int32_t rank, int32_t world);
