@@ -182,6 +182,7 @@ EXPORTS = [
     "cilqr_clearance_rows", "cilqr_clearance_rows_batch",
     "cilqr_constraint_margins", "cilqr_constraint_margins_batch",
     "cilqr_track_rows", "cilqr_track_rows_batch",
+    "cilqr_window_scene", "cilqr_window_scenes_batch", "cilqr_plan_scenes_batch_warm",
     "cilqr_road_barriers", "cilqr_default_tracker_config",
     "cilqr_set_tracker_config",
     "cilqr_solve_batch_warm", "cilqr_submit_warm", "cilqr_stage_load_warm", "cilqr_pool_submit_warm", "cilqr_multi_solve_warm",
@@ -261,6 +262,14 @@ def lib():
         L.cilqr_plan_scenes_batch.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(CorridorConfig),
                                               C.POINTER(SceneBatchStruct), C.c_void_p, C.c_int32, C.POINTER(SolutionBatch),
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.cilqr_plan_scenes_batch_warm.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(CorridorConfig),
+                                                   C.POINTER(SceneBatchStruct), C.c_void_p, C.c_int32, C.POINTER(WarmStart),
+                                                   C.POINTER(SolutionBatch), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.cilqr_window_scene.argtypes = [C.POINTER(SceneStruct), C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_int32)]
+        L.cilqr_window_scenes_batch.argtypes = [C.c_void_p, C.POINTER(SceneBatchStruct), C.c_void_p, C.c_double, C.c_int32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.cilqr_check_collisions.argtypes = [C.POINTER(DpConfig), C.POINTER(SceneStruct), C.c_int32, C.c_void_p, C.c_int32,
                                              C.c_double, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.cilqr_check_collisions_batch.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(SceneBatchStruct), C.c_int32,
@@ -759,12 +768,13 @@ class BatchIlqrOptimizer:
                                                max_points, points_ptr, count_ptr, ok_ptr)
 
     def plan_scenes(self, packed: dict, start, dp_cfg: "DpConfig | None" = None, corridor_cfg: "CorridorConfig | None" = None,
-                    alpha_trace: bool = False):
+                    alpha_trace: bool = False, warm=None):
         """TrajectoryPlanner::Plan for a batch of scenes on the GPU (cilqr_plan_scenes_batch), host arrays: DP -> obstacle
         points -> corridors (the handle's cmax) -> lane constraints -> solve -> result rows.  `packed` =
         scene_io.pack_scene_batch(center, scenes), start [B,4] = x, y, theta, v.  Returns the dict of plan() plus plan
         [B,K,11] = time s x y theta kappa velocity a delta jerk delta_rate, dp [B,K,9], outcome [B] int32 (PLAN_OK /
-        PLAN_DP_FAILED / PLAN_CORRIDOR_FAILED), n_dp_failed, n_corridor_failed."""
+        PLAN_DP_FAILED / PLAN_CORRIDOR_FAILED), n_dp_failed, n_corridor_failed.  warm = (rows, shift, layout) as make_warm
+        takes it, NumPy arrays: the solve starts from those controls (cilqr_plan_scenes_batch_warm); None: the plain call."""
         dp_cfg = dp_cfg or default_dp_config(tf=self.N * self.cfg.dt, delta_t=self.cfg.dt)
         corridor_cfg = corridor_cfg or default_corridor_config()
         B, K, M = int(packed["batch"]), self.K, self.cfg.max_iter
@@ -778,22 +788,71 @@ class BatchIlqrOptimizer:
         at = np.full((B, M), -3, np.int8) if alpha_trace else None
         sol = SolutionBatch(MEM_HOST, 0, _ptr(traj), _ptr(hist), _ptr(n_cost), _ptr(status), _ptr(n_iter), None, None, _ptr(at))
         plan, dp, outcome = np.zeros((B, K, PLAN_FIELDS)), np.zeros((B, K, COARSE_FIELDS)), np.zeros(B, np.int32)
-        rc, n_dp, n_cor = self.plan_scenes_raw(dp_cfg, corridor_cfg, sb, _ptr(start), K, sol, _ptr(plan), _ptr(dp), _ptr(outcome))
+        w, keep_warm = make_warm(warm, self.N)
+        rc, n_dp, n_cor = self.plan_scenes_raw(dp_cfg, corridor_cfg, sb, _ptr(start), K, sol, _ptr(plan), _ptr(dp), _ptr(outcome),
+                                               warm=w)
+        del keep_warm
         self._chk(rc, "plan_scenes")
         self.B = B
         return dict(rc=rc, traj=traj, cost_hist=hist, n_cost=n_cost, status=status, n_iter=n_iter, alpha_trace=at, plan=plan,
                     dp=dp, outcome=outcome, n_dp_failed=n_dp, n_corridor_failed=n_cor)
 
     def plan_scenes_raw(self, dp_cfg, corridor_cfg, scene_batch, start_ptr, n_knots, sol: SolutionBatch, plan_ptr=None,
-                        coarse9_ptr=None, outcome_ptr=None):
+                        coarse9_ptr=None, outcome_ptr=None, warm: "WarmStart | None" = None):
         """Pointer-level form (start / plan / coarse9 / outcome in device or host memory as scene_batch.memory says, the
-        solver's outputs as sol.memory says); returns (rc, n_dp_failed, n_corridor_failed)."""
+        solver's outputs as sol.memory says); warm: a WarmStart in the memory of the scenes (cilqr_plan_scenes_batch_warm),
+        None: the plain call.  Returns (rc, n_dp_failed, n_corridor_failed)."""
         n_dp, n_cor = C.c_int32(0), C.c_int32(0)
-        rc = self.L.cilqr_plan_scenes_batch(self.h, C.byref(dp_cfg) if dp_cfg is not None else None,
-                                            C.byref(corridor_cfg) if corridor_cfg is not None else None, C.byref(scene_batch),
-                                            start_ptr, n_knots, C.byref(sol), plan_ptr, coarse9_ptr, outcome_ptr,
-                                            C.byref(n_dp), C.byref(n_cor))
+        dp_ref = C.byref(dp_cfg) if dp_cfg is not None else None
+        cor_ref = C.byref(corridor_cfg) if corridor_cfg is not None else None
+        if warm is None:
+            rc = self.L.cilqr_plan_scenes_batch(self.h, dp_ref, cor_ref, C.byref(scene_batch), start_ptr, n_knots,
+                                                C.byref(sol), plan_ptr, coarse9_ptr, outcome_ptr, C.byref(n_dp), C.byref(n_cor))
+        else:
+            rc = self.L.cilqr_plan_scenes_batch_warm(self.h, dp_ref, cor_ref, C.byref(scene_batch), start_ptr, n_knots,
+                                                     C.byref(warm), C.byref(sol), plan_ptr, coarse9_ptr, outcome_ptr,
+                                                     C.byref(n_dp), C.byref(n_cor))
         return rc, int(n_dp.value), int(n_cor.value)
+
+    def window_scenes(self, packed: dict, t0, span: float, out_samples: "int | None" = None):
+        """The scenes of a batch on the clocks of a later planning cycle, on the GPU (cilqr_window_scenes_batch), host
+        arrays: scene b as a cycle that starts at scene time t0[b] reads it on 0 ... span.  `packed` =
+        scene_io.pack_scene_batch(center, scenes) -- its max_samples may exceed DP_MAX_SAMPLES --, t0 [B] (or one value for
+        all).  Returns a packed dict that shares every other array with `packed`: dynamic_trajectories [B,D,out_samples,4]
+        (zeros behind a count), dynamic_trajectory_counts [B,D] (-1: the window does not fit out_samples), max_samples =
+        out_samples, plus window_ok [B] bool and n_overflow.  out_samples defaults to the largest window of the batch."""
+        from . import scene_io
+        B, D = int(packed["batch"]), int(packed["max_dynamic"])
+        t0 = np.ascontiguousarray(np.broadcast_to(_f64(t0).ravel(), (B,)))
+        src = _f64(packed["dynamic_trajectories"])
+        src_counts = np.ascontiguousarray(packed["dynamic_trajectory_counts"], dtype=np.int32)
+        if out_samples is None:
+            out_samples = 1
+            for b in range(B):
+                for d in range(D):
+                    lo, hi = scene_io.window_bounds(src[b, d, :max(0, int(src_counts[b, d])), 0], t0[b], span)
+                    out_samples = max(out_samples, hi - lo + 1)
+        out_samples = int(out_samples)
+        keep = {k: np.ascontiguousarray(v) for k, v in packed.items() if isinstance(v, np.ndarray)}
+        keep["dynamic_trajectories"], keep["dynamic_trajectory_counts"] = src, src_counts
+        sb = scene_batch_struct(packed, MEM_HOST, **{k: _ptr(keep[k]) for k in _SCENE_BATCH_ARRAYS})
+        win = np.zeros((B, D, max(out_samples, 0), 4))
+        counts, ok = np.zeros((B, D), dtype=np.int32), np.zeros(B, dtype=np.int32)
+        rc, n = self.window_scenes_raw(sb, _ptr(t0), span, out_samples, _ptr(win), _ptr(counts), _ptr(ok))
+        self._chk(rc, "window_scenes")
+        out = dict(packed)
+        out.update(max_samples=out_samples, dynamic_trajectories=win, dynamic_trajectory_counts=counts,
+                   window_ok=ok.astype(bool), n_overflow=n)
+        return out
+
+    def window_scenes_raw(self, scene_batch, t0_ptr, span, out_samples, trajectories_ptr, counts_ptr, ok_ptr=None):
+        """Pointer-level form (t0 / trajectories / counts / ok in device or host memory as scene_batch.memory says: a
+        SceneBatchStruct with these two arrays and max_samples = out_samples feeds plan_scenes_raw and the audits where
+        they lie); returns (rc, the number of scenes with ok = 0)."""
+        n = C.c_int32(0)
+        rc = self.L.cilqr_window_scenes_batch(self.h, C.byref(scene_batch), t0_ptr, C.c_double(span), out_samples,
+                                              trajectories_ptr, counts_ptr, ok_ptr, C.byref(n))
+        return rc, int(n.value)
 
     def check_collisions(self, packed: dict, rows, layout: int, cfg: "DpConfig | None" = None, buffer: float = 0.0):
         """Environment::CheckOptimizationCollision for every knot of a batch of trajectories on the GPU
@@ -1112,6 +1171,25 @@ def clearance_rows(flat: dict, rows, layout: int, cfg: "DpConfig | None" = None)
     if rc != OK:
         raise CilqrError(rc, "in cilqr_clearance_rows")
     return clearance, nearest, float(lowest.value), int(knot.value)
+
+
+def window_scene(flat: dict, t0: float, span: float, out_samples: int, trajectories=None):
+    """The window rule of include/cilqr.h ("scene window") for one scene through the C-ABI (cilqr_window_scene, host only).
+    `flat` = scene_io.flatten_scene(center, scene).  Returns (trajectories [D,out_samples,4], counts [D] int32 -- -1: the
+    window does not fit --, n_overflow); `trajectories`, if given, is written in place: rows past a count stay as they are."""
+    sc, keep = scene_struct(flat)
+    D = len(keep["dynamic_trajectory_counts"])
+    if trajectories is None:
+        trajectories = np.zeros((D, max(int(out_samples), 0), 4))
+    if not (isinstance(trajectories, np.ndarray) and trajectories.dtype == np.float64 and trajectories.flags.c_contiguous):
+        raise ValueError("trajectories must be a C-contiguous float64 array")
+    counts = np.zeros(D, dtype=np.int32)
+    n = C.c_int32(0)
+    rc = lib().cilqr_window_scene(C.byref(sc), C.c_double(t0), C.c_double(span), int(out_samples), trajectories.ctypes.data,
+                                  counts.ctypes.data, C.byref(n))
+    if rc != OK:
+        raise CilqrError(rc, "in cilqr_window_scene")
+    return trajectories, counts, int(n.value)
 
 
 def margin_problem(scene: dict, B: int, K: int):

@@ -3,10 +3,13 @@
 // algorithm/planner/dp_planner.cpp:135-281 with ComputePathProfile, discrete_points_math.cc:27-176) for
 // callers that are not C++ (the ctypes tests, the scene generator); cilqr_check_collisions asks DpEnvironment::CollisionMask
 // about every knot of a trajectory (Environment::CheckOptimizationCollision, environment.cpp:92-111), cilqr_clearance_rows
-// asks DpEnvironment::Clearance (Polygon2d::DistanceTo, polygon2d.cpp:43-52).  No device code in this file.
+// asks DpEnvironment::Clearance (Polygon2d::DistanceTo, polygon2d.cpp:43-52); cilqr_window_scene cuts the window of
+// include/cilqr/scene_window.hpp out of a scene's trajectories.  No device code in this file.
+#include <cmath>
 #include <limits>
 #include <vector>
 
+#include "../../include/cilqr/scene_window.hpp"
 #include "collision.hpp"
 #include "scene_batch.hpp"
 
@@ -209,6 +212,29 @@ int cilqr_clearance_rows(const cilqr_dp_config* cfg, const cilqr_scene* scene, i
   }
   *min_clearance = lowest;
   *min_knot = at;
+  return CILQR_OK;
+}
+
+int cilqr_window_scene(const cilqr_scene* scene, double t0, double span, int32_t out_samples, double* trajectories,
+                       int32_t* counts, int32_t* n_overflow) {
+  if (scene == nullptr) return CILQR_ERR_NULL;
+  if (scene->n_dynamic < 0) return CILQR_ERR_ARG;
+  if (scene->n_dynamic > 0 && (scene->dynamic_trajectories == nullptr || scene->dynamic_trajectory_counts == nullptr ||
+                               trajectories == nullptr || counts == nullptr))
+    return CILQR_ERR_NULL;
+  if (!std::isfinite(t0) || !std::isfinite(span) || span < 0.0 || out_samples < 1) return CILQR_ERR_ARG;
+  for (int o = 0; o < scene->n_dynamic; ++o)
+    if (scene->dynamic_trajectory_counts[o] < 0) return CILQR_ERR_ARG;
+  size_t at = 0;
+  int overflow = 0;
+  for (int o = 0; o < scene->n_dynamic; ++o) {
+    const int T = scene->dynamic_trajectory_counts[o];
+    counts[o] = cilqr::scene_window::window_trajectory(scene->dynamic_trajectories + at * 4, T, t0, span, out_samples,
+                                                       trajectories + (size_t)o * out_samples * 4);
+    if (counts[o] < 0) ++overflow;
+    at += T;
+  }
+  if (n_overflow) *n_overflow = overflow;
   return CILQR_OK;
 }
 

@@ -1,6 +1,6 @@
-// cilqr_scene_points_batch and cilqr_plan_scenes_batch (include/cilqr.h): the host side -- argument checks, the handle's
+// cilqr_scene_points_batch and cilqr_plan_scenes_batch / _warm (include/cilqr.h): the host side -- argument checks, the handle's
 // work space, staging of HOST arrays, the launches of kernels_scene_points.hip and, for the pipeline, the calls of the
-// stages it chains (cilqr_dp_plan_batch, cilqr_build_corridors, cilqr_solve_batch: the public entry points on device
+// stages it chains (cilqr_dp_plan_batch, cilqr_build_corridors, cilqr_solve_batch_warm: the public entry points on device
 // views, so that what they compute is what a caller of the four calls gets).
 #include <algorithm>
 #include <cstring>
@@ -88,10 +88,13 @@ extern "C" int cilqr_scene_points_batch(cilqr_handle h, const cilqr_scene_batch*
   return CILQR_OK;
 }
 
-extern "C" int cilqr_plan_scenes_batch(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilqr_corridor_config* corridor_cfg,
-                                       const cilqr_scene_batch* scenes, const double* start4, int32_t n_knots,
-                                       cilqr_solution_batch* out, double* plan, double* coarse9, int32_t* outcome,
-                                       int32_t* n_dp_failed, int32_t* n_corridor_failed) {
+namespace {
+
+// the body of both pipeline entry points; `warm` NULL: the plain call (cilqr_solve_batch_warm with NULL is cilqr_solve_batch)
+int plan_scenes(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilqr_corridor_config* corridor_cfg,
+                const cilqr_scene_batch* scenes, const double* start4, int32_t n_knots, const cilqr_warm_start* warm,
+                cilqr_solution_batch* out, double* plan, double* coarse9, int32_t* outcome, int32_t* n_dp_failed,
+                int32_t* n_corridor_failed) {
   if (h == nullptr || dp_cfg == nullptr || corridor_cfg == nullptr || scenes == nullptr || start4 == nullptr ||
       out == nullptr || scenes->center == nullptr)
     return CILQR_ERR_NULL;
@@ -103,6 +106,15 @@ extern "C" int cilqr_plan_scenes_batch(cilqr_handle h, const cilqr_dp_config* dp
   if (out->memory != CILQR_MEM_HOST && out->memory != CILQR_MEM_DEVICE) return CILQR_ERR_ARG;
   if ((int32_t)(dp_cfg->tf / dp_cfg->delta_t + 1) != n_knots || n_knots != h->cfg.n_steps + 1) return CILQR_ERR_KNOTS;
   if (beyond_limits(sb, n_knots) || sb.batch > h->capacity) return CILQR_ERR_CAPACITY;
+  // the warm start against the problem batch the solve will get: n_knots knots, its arrays where the scenes are
+  int w_stride = 0, w_rows = 0, w_col = 0;
+  if (warm != nullptr) {
+    cilqr_problem_batch like;
+    std::memset(&like, 0, sizeof(like));
+    like.batch = sb.batch; like.n_knots = n_knots; like.memory = sb.memory;
+    if (int rc = cilqr_check_warm(&like, warm)) return rc;
+    cilqr_warm_geometry(warm->layout, n_knots, &w_stride, &w_rows, &w_col);
+  }
   const int per_vertex = corridor_cfg->is_multiple_sample ? 6 : 1;
   const int max_points = worst_case_points(sb, per_vertex);
   if (max_points + (corridor_cfg->is_multiple_sample ? 24 : 8) > kCorMaxPts) return CILQR_ERR_CAPACITY;
@@ -136,6 +148,7 @@ extern "C" int cilqr_plan_scenes_batch(cilqr_handle h, const cilqr_dp_config* dp
   const SceneImage im(l_work, sb);
   const slot s_s4 = l_work.add(B * 4 * 8), s_plan = l_work.add(plan ? B * K * CILQR_PLAN_FIELDS * 8 : 0);
   const slot s_c9 = l_work.add(coarse9 ? B * K * CILQR_COARSE_FIELDS * 8 : 0), s_outcome = l_work.add(outcome ? B * 4 : 0);
+  const slot s_wrows = l_work.add(warm ? B * (size_t)w_rows * w_stride * 8 : 0), s_wshift = l_work.add(warm && warm->shift ? B * 4 : 0);
   HIP_TRY(h->ps_work.grow((on_host ? l_work.bytes() : b_device) + 256, &h->grown_bytes));
   const size_t per_scene = K * ((size_t)max_points * 2 * 8 + 4);
   size_t chunk = std::min(B, std::max<size_t>(1, kPointsBytesCap / per_scene));
@@ -159,6 +172,17 @@ extern "C" int cilqr_plan_scenes_batch(cilqr_handle h, const cilqr_dp_config* dp
     if (plan) d_plan = s_plan.in<double>(w);
     if (coarse9) d_c9 = s_c9.in<double>(w);
     if (outcome) d_outcome = s_outcome.in<int>(w);
+  }
+  cilqr_warm_start dw;   // the warm start as the solve on device views takes it
+  if (warm != nullptr) {
+    dw = *warm;
+    dw.memory = CILQR_MEM_DEVICE;
+    if (on_host) {
+      if (int rc = copy_in(w, s_wrows, warm->rows, st)) return rc;
+      if (int rc = copy_in(w, s_wshift, warm->shift, st)) return rc;
+      dw.rows = s_wrows.in<const double>(w);
+      dw.shift = warm->shift ? s_wshift.in<const int32_t>(w) : nullptr;
+    }
   }
   HIP_TRY(hipMemsetAsync(d_counts, 0, s_counts.bytes, st));
 
@@ -193,7 +217,7 @@ extern "C" int cilqr_plan_scenes_batch(cilqr_handle h, const cilqr_dp_config* dp
   prob.start = d_s4; prob.coarse = d_c6; prob.corridor = d_cor; prob.corridor_count = d_ccnt;
   prob.n_left = n_left; prob.n_right = n_right; prob.left_lane = left_rows.data(); prob.right_lane = right_rows.data();
   prob.coarse_station = d_stn;
-  if (int rc = cilqr_solve_batch(h, &prob, out)) return rc;
+  if (int rc = cilqr_solve_batch_warm(h, &prob, warm ? &dw : nullptr, out)) return rc;
 
   // ---- the result rows (trajectory_planner.cpp:101-125) and the way back
   if (plan) {
@@ -216,4 +240,23 @@ extern "C" int cilqr_plan_scenes_batch(cilqr_handle h, const cilqr_dp_config* dp
   if (n_dp_failed) *n_dp_failed = counts_host[0];
   if (n_corridor_failed) *n_corridor_failed = counts_host[1];
   return CILQR_OK;
+}
+
+}  // namespace
+
+extern "C" int cilqr_plan_scenes_batch(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilqr_corridor_config* corridor_cfg,
+                                       const cilqr_scene_batch* scenes, const double* start4, int32_t n_knots,
+                                       cilqr_solution_batch* out, double* plan, double* coarse9, int32_t* outcome,
+                                       int32_t* n_dp_failed, int32_t* n_corridor_failed) {
+  return plan_scenes(h, dp_cfg, corridor_cfg, scenes, start4, n_knots, nullptr, out, plan, coarse9, outcome, n_dp_failed,
+                     n_corridor_failed);
+}
+
+extern "C" int cilqr_plan_scenes_batch_warm(cilqr_handle h, const cilqr_dp_config* dp_cfg,
+                                            const cilqr_corridor_config* corridor_cfg, const cilqr_scene_batch* scenes,
+                                            const double* start4, int32_t n_knots, const cilqr_warm_start* warm,
+                                            cilqr_solution_batch* out, double* plan, double* coarse9, int32_t* outcome,
+                                            int32_t* n_dp_failed, int32_t* n_corridor_failed) {
+  return plan_scenes(h, dp_cfg, corridor_cfg, scenes, start4, n_knots, warm, out, plan, coarse9, outcome, n_dp_failed,
+                     n_corridor_failed);
 }

@@ -275,6 +275,10 @@ struct cilqr_solver {
   // table of the call (track.hpp), the staging of HOST rows and start states, of HOST driven rows and flags
   cilqr::pinned_mem tk_tab_host;
   cilqr::dev_mem tk_tab, tk_work, tk_in, tk_out;
+  // cilqr_window_scenes_batch (scene_window_batch.hip), grown likewise: the count of failed scenes and its way back, the
+  // staging of HOST source trajectories, counts and t0, of HOST windows, counts and flags
+  cilqr::pinned_mem sw_tab_host;
+  cilqr::dev_mem sw_tab, sw_in, sw_out;
 };
 
 namespace cilqr {

@@ -535,6 +535,62 @@ def unpack_scene(packed: dict, b: int) -> dict:
         dynamic_trajectory_counts=tc[do].astype(np.int32))
 
 
+WINDOW_MARGIN = 1e-9   # include/cilqr.h, "scene window"
+
+
+def _first_true(T: int, pred) -> int:
+    """std::lower_bound's halving written out over a predicate (the window rule's two searches)."""
+    first, n = 0, T
+    while n > 0:
+        half = n >> 1
+        if not pred(first + half):
+            first += half + 1
+            n -= half + 1
+        else:
+            n = half
+    return first
+
+
+def window_bounds(times, t0: float, span: float) -> tuple:
+    """(lo, hi) of the window rule for sample times [T]: the samples a scene that starts at t0 reads on 0 ... span;
+    (0, -1) for T < 1."""
+    s = np.asarray(times, dtype=np.float64) - np.float64(t0)
+    T = len(s)
+    if T < 1:
+        return 0, -1
+    upper = np.float64(span) + np.float64(WINDOW_MARGIN)
+    L = _first_true(T, lambda k: not (s[k] < -WINDOW_MARGIN))
+    H = _first_true(T, lambda k: bool(upper < s[k]))
+    return max(0, L - 1), min(T - 1, H)
+
+
+def window_trajectory(traj, t0: float, span: float) -> np.ndarray:
+    """The window rule of include/cilqr.h ("scene window") in NumPy: the samples lo ... hi of traj [T,4] = time x y theta
+    with the time column on the clock time - t0 (one rounding), the other columns untouched.  [count,4]."""
+    traj = np.asarray(traj, dtype=np.float64).reshape(-1, 4)
+    lo, hi = window_bounds(traj[:, 0], t0, span)
+    out = traj[lo:hi + 1].copy()
+    out[:, 0] = out[:, 0] - np.float64(t0)
+    return out
+
+
+def window_scene(scene: Scene, t0: float, span: float) -> Scene:
+    """`scene` as a planning cycle that starts at scene time t0 reads it: every dynamic trajectory cut to its window."""
+    return Scene(start=scene.start, coarse=scene.coarse, static=scene.static,
+                 dynamic=[DynamicObstacle(polygon=d.polygon, trajectory=window_trajectory(d.trajectory, t0, span))
+                          for d in scene.dynamic])
+
+
+def shift_scene(scene: Scene, t0: float) -> Scene:
+    """`scene` with every sample of every dynamic trajectory on the clock time - t0: what the window is cut out of."""
+    def shifted(t):
+        t = np.asarray(t, dtype=np.float64).reshape(-1, 4).copy()
+        t[:, 0] = t[:, 0] - np.float64(t0)
+        return t
+    return Scene(start=scene.start, coarse=scene.coarse, static=scene.static,
+                 dynamic=[DynamicObstacle(polygon=d.polygon, trajectory=shifted(d.trajectory)) for d in scene.dynamic])
+
+
 # ---------------------------------------------------------------------------------------------
 # the reference's own scene artefact: reference.pickle
 # ---------------------------------------------------------------------------------------------

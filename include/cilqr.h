@@ -979,6 +979,88 @@ int cilqr_plan_scenes_batch(cilqr_handle h, const cilqr_dp_config* dp_cfg, const
                             const cilqr_scene_batch* scenes, const double* start4, int32_t n_knots,
                             cilqr_solution_batch* out, double* plan, double* coarse9, int32_t* outcome,
                             int32_t* n_dp_failed, int32_t* n_corridor_failed);
+/* ... with a warm start (see cilqr_solve_batch_warm): the pipeline of the second and every later planning cycle.  `warm` is
+ * the cilqr_warm_start of the solve at the pipeline's end, for the B scenes in their order; warm->memory must equal
+ * scenes->memory (HOST rows and shifts are staged into the pipeline's work space).  warm == NULL is exactly
+ * cilqr_plan_scenes_batch.  The results are, bit for bit, those of the four calls made one after the other with
+ * cilqr_solve_batch_warm last: a scene with shift < 0 has the bits of the cold pipeline, and one the pipeline does not
+ * optimise (outcome != 0) ends with CILQR_ST_NO_CORRIDOR as there, its traj the first iterate.  The checks of cilqr_solve_batch_warm (CILQR_ERR_NULL for NULL rows, CILQR_ERR_ARG
+ * for an unknown layout, CILQR_ROWS_COARSE, a bad or differing memory flag) are made with the others, before anything is
+ * launched. */
+int cilqr_plan_scenes_batch_warm(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilqr_corridor_config* corridor_cfg,
+                                 const cilqr_scene_batch* scenes, const double* start4, int32_t n_knots,
+                                 const cilqr_warm_start* warm, cilqr_solution_batch* out, double* plan, double* coarse9,
+                                 int32_t* outcome, int32_t* n_dp_failed, int32_t* n_corridor_failed);
+
+/* ---- scene window: a scene on the clock of a later planning cycle (additive, ABI 7) ----
+ * Every scene call above reads a scene on the clock 0 ... tf, and a dynamic obstacle's samples carry absolute times.  To
+ * plan again at scene time t0 the trajectories have to be on the clock t - t0, and of a long recording only the samples
+ * the horizon can reach are wanted (CILQR_DP_MAX_SAMPLES holds for what the scene kernels read, not for what was recorded).
+ * The window rule, for ONE dynamic obstacle with T samples time x y theta (times taken as non-decreasing, as everywhere in
+ * the scene calls), a scene time t0, a span >= 0 and an output capacity out_samples; every operation is rounded once,
+ * s[k] = time[k] - t0:
+ *   T < 1:  count 0.  Otherwise
+ *   L = the first k with !(s[k] < -1e-9), T if there is none;             lo = max(0, L - 1)
+ *   H = the first k with (span + 1e-9) < s[k], T if there is none;        hi = min(T - 1, H)
+ *       both searches are std::lower_bound's halving written out over the predicate, as in the resample rule,
+ *           first = 0, len = T;  while (len > 0) { half = len >> 1;
+ *               if (!pred(first + half)) { first += half + 1; len -= half + 1; } else len = half; }
+ *       -- defined for any input, and L <= H on any input (the second predicate implies the first, so the two halvings
+ *       probe the same samples until they part, the first going left); so count >= 1 whenever T >= 1;
+ *   count = hi - lo + 1;  output sample j = (s[lo + j], then x, y, theta of sample lo + j copied as bits).
+ *   count > out_samples: the obstacle OVERFLOWS.  Its count is written as -1, not as 0: the scene calls then refuse the
+ *       scene (HOST arrays: CILQR_ERR_ARG; DEVICE arrays: the scene is reported invalid by the kernel that reads it) rather
+ *       than plan it without that obstacle.  A source count that is negative or above the source's max_samples is treated
+ *       the same way.  Nothing is written to the rows of such an obstacle.
+ * Why the window is safe.  scene_core.hpp: scene_present / scene_sample_index choose the sample an obstacle shows at a
+ * query time t, in a plain form (t < time[k]; present unless time[0] > t or time[T-1] < t) and in the 1e-10 form of the
+ * Query...Points rule (t < time[k] + 1e-10; time[0] > t + 1e-10, time[T-1] < t - 1e-10).  Take any t in [0, span].
+ *   - The chosen index is the first k with t < s[k] (+ 1e-10), T - 1 past the end.  Such a k has s[k] > -1e-10 (1 + 2^-52)
+ *     > -1e-9, so !(s[k] < -1e-9) holds and k >= L >= lo.  If H < T, s[H] > span + 1e-9 > t, so the first such k is <= H;
+ *     if H = T the index is at most T - 1.  Either way it is <= hi.
+ *   - Every sample below lo has s < -1e-9, so neither form chooses it and the search over samples lo ... hi finds the same
+ *     sample at index - lo; where the full search runs past the end (H = T) the window ends at T - 1 as well.
+ *   - Presence.  If lo > 0, s[lo] < -1e-9 <= t: both `first sample later than t` tests are false on s[lo], and on s[0] <=
+ *     s[lo] too.  If hi < T - 1, s[hi] > span + 1e-9 >= t + 1e-9: both `last sample earlier than t` tests are false on
+ *     s[hi], and on s[T-1] >= s[hi] too.  Otherwise the window's end sample is the trajectory's.
+ * So the window is not only close to the full shifted trajectory (time - t0, x, y, theta for all T samples): every scene
+ * call returns the same bits on both, for knot and row times in [0, span].  The margins of 1e-9 against the rule's 1e-10
+ * are what make this hold under rounding: a sum t + 1e-10 or s + 1e-10 is off by less than 1e-25 at these magnitudes.
+ *
+ * cilqr_window_scene: one scene on the host, no handle (C++ callers use include/cilqr/scene_window.hpp directly).  No limit
+ * is placed on the source sample counts.
+ *   trajectories [n_dynamic][out_samples][4], counts [n_dynamic]; rows past an obstacle's count are left untouched
+ *   *n_overflow (optional): the obstacles that overflowed
+ * CILQR_ERR_NULL; CILQR_ERR_ARG for a non-finite t0, a span that is non-finite or negative, out_samples < 1, n_dynamic < 0
+ * and a negative count. */
+int cilqr_window_scene(const cilqr_scene* scene, double t0, double span, int32_t out_samples,
+                       double* trajectories /* [n_dynamic][out_samples][4] */, int32_t* counts /* [n_dynamic] */,
+                       int32_t* n_overflow);
+/* ---- the same for B scenes per call, each at its own t0, on the GPU (kernels_scene_window.hip) ----
+ * The windows of a batch that is resident on the device: a cilqr_scene_batch with dynamic_trajectories = `trajectories`,
+ * dynamic_trajectory_counts = `counts`, max_samples = out_samples and every other member as in `scenes` is the batch on the
+ * clocks t - t0[b], and nothing but t0 crosses to the device per cycle.  scenes->max_samples may be any positive value:
+ * this call alone does not hold the source to CILQR_DP_MAX_SAMPLES (CILQR_ERR_CAPACITY for out_samples beyond it).
+ *   t0           [B]                                     (memory as scenes->memory, like the three arrays below)
+ *   trajectories [B][max_dynamic][out_samples][4]        rows past a count are left untouched
+ *   counts       [B][max_dynamic]
+ *   ok           [B] 1 / 0, optional (NULL to skip): 0 where one of the scene's counts is -1
+ *   *n_overflow  (HOST, optional): the scenes with ok = 0
+ * One wavefront per (scene, slot); the two searches are made by the wave together (64 probes and one ballot per round)
+ * and return what the halving returns on non-decreasing times (on times that decrease the wave's two searches can cross;
+ * such an obstacle is refused with count -1).  Every element is the host call's bit for bit; a scene's windows do not depend
+ * on the batch around it; no alignment beyond a double's is assumed.  Runs on the handle's stream and waits for that stream
+ * only; DEVICE arrays need no work space beyond the count, HOST arrays are staged in blocks that belong to the handle and
+ * grow to the largest call.  Checked before anything is launched, the handle staying usable: CILQR_ERR_NULL;
+ * CILQR_ERR_ARG for a bad batch, sizes or memory flag, a span that is non-finite or negative, out_samples < 1 and -- HOST
+ * arrays -- a non-finite t0[b] or a source count that is negative or above max_samples; CILQR_ERR_CAPACITY as above;
+ * CILQR_ERR_STATE while solves are submitted on the handle.  With DEVICE arrays t0 and the counts are checked in the
+ * kernel: a non-finite t0[b] or a bad source count gives every slot of that scene the count -1 and ok 0, the other scenes
+ * are unaffected. */
+int cilqr_window_scenes_batch(cilqr_handle h, const cilqr_scene_batch* scenes, const double* t0 /* [B] */, double span,
+                              int32_t out_samples, double* trajectories /* [B][max_dynamic][out_samples][4] */,
+                              int32_t* counts /* [B][max_dynamic] */, int32_t* ok /* [B], optional */,
+                              int32_t* n_overflow /* HOST, optional */);
 
 /* ---- several GPUs from ONE host process (the reference's caller is one process:
  * algorithm/planning_node.cc:9-31) ----
