@@ -1534,6 +1534,30 @@ def test_delta_v_evaluation_switch():
     rep = json.loads(r.stdout.strip().splitlines()[-1])
     assert rep["ok"] and rep["steps"]["steps"] > 1000
     print(f"\neager delta_V build: {rep}")
+    # the child held the eager library to the long-double statement's eager reading on the crafted table (dv_eval_check.py:
+    # eager_against_the_statement); the PRODUCT library's delta_V on the same table and lambdas is not that reading's -- the
+    # switch matters there too -- while its gains are the statement's
+    import riccati_cases as rc
+    import riccati_reference as rr
+    import stage_cases as stc
+    assert max(rep["eager_statement_on_the_table"]["worst_vs_eager_statement"].values()) < 1e-9
+    g = stc.evaluate("default", True, 1)[stc.MAIN_CMAX]
+    B = g["X"].shape[0]
+    opt = api.BatchIlqrOptimizer(api.default_config(stc.N_STEPS), batch_capacity=B, cmax=stc.MAIN_CMAX)
+    opt.set_option(api.OPT_EXACT_LANE_TIES, 1)
+    opt.stage_load(g["scene"])
+    opt.stage_set_trajectory(g["X"], g["U"])
+    opt.stage_quadratize()
+    q = {k: opt.read(t) for k, t in dict(A=api.T_A, B=api.T_B, lx=api.T_LX, lu=api.T_LU, lxx=api.T_LXX, luu=api.T_LUU).items()}
+    lam = np.array([rc.TABLE_LAMBDAS[b % len(rc.TABLE_LAMBDAS)] for b in range(B)])
+    opt.stage_backward(lam)
+    Kfb, kff, dV = opt.read(api.T_KFB), opt.read(api.T_KFF), opt.read(api.T_DV)
+    opt.close()
+    sK, sk, s_eager = rr.backward(lam, q, eager=True)
+    differs = sum(int(rc.backward_distance([dV[b]], [s_eager[b]])[0] > 1e-6) for b in range(B))
+    print(f"product library on the table: delta_V differs from the eager statement on {differs} of {B} problems")
+    assert differs >= 1
+    assert max(rc.backward_distance((Kfb[b], kff[b]), (sK[b], sk[b])).max() for b in range(B)) < 1e-9
 
 
 def test_dot_order_switch():

@@ -197,7 +197,9 @@ def test_backward_and_forward_from_the_crafted_quadratisation():
     """cilqr_stage_backward with a lambda per problem on the crafted quadratisation (relaxed terms of 1e4 beside entries of 1):
     the one-lane, team and wave kernels agree bit for bit and with the oracle's Backward fed the device's own q; then
     cilqr_stage_forward at the largest, a middle and the smallest step of the line search against the oracle's Forward, with
-    test_stage_parity's rule (tight where the oracle's rollout stays physical)."""
+    test_stage_parity's rule (tight where the oracle's rollout stays physical).
+    (lambda 0 .. 1e11, every configuration, the horizons 1 .. 5 and 64 .. 130, all eleven step sizes and the long-double
+    statement of these stages: tests/test_gpu_riccati.py.)"""
     g = sc.evaluate("default", True, 1)[sc.MAIN_CMAX]
     B = g["X"].shape[0]
     opt = _handle("default", sc.MAIN_CMAX, B, True)
