@@ -82,6 +82,13 @@ class WarmStart(C.Structure):
     _fields_ = [("memory", C.c_int32), ("layout", C.c_int32), ("rows", C.c_void_p), ("shift", C.c_void_p)]
 
 
+class Carry(C.Structure):
+    """cilqr_carry (include/cilqr.h): the previous cycle's rows and the time driven since, for cilqr_plan_scenes_batch_carry."""
+    _fields_ = [("memory", C.c_int32), ("layout", C.c_int32), ("n_rows", C.c_int32), ("reserved0", C.c_int32),
+                ("rows", C.c_void_p), ("advance", C.c_void_p), ("max_advance", C.c_double),
+                ("max_start_offset", C.c_double), ("collision_buffer", C.c_double)]
+
+
 class CorridorConfig(C.Structure):
     """CorridorConfig of the reference (algorithm/params/planner_config.h:75-86)."""
     _fields_ = [("max_diff_x", C.c_double), ("max_diff_y", C.c_double), ("radius", C.c_double),
@@ -130,6 +137,9 @@ HIT_FRONT_STATIC, HIT_FRONT_BARRIER, HIT_FRONT_DYNAMIC = 8, 16, 32
 HIT_BITS = (HIT_REAR_STATIC, HIT_REAR_BARRIER, HIT_REAR_DYNAMIC, HIT_FRONT_STATIC, HIT_FRONT_BARRIER, HIT_FRONT_DYNAMIC)
 # cilqr_resample_rows / cilqr_resample_rows_batch: the key column of a query (CILQR_KEY_*)
 KEY_TIME, KEY_STATION = 0, 1
+# cilqr_carry_rows / cilqr_carry_rows_batch: the state of a trajectory, and what cilqr_plan_scenes_batch_carry adds to it
+# in `source` (CILQR_CARRY_*)
+CARRY_KEPT, CARRY_NOT_ASKED, CARRY_REFUSED, CARRY_OFF_START, CARRY_HIT = 0, 1, 2, 3, 4
 # cilqr_frenet_rows / cilqr_frenet_rows_batch: plain [K][2] x, y rows (CILQR_ROWS_POINTS; these two calls only), the doubles
 # of a centre-line row and of a result row (CILQR_FRENET_FIELDS), doubles per row of every layout they accept
 ROWS_POINTS = 4
@@ -183,6 +193,7 @@ EXPORTS = [
     "cilqr_constraint_margins", "cilqr_constraint_margins_batch",
     "cilqr_track_rows", "cilqr_track_rows_batch",
     "cilqr_window_scene", "cilqr_window_scenes_batch", "cilqr_plan_scenes_batch_warm",
+    "cilqr_carry_rows", "cilqr_carry_rows_batch", "cilqr_plan_scenes_batch_carry",
     "cilqr_road_barriers", "cilqr_default_tracker_config",
     "cilqr_set_tracker_config",
     "cilqr_solve_batch_warm", "cilqr_submit_warm", "cilqr_stage_load_warm", "cilqr_pool_submit_warm", "cilqr_multi_solve_warm",
@@ -266,6 +277,16 @@ def lib():
                                                    C.POINTER(SceneBatchStruct), C.c_void_p, C.c_int32, C.POINTER(WarmStart),
                                                    C.POINTER(SolutionBatch), C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.cilqr_plan_scenes_batch_carry.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(CorridorConfig),
+                                                    C.POINTER(SceneBatchStruct), C.c_void_p, C.c_int32, C.POINTER(Carry),
+                                                    C.POINTER(WarmStart), C.POINTER(SolutionBatch), C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                    C.POINTER(C.c_int32)]
+        L.cilqr_carry_rows.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+        L.cilqr_carry_rows_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double,
+                                             C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
         L.cilqr_window_scene.argtypes = [C.POINTER(SceneStruct), C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_int32)]
         L.cilqr_window_scenes_batch.argtypes = [C.c_void_p, C.POINTER(SceneBatchStruct), C.c_void_p, C.c_double, C.c_int32,
@@ -386,6 +407,29 @@ def make_warm(warm, n_steps: int | None = None):
 
 def _warm_ref(w):
     return C.byref(w) if w is not None else None
+
+
+def make_carry(carry):
+    """carry: None, a Carry, or a dict(rows [B,R,F], advance [B], layout=ROWS_PLAN, max_advance, max_start_offset,
+    collision_buffer=0.0) -- rows / advance NumPy arrays (host memory) or contiguous float64 device tensors, both of the
+    same kind, the kind the scenes' arrays are.  Returns (Carry or None, what must stay alive until the call returns)."""
+    if carry is None or isinstance(carry, Carry):
+        return carry, None
+    rows, advance, layout = carry["rows"], carry["advance"], int(carry.get("layout", ROWS_PLAN))
+    limits = (float(carry["max_advance"]), float(carry["max_start_offset"]), float(carry.get("collision_buffer", 0.0)))
+    if _is_device_tensor(rows) != _is_device_tensor(advance):
+        raise ValueError("carry rows and advance must both be NumPy arrays or both device tensors")
+    if _is_device_tensor(rows):
+        for t in (rows, advance):
+            if not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64":
+                raise ValueError("carry rows / advance on the device: contiguous float64 tensors")
+        memory, ptrs = MEM_DEVICE, (rows.data_ptr(), advance.data_ptr())
+    else:
+        rows, advance = _f64(rows), _f64(advance)
+        memory, ptrs = MEM_HOST, (rows.ctypes.data, advance.ctypes.data)
+    if rows.ndim != 3 or rows.shape[2] != ROWS_FIELDS.get(layout, rows.shape[2]) or tuple(advance.shape) != (rows.shape[0],):
+        raise ValueError(f"carry rows must be [B, R, {ROWS_FIELDS.get(layout)}] and advance [B]")
+    return Carry(memory, layout, int(rows.shape[1]), 0, ptrs[0], ptrs[1], *limits), (rows, advance)
 
 
 class BatchIlqrOptimizer:
@@ -768,13 +812,16 @@ class BatchIlqrOptimizer:
                                                max_points, points_ptr, count_ptr, ok_ptr)
 
     def plan_scenes(self, packed: dict, start, dp_cfg: "DpConfig | None" = None, corridor_cfg: "CorridorConfig | None" = None,
-                    alpha_trace: bool = False, warm=None):
+                    alpha_trace: bool = False, warm=None, carry=None):
         """TrajectoryPlanner::Plan for a batch of scenes on the GPU (cilqr_plan_scenes_batch), host arrays: DP -> obstacle
         points -> corridors (the handle's cmax) -> lane constraints -> solve -> result rows.  `packed` =
         scene_io.pack_scene_batch(center, scenes), start [B,4] = x, y, theta, v.  Returns the dict of plan() plus plan
         [B,K,11] = time s x y theta kappa velocity a delta jerk delta_rate, dp [B,K,9], outcome [B] int32 (PLAN_OK /
         PLAN_DP_FAILED / PLAN_CORRIDOR_FAILED), n_dp_failed, n_corridor_failed.  warm = (rows, shift, layout) as make_warm
-        takes it, NumPy arrays: the solve starts from those controls (cilqr_plan_scenes_batch_warm); None: the plain call."""
+        takes it, NumPy arrays: the solve starts from those controls (cilqr_plan_scenes_batch_warm); None: the plain call.
+        carry = a dict as make_carry takes it, NumPy arrays: the previous cycle's rows are carried forward and the DP planner
+        runs only where they do not hold (cilqr_plan_scenes_batch_carry); the result then has source [B] int32 (CARRY_*)
+        and n_kept as well.  None: today's calls."""
         dp_cfg = dp_cfg or default_dp_config(tf=self.N * self.cfg.dt, delta_t=self.cfg.dt)
         corridor_cfg = corridor_cfg or default_corridor_config()
         B, K, M = int(packed["batch"]), self.K, self.cfg.max_iter
@@ -789,22 +836,39 @@ class BatchIlqrOptimizer:
         sol = SolutionBatch(MEM_HOST, 0, _ptr(traj), _ptr(hist), _ptr(n_cost), _ptr(status), _ptr(n_iter), None, None, _ptr(at))
         plan, dp, outcome = np.zeros((B, K, PLAN_FIELDS)), np.zeros((B, K, COARSE_FIELDS)), np.zeros(B, np.int32)
         w, keep_warm = make_warm(warm, self.N)
-        rc, n_dp, n_cor = self.plan_scenes_raw(dp_cfg, corridor_cfg, sb, _ptr(start), K, sol, _ptr(plan), _ptr(dp), _ptr(outcome),
-                                               warm=w)
-        del keep_warm
+        cy, keep_carry = make_carry(carry)
+        if cy is None:
+            rc, n_dp, n_cor = self.plan_scenes_raw(dp_cfg, corridor_cfg, sb, _ptr(start), K, sol, _ptr(plan), _ptr(dp),
+                                                   _ptr(outcome), warm=w)
+            more = {}
+        else:
+            source = np.zeros(B, np.int32)
+            rc, n_dp, n_cor, n_kept = self.plan_scenes_raw(dp_cfg, corridor_cfg, sb, _ptr(start), K, sol, _ptr(plan), _ptr(dp),
+                                                           _ptr(outcome), warm=w, carry=cy, source_ptr=_ptr(source))
+            more = dict(source=source, n_kept=n_kept)
+        del keep_warm, keep_carry
         self._chk(rc, "plan_scenes")
         self.B = B
         return dict(rc=rc, traj=traj, cost_hist=hist, n_cost=n_cost, status=status, n_iter=n_iter, alpha_trace=at, plan=plan,
-                    dp=dp, outcome=outcome, n_dp_failed=n_dp, n_corridor_failed=n_cor)
+                    dp=dp, outcome=outcome, n_dp_failed=n_dp, n_corridor_failed=n_cor, **more)
 
     def plan_scenes_raw(self, dp_cfg, corridor_cfg, scene_batch, start_ptr, n_knots, sol: SolutionBatch, plan_ptr=None,
-                        coarse9_ptr=None, outcome_ptr=None, warm: "WarmStart | None" = None):
+                        coarse9_ptr=None, outcome_ptr=None, warm: "WarmStart | None" = None, carry: "Carry | None" = None,
+                        source_ptr=None):
         """Pointer-level form (start / plan / coarse9 / outcome in device or host memory as scene_batch.memory says, the
         solver's outputs as sol.memory says); warm: a WarmStart in the memory of the scenes (cilqr_plan_scenes_batch_warm),
-        None: the plain call.  Returns (rc, n_dp_failed, n_corridor_failed)."""
+        None: the plain call.  Returns (rc, n_dp_failed, n_corridor_failed).  carry: a Carry in the memory of the scenes
+        (cilqr_plan_scenes_batch_carry, with source_ptr [B] int32 there too, optional); then (rc, n_dp_failed,
+        n_corridor_failed, n_kept) is returned.  None: the calls above."""
         n_dp, n_cor = C.c_int32(0), C.c_int32(0)
         dp_ref = C.byref(dp_cfg) if dp_cfg is not None else None
         cor_ref = C.byref(corridor_cfg) if corridor_cfg is not None else None
+        if carry is not None:
+            n_kept = C.c_int32(0)
+            rc = self.L.cilqr_plan_scenes_batch_carry(self.h, dp_ref, cor_ref, C.byref(scene_batch), start_ptr, n_knots,
+                                                      C.byref(carry), _warm_ref(warm), C.byref(sol), plan_ptr, coarse9_ptr,
+                                                      outcome_ptr, source_ptr, C.byref(n_dp), C.byref(n_cor), C.byref(n_kept))
+            return rc, int(n_dp.value), int(n_cor.value), int(n_kept.value)
         if warm is None:
             rc = self.L.cilqr_plan_scenes_batch(self.h, dp_ref, cor_ref, C.byref(scene_batch), start_ptr, n_knots,
                                                 C.byref(sol), plan_ptr, coarse9_ptr, outcome_ptr, C.byref(n_dp), C.byref(n_cor))
@@ -984,6 +1048,56 @@ class BatchIlqrOptimizer:
         check_collisions_raw where they lie); returns the code."""
         return self.L.cilqr_resample_rows_batch(self.h, batch, layout, rows_ptr, n_knots, key, queries_ptr, n_queries,
                                                 int(per_problem), out_ptr, memory)
+
+    def carry(self, rows, layout: int, advance, max_advance: float, n_knots: "int | None" = None, delta_t: "float | None" = None):
+        """The trajectories of the previous cycle as coarse trajectories of the next, on the GPU (cilqr_carry_rows_batch):
+        rows [B,R,F] in `layout` (ROWS_TRAJ / ROWS_PLAN / ROWS_COARSE), advance [B] seconds driven since each one's time[0]
+        (negative: not asked), n_knots (None: the handle's) knots delta_t (None: the handle's dt) apart.  NumPy arrays, or
+        contiguous float64 device tensors (both of the same kind).  Returns dict(coarse9 [B,n_knots,9], coarse6 [B,n_knots,6],
+        knots3 [B,n_knots,3], station [B,n_knots], state [B] int32 (CARRY_KEPT / CARRY_NOT_ASKED / CARRY_REFUSED)) of that
+        kind, and n_kept."""
+        on_device = _is_device_tensor(rows)
+        if on_device != _is_device_tensor(advance):
+            raise ValueError("rows and advance must both be NumPy arrays or both device tensors")
+        if on_device:
+            for t in (rows, advance):
+                if not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64":
+                    raise ValueError("rows / advance on the device: contiguous float64 tensors")
+        else:
+            rows, advance = _f64(rows), _f64(advance)
+        if rows.ndim != 3 or rows.shape[2] != ROWS_FIELDS.get(layout, rows.shape[2]):
+            raise ValueError(f"rows must be [B, R, {ROWS_FIELDS.get(layout)}]")
+        B, R = int(rows.shape[0]), int(rows.shape[1])
+        if tuple(advance.shape) != (B,):
+            raise ValueError(f"advance must be [{B}]")
+        K = self.K if n_knots is None else int(n_knots)
+        dt = self.cfg.dt if delta_t is None else float(delta_t)
+        shapes = dict(coarse9=(B, max(K, 0), COARSE_FIELDS), coarse6=(B, max(K, 0), 6), knots3=(B, max(K, 0), 3), station=(B, max(K, 0)))
+        if on_device:
+            import torch
+            out = {k: torch.empty(v, dtype=torch.float64, device=rows.device) for k, v in shapes.items()}
+            out["state"] = torch.empty((B,), dtype=torch.int32, device=rows.device)
+            ptr = lambda t: t.data_ptr()
+        else:
+            out = {k: np.empty(v) for k, v in shapes.items()}
+            out["state"] = np.empty(B, np.int32)
+            ptr = lambda a: a.ctypes.data
+        rc, n_kept = self.carry_raw(B, layout, ptr(rows), R, ptr(advance), max_advance, K, dt, ptr(out["coarse9"]),
+                                    ptr(out["coarse6"]), ptr(out["knots3"]), ptr(out["station"]), ptr(out["state"]),
+                                    MEM_DEVICE if on_device else MEM_HOST)
+        self._chk(rc, "carry")
+        out["n_kept"] = n_kept
+        return out
+
+    def carry_raw(self, batch, layout, rows_ptr, n_rows, advance_ptr, max_advance, n_knots, delta_t, coarse9_ptr, coarse6_ptr,
+                  knots3_ptr, station_ptr, state_ptr, memory):
+        """Pointer-level form (every array in device or host memory as `memory` says; the four outputs are optional: the
+        carried coarse9 feeds check_collisions_raw where it lies); returns (code, number of kept trajectories)."""
+        n = C.c_int32(0)
+        rc = self.L.cilqr_carry_rows_batch(self.h, batch, layout, rows_ptr, n_rows, advance_ptr, C.c_double(max_advance),
+                                           n_knots, C.c_double(delta_t), coarse9_ptr, coarse6_ptr, knots3_ptr, station_ptr,
+                                           state_ptr, C.byref(n), memory)
+        return rc, int(n.value)
 
     def track(self, rows, layout: int, start6=None, n_drive: int | None = None):
         """Drive a vehicle along every trajectory of a batch with the closed-loop Tracker, on the GPU
@@ -1256,6 +1370,24 @@ def resample_rows(rows, layout: int, queries, key: int = KEY_TIME) -> np.ndarray
                                    out.ctypes.data)
     if rc != OK:
         raise CilqrError(rc, "in cilqr_resample_rows")
+    return out
+
+
+def carry_rows(rows, layout: int, advance: float, max_advance: float, n_knots: int, delta_t: float) -> dict:
+    """The carry rule for one trajectory through the C-ABI (cilqr_carry_rows, host, no GPU): rows [R,F] in `layout`, the
+    time driven since its time[0] -> dict(state, coarse9 [n_knots,9], coarse6 [n_knots,6], knots3 [n_knots,3],
+    station [n_knots])."""
+    rows = _f64(rows)
+    K = max(int(n_knots), 0)
+    out = dict(coarse9=np.empty((K, COARSE_FIELDS)), coarse6=np.empty((K, 6)), knots3=np.empty((K, 3)), station=np.empty(K))
+    state = C.c_int32(-1)
+    rc = lib().cilqr_carry_rows(layout, rows.ctypes.data, rows.shape[0] if rows.ndim == 2 else 0, C.c_double(advance),
+                                C.c_double(max_advance), int(n_knots), C.c_double(delta_t), out["coarse9"].ctypes.data,
+                                out["coarse6"].ctypes.data, out["knots3"].ctypes.data, out["station"].ctypes.data,
+                                C.byref(state))
+    if rc != OK:
+        raise CilqrError(rc, "in cilqr_carry_rows")
+    out["state"] = int(state.value)
     return out
 
 

@@ -20,6 +20,22 @@ extern "C" int cilqr_dp_plan_batch(cilqr_handle h, const cilqr_dp_config* cfg, c
                                   nullptr);
 }
 
+int cilqr_dp_path_samples(const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes, int32_t n_knots, int32_t* n_samples) {
+  if (!(cfg->delta_t > 0.0) || !(cfg->tf > 0.0)) return CILQR_ERR_ARG;
+  if ((int32_t)(cfg->tf / cfg->delta_t + 1) != n_knots) return CILQR_ERR_KNOTS;
+  const cilqr::DpConfig d = cilqr::dp_config_of(*cfg);
+  const cilqr::DpEnvironment env(d, cilqr::reference_line_of(scenes->center, scenes->n_center));
+  const cilqr::DpPlanner dp(d, &env);
+  int nq = 0;
+  for (int t = 0; t < cilqr::kDpNT; ++t) {
+    if (dp.segment_points(t) < 1) return CILQR_ERR_KNOTS;
+    nq += dp.segment_points(t);
+  }
+  if (nq > CILQR_DP_MAX_KNOTS) return CILQR_ERR_CAPACITY;
+  *n_samples = nq;
+  return CILQR_OK;
+}
+
 int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes, const double* start3,
                              int32_t n_knots, double* coarse9, double* coarse6, double* knots3, double* station,
                              int32_t* found, int32_t* n_not_found, double* times_out) {

@@ -1,12 +1,13 @@
 // cilqr_scene_points_batch and cilqr_plan_scenes_batch / _warm (include/cilqr.h): the host side -- argument checks, the handle's
 // work space, staging of HOST arrays, the launches of kernels_scene_points.hip and, for the pipeline, the calls of the
 // stages it chains (cilqr_dp_plan_batch, cilqr_build_corridors, cilqr_solve_batch_warm: the public entry points on device
-// views, so that what they compute is what a caller of the four calls gets).
+// views, so that what they compute is what a caller of the four calls gets).  The pipeline's body is shared with
+// carry_pipeline.hip (scene_pipeline.hpp), which puts another coarse stage in the DP planner's place.
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
-#include "scene_batch.hpp"
+#include "scene_pipeline.hpp"
 #include "scene_points.hpp"
 
 using namespace cilqr;
@@ -88,13 +89,12 @@ extern "C" int cilqr_scene_points_batch(cilqr_handle h, const cilqr_scene_batch*
   return CILQR_OK;
 }
 
-namespace {
-
-// the body of both pipeline entry points; `warm` NULL: the plain call (cilqr_solve_batch_warm with NULL is cilqr_solve_batch)
-int plan_scenes(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilqr_corridor_config* corridor_cfg,
-                const cilqr_scene_batch* scenes, const double* start4, int32_t n_knots, const cilqr_warm_start* warm,
-                cilqr_solution_batch* out, double* plan, double* coarse9, int32_t* outcome, int32_t* n_dp_failed,
-                int32_t* n_corridor_failed) {
+// the body of the pipeline entry points; `warm` NULL: the plain call (cilqr_solve_batch_warm with NULL is cilqr_solve_batch);
+// `coarse` NULL: the DP planner on the whole batch
+int cilqr::plan_scenes(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilqr_corridor_config* corridor_cfg,
+                       const cilqr_scene_batch* scenes, const double* start4, int32_t n_knots, const cilqr_warm_start* warm,
+                       CoarseStage* coarse, cilqr_solution_batch* out, double* plan, double* coarse9, int32_t* outcome,
+                       int32_t* n_dp_failed, int32_t* n_corridor_failed) {
   if (h == nullptr || dp_cfg == nullptr || corridor_cfg == nullptr || scenes == nullptr || start4 == nullptr ||
       out == nullptr || scenes->center == nullptr)
     return CILQR_ERR_NULL;
@@ -118,6 +118,8 @@ int plan_scenes(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilqr_corri
   const int per_vertex = corridor_cfg->is_multiple_sample ? 6 : 1;
   const int max_points = worst_case_points(sb, per_vertex);
   if (max_points + (corridor_cfg->is_multiple_sample ? 24 : 8) > kCorMaxPts) return CILQR_ERR_CAPACITY;
+  if (coarse != nullptr)
+    if (int rc = coarse->check(*dp_cfg, sb, n_knots)) return rc;
   if (solves_in_flight(h)) return CILQR_ERR_STATE;
   const bool on_host = sb.memory == CILQR_MEM_HOST;
   if (on_host && !host_counts_valid(sb)) return CILQR_ERR_ARG;
@@ -186,12 +188,17 @@ int plan_scenes(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilqr_corri
   }
   HIP_TRY(hipMemsetAsync(d_counts, 0, s_counts.bytes, st));
 
-  // ---- DpPlanner::Plan (trajectory_planner.cpp:32)
-  launch_plan_start3((int)B, d_s4, d_s3, st);
-  HIP_TRY(hipGetLastError());
+  // ---- DpPlanner::Plan (trajectory_planner.cpp:32), or the caller's coarse stage in its place
   std::vector<double> times(K);
-  if (int rc = cilqr_dp_plan_batch_impl(h, dp_cfg, &dv, d_s3, n_knots, d_c9, d_c6, d_k3, d_stn, d_found, nullptr, times.data()))
-    return rc;
+  if (coarse == nullptr) {
+    launch_plan_start3((int)B, d_s4, d_s3, st);
+    HIP_TRY(hipGetLastError());
+    if (int rc = cilqr_dp_plan_batch_impl(h, dp_cfg, &dv, d_s3, n_knots, d_c9, d_c6, d_k3, d_stn, d_found, nullptr, times.data()))
+      return rc;
+  } else {
+    const CoarseArgs a{h, dp_cfg, &sb, &dv, n_knots, d_s4, d_s3, d_c9, d_c6, d_k3, d_stn, d_found, times.data()};
+    if (int rc = coarse->run(a)) return rc;
+  }
 
   // ---- Corridor::BuildCorridorConstraints (corridor.cc:58-87) with the Environment's points, a chunk of scenes at a time
   if (int rc = upload_times(h, times.data(), n_knots, st)) return rc;
@@ -242,14 +249,12 @@ int plan_scenes(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilqr_corri
   return CILQR_OK;
 }
 
-}  // namespace
-
 extern "C" int cilqr_plan_scenes_batch(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilqr_corridor_config* corridor_cfg,
                                        const cilqr_scene_batch* scenes, const double* start4, int32_t n_knots,
                                        cilqr_solution_batch* out, double* plan, double* coarse9, int32_t* outcome,
                                        int32_t* n_dp_failed, int32_t* n_corridor_failed) {
-  return plan_scenes(h, dp_cfg, corridor_cfg, scenes, start4, n_knots, nullptr, out, plan, coarse9, outcome, n_dp_failed,
-                     n_corridor_failed);
+  return plan_scenes(h, dp_cfg, corridor_cfg, scenes, start4, n_knots, nullptr, nullptr, out, plan, coarse9, outcome,
+                     n_dp_failed, n_corridor_failed);
 }
 
 extern "C" int cilqr_plan_scenes_batch_warm(cilqr_handle h, const cilqr_dp_config* dp_cfg,
@@ -257,6 +262,6 @@ extern "C" int cilqr_plan_scenes_batch_warm(cilqr_handle h, const cilqr_dp_confi
                                             const double* start4, int32_t n_knots, const cilqr_warm_start* warm,
                                             cilqr_solution_batch* out, double* plan, double* coarse9, int32_t* outcome,
                                             int32_t* n_dp_failed, int32_t* n_corridor_failed) {
-  return plan_scenes(h, dp_cfg, corridor_cfg, scenes, start4, n_knots, warm, out, plan, coarse9, outcome, n_dp_failed,
-                     n_corridor_failed);
+  return plan_scenes(h, dp_cfg, corridor_cfg, scenes, start4, n_knots, warm, nullptr, out, plan, coarse9, outcome,
+                     n_dp_failed, n_corridor_failed);
 }

@@ -279,6 +279,12 @@ struct cilqr_solver {
   // staging of HOST source trajectories, counts and t0, of HOST windows, counts and flags
   cilqr::pinned_mem sw_tab_host;
   cilqr::dev_mem sw_tab, sw_in, sw_out;
+  // cilqr_carry_rows_batch (carry_batch.hip), grown likewise: the count of kept trajectories and its way back, the staging
+  // of HOST rows and advances, of HOST coarse trajectories and states; cilqr_plan_scenes_batch_carry (carry_pipeline.hip):
+  // the intermediates of its coarse stage (states, hits, the list, the gathered scenes and their plans), the list's length
+  // on its way back
+  cilqr::pinned_mem cy_tab_host, cy_sel_host;
+  cilqr::dev_mem cy_tab, cy_in, cy_out, cy_work, cy_chunk;
 };
 
 namespace cilqr {
@@ -297,3 +303,6 @@ bool cilqr_warm_geometry(int32_t layout, int32_t n_knots, int* stride, int* rows
 int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes, const double* start3,
                              int32_t n_knots, double* coarse9, double* coarse6, double* knots3, double* station,
                              int32_t* found, int32_t* n_not_found, double* times_out);
+// the path samples of the five layers together: how many of a trajectory's n_knots rows k_dp_plan fills (the others stay
+// zero); the checks on cfg are those of the call above (CILQR_ERR_ARG, CILQR_ERR_KNOTS, CILQR_ERR_CAPACITY)
+int cilqr_dp_path_samples(const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes, int32_t n_knots, int32_t* n_samples);

@@ -14,7 +14,7 @@ from . import api
 
 def run_episode(opt: "api.BatchIlqrOptimizer", packed: dict, start4, n_cycles: int, n_drive: int = 6,
                 out_samples: "int | None" = None, dp_cfg: "api.DpConfig | None" = None,
-                corridor_cfg: "api.CorridorConfig | None" = None) -> dict:
+                corridor_cfg: "api.CorridorConfig | None" = None, carry: "dict | None" = None) -> dict:
     """n_cycles planning cycles on the scenes of `packed` (scene_io.pack_scene_batch; recordings of any length, absolute
     times), all scenes starting at scene time 0 in start4 [B,4] = x y theta v.  Per cycle:
 
@@ -26,6 +26,13 @@ def run_episode(opt: "api.BatchIlqrOptimizer", packed: dict, start4, n_cycles: i
                start = the previous cycle's last driven row (first cycle: start4 with a = delta = 0);
       advance  the next start4 is x y theta v of the last driven row (the solver's knot 0 keeps a = delta = 0, as the
                warm-start contract says), and t0 advances by that row's time minus row 0's time.
+
+    carry = dict(max_advance, max_start_offset, collision_buffer, refresh_every): from the second cycle on the plan step is
+    opt.plan_scenes(..., carry=...) -- the previous cycle's `plan` rows (ROWS_PLAN) with the time driven since as `advance`,
+    so the DP planner runs only where those rows do not hold (cilqr_plan_scenes_batch_carry).  advance is -1 (plan with the
+    DP planner) where the previous outcome was not PLAN_OK or the scene is not alive, and for every scene in every
+    refresh_every-th cycle (0 or absent: never).  Each such cycle's dict gains source [B] and n_kept; the first cycle has
+    source = CARRY_NOT_ASKED for all.  carry = None: the loop as above.
 
     A scene whose tracker failed (ok = 0) or whose window overflowed keeps its start and its t0, and its `alive` flag is 0
     for the rest of the episode.  It is still carried through the calls -- after an overflow with the counts of the
@@ -42,7 +49,8 @@ def run_episode(opt: "api.BatchIlqrOptimizer", packed: dict, start4, n_cycles: i
     start6 = np.concatenate([start, np.zeros((B, 2))], axis=1)
     t0, alive = np.zeros(B), np.ones(B, dtype=bool)
     prev, cycles = None, []
-    for _ in range(int(n_cycles)):
+    driven_time = np.zeros(B)
+    for cycle in range(int(n_cycles)):
         win = opt.window_scenes(packed, t0, float(dp_cfg.tf), out_samples)
         window_ok = win["window_ok"]
         if not window_ok.all():
@@ -51,13 +59,25 @@ def run_episode(opt: "api.BatchIlqrOptimizer", packed: dict, start4, n_cycles: i
         if prev is not None:
             shift = np.where(prev["outcome"] == api.PLAN_OK, n_drive - 1, -1).astype(np.int32)
             warm = (prev["traj"], shift, api.ROWS_TRAJ)
-        plan = opt.plan_scenes(win, start, dp_cfg, corridor_cfg, warm=warm)
+        if carry is None:
+            plan = opt.plan_scenes(win, start, dp_cfg, corridor_cfg, warm=warm)
+        elif prev is None:
+            plan = opt.plan_scenes(win, start, dp_cfg, corridor_cfg, warm=warm)
+            plan.update(source=np.full(B, api.CARRY_NOT_ASKED, np.int32), n_kept=0)
+        else:
+            refresh = int(carry.get("refresh_every", 0))
+            asked = (prev["outcome"] == api.PLAN_OK) & alive & (refresh <= 0 or cycle % refresh != 0)
+            plan = opt.plan_scenes(win, start, dp_cfg, corridor_cfg, warm=warm, carry=dict(
+                rows=prev["plan"], layout=api.ROWS_PLAN, advance=np.where(asked, driven_time, -1.0),
+                max_advance=carry["max_advance"], max_start_offset=carry["max_start_offset"],
+                collision_buffer=carry.get("collision_buffer", 0.0)))
         driven, track_ok = opt.track(plan["traj"], api.ROWS_TRAJ, start6, n_drive)
         alive = alive & window_ok & (track_ok != 0)
         cycles.append(dict(plan, driven=driven, track_ok=track_ok, window_ok=window_ok, t0=t0.copy(), alive=alive.copy()))
         last = driven[:, n_drive - 1]
         start6 = np.where(alive[:, None], last[:, 1:7], start6)
         start = np.ascontiguousarray(start6[:, :4])
-        t0 = np.where(alive, t0 + (last[:, 0] - driven[:, 0, 0]), t0)
+        driven_time = last[:, 0] - driven[:, 0, 0]
+        t0 = np.where(alive, t0 + driven_time, t0)
         prev = plan
     return dict(cycles=cycles, t0=t0, start4=start, alive=alive)

@@ -1062,6 +1062,93 @@ int cilqr_window_scenes_batch(cilqr_handle h, const cilqr_scene_batch* scenes, c
                               int32_t* counts /* [B][max_dynamic] */, int32_t* ok /* [B], optional */,
                               int32_t* n_overflow /* HOST, optional */);
 
+/* ---- carry: the plan of the previous cycle as the coarse trajectory of the next (additive, ABI 7) ----
+ * A later planning cycle need not search the lattice again: the plan of cycle n, read from the time the vehicle has reached,
+ * is a coarse trajectory for cycle n + 1 as long as it still clears the obstacles on the new clock.  The carry rule makes that
+ * coarse trajectory -- DiscretizedTrajectory::EvaluateTime at the knot times of the new cycle -- in the four forms
+ * cilqr_dp_plan_batch returns.  For ONE trajectory of n_rows >= 2 rows in CILQR_ROWS_TRAJ / _PLAN / _COARSE, an `advance` in
+ * seconds (the time driven since the rows' time[0]), max_advance, n_knots >= 1 and delta_t > 0; every operation is rounded
+ * once (no fused multiply-add):
+ *   state 1 (CILQR_CARRY_NOT_ASKED)   advance < 0.  Every output row is zero.
+ *   state 2 (CILQR_CARRY_REFUSED)     advance is a NaN or above max_advance; or !(time[n_rows-1] - time[0] > 0) -- the all-zero
+ *                                     rows a failed tracker leaves, NaN times --; or any coarse6 column of any row produced
+ *                                     below is not finite.  Every output row is zero.
+ *   state 0 (CILQR_CARRY_KEPT)        otherwise.  q_k = (time[0] + advance) + k * delta_t;  r_k = the resample rule above with
+ *                                     CILQR_KEY_TIME at q_k (its extrapolation past the last row, its degenerate pair and its
+ *                                     slerp included);  coarse9 row k = delta_t * k, s_k, r.x, r.y, r.theta, r.kappa,
+ *                                     r.velocity, r.a, r.delta with s_0 = 0, s_k = s_{k-1} + hypot(x_k - x_{k-1}, y_k - y_{k-1})
+ *                                     summed in knot order (the hypot of the `plan` rows of cilqr_plan_scenes_batch);
+ *                                     coarse6, knots3 and station are the projections cilqr_dp_plan_batch writes.
+ *   columns read   CILQR_ROWS_TRAJ x 1 y 2 theta 3 v 4 a 5 delta 6 kappa 7;  CILQR_ROWS_PLAN and _COARSE x 2 y 3 theta 4
+ *                  kappa 5 v 6 a 7 delta 8.
+ * cilqr_carry_rows: one trajectory on the host, no handle (C++ callers use include/cilqr/trajectory_queries.hpp: carry_rows).
+ *   coarse9 [n_knots][CILQR_COARSE_FIELDS], coarse6 [n_knots][6], knots3 [n_knots][3], station [n_knots]: each optional
+ * CILQR_ERR_NULL (rows, state); CILQR_ERR_ARG for an unknown layout, n_rows < 2, n_knots < 1, a delta_t that is not positive,
+ * a max_advance that is negative or not finite; CILQR_ERR_CAPACITY for n_rows or n_knots > CILQR_DP_MAX_KNOTS. */
+#define CILQR_CARRY_KEPT 0
+#define CILQR_CARRY_NOT_ASKED 1
+#define CILQR_CARRY_REFUSED 2
+#define CILQR_CARRY_OFF_START 3   /* cilqr_plan_scenes_batch_carry only, like the next */
+#define CILQR_CARRY_HIT 4
+int cilqr_carry_rows(int32_t layout, const double* rows, int32_t n_rows, double advance, double max_advance,
+                     int32_t n_knots, double delta_t, double* coarse9, double* coarse6, double* knots3, double* station,
+                     int32_t* state);
+/* ---- the same for B trajectories per call, each with its own advance, on the GPU (kernels_carry.hip) ----
+ *   rows [B][n_rows][fields], advance [B], coarse9 / coarse6 / knots3 / station [B][n_knots][9 | 6 | 3 | 1] (each optional),
+ *   state [B]: all in `memory`; *n_kept (HOST, optional): the trajectories with state 0
+ * A workgroup takes a run of whole trajectories: their rows are staged in LDS once, the (trajectory, knot) pairs are spread
+ * over the lanes, which bracket and interpolate there, the test for a non-finite value is one ballot per wavefront, the
+ * running station one lane's sum per trajectory over chord lengths in LDS, and the four outputs leave as consecutive
+ * doubles.  Every element is the host call's bit for bit (the kernel is built without
+ * contraction, wraps angles with the routine of cilqr_device_math fn 6 and takes the hypot of fn 9); a trajectory's bits do
+ * not depend on the batch around it; nothing beyond the alignment of a double is assumed.  Runs on the handle's stream and
+ * waits for that stream only; DEVICE arrays need no work space beyond the count, HOST arrays are staged in blocks that belong
+ * to the handle and grow to the largest call.  Checked before anything is launched, the handle staying usable:
+ * CILQR_ERR_NULL (handle, rows, advance, state); CILQR_ERR_ARG for batch < 1, an unknown memory flag and what the host call
+ * refuses; CILQR_ERR_CAPACITY as there; CILQR_ERR_STATE while solves are submitted on the handle. */
+int cilqr_carry_rows_batch(cilqr_handle h, int32_t batch, int32_t layout, const double* rows, int32_t n_rows,
+                           const double* advance, double max_advance, int32_t n_knots, double delta_t, double* coarse9,
+                           double* coarse6, double* knots3, double* station, int32_t* state, int32_t* n_kept,
+                           int32_t memory);
+
+/* ---- the pipeline of a later cycle: carried plans where they hold, the DP planner where they do not ----
+ * cilqr_plan_scenes_batch_warm with the DP planner run for exactly the scenes that need it.
+ *   1. carry    cilqr_carry_rows_batch on carry->rows / carry->advance with the planner's delta_t, for the path samples the
+ *               planner fills (all n_knots rows with the default configuration; rows past them are zero, as the planner
+ *               leaves them);
+ *   2. audit    cilqr_check_collisions_batch (CILQR_ROWS_COARSE, the carried coarse9, carry->collision_buffer);
+ *   3. select   source[b], first match wins: CILQR_CARRY_NOT_ASKED (state 1), CILQR_CARRY_REFUSED (state 2),
+ *               CILQR_CARRY_OFF_START  !(hypot(start.x - row0.x, start.y - row0.y) <= carry->max_start_offset),
+ *               CILQR_CARRY_HIT  first_hit[b] != -1 (the audit's -2 included), CILQR_CARRY_KEPT otherwise.  The scenes with
+ *               a non-zero source are listed in ascending order (ballots, population counts and a prefix over wavefronts
+ *               decide the positions, never an atomic);
+ *   4. plan     cilqr_dp_plan_batch for the listed scenes alone: nothing for an empty list; the batch as it lies when all
+ *               are listed; otherwise the listed scenes are gathered, CILQR_OPT_SCENE_CHUNK (or what fits a byte cap) at a
+ *               time, planned, and their rows and `found` written over the carried ones.  A kept scene has found = 1;
+ *   5. the rest as in cilqr_plan_scenes_batch_warm: obstacle points at the planner's time axis, corridors, outcome, the
+ *               solve (`warm` may be NULL and is independent of `carry`), the plan rows.  coarse9 returns the merged coarse
+ *               trajectories.
+ * The results are, bit for bit, those of the public calls made one after the other: cilqr_carry_rows_batch,
+ * cilqr_check_collisions_batch, the selection above, cilqr_dp_plan_batch on the listed scenes as a batch of their own with
+ * the same max_*, the merge, cilqr_scene_points_batch, cilqr_build_corridors, cilqr_solve_batch_warm.  With carry == NULL or
+ * every advance < 0 the call is cilqr_plan_scenes_batch_warm bit for bit.
+ *   source [B], optional (memory as scenes->memory); *n_kept (HOST, optional): the scenes with source 0
+ * Checked with the others, before anything is launched: CILQR_ERR_NULL for NULL rows or advance; CILQR_ERR_ARG for an unknown
+ * layout, a memory flag that differs from scenes->memory, n_rows < 2, a max_advance, max_start_offset or collision_buffer
+ * that is negative or not finite; CILQR_ERR_CAPACITY for n_rows > CILQR_DP_MAX_KNOTS. */
+typedef struct cilqr_carry {   /* the previous cycle's rows, for the B scenes in their order */
+  int32_t memory, layout;      /* memory must equal scenes->memory; CILQR_ROWS_TRAJ / _PLAN / _COARSE */
+  int32_t n_rows, reserved0;
+  const double* rows;          /* [B][n_rows][fields] */
+  const double* advance;       /* [B] seconds driven since those rows' time[0]; < 0: plan this scene with the DP planner */
+  double max_advance, max_start_offset, collision_buffer;
+} cilqr_carry;
+int cilqr_plan_scenes_batch_carry(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilqr_corridor_config* corridor_cfg,
+                                  const cilqr_scene_batch* scenes, const double* start4, int32_t n_knots,
+                                  const cilqr_carry* carry, const cilqr_warm_start* warm, cilqr_solution_batch* out,
+                                  double* plan, double* coarse9, int32_t* outcome, int32_t* source /* [B], optional */,
+                                  int32_t* n_dp_failed, int32_t* n_corridor_failed, int32_t* n_kept);
+
 /* ---- several GPUs from ONE host process (the reference's caller is one process:
  * algorithm/planning_node.cc:9-31) ----
  * A multi handle owns one solver handle per listed device.  cilqr_multi_solve cuts the batch into contiguous shards

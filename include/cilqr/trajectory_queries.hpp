@@ -2,7 +2,7 @@
 // (algorithm/utils/discretized_trajectory.cpp:50-136, math::slerp math_utils.h:208-225) on rows in the layouts of
 // include/cilqr.h: the host statement of cilqr_resample_rows, which cilqr_resample_rows_batch is held to bit for bit.
 // Further down, GetProjection / GetCartesian (cpp:138-196) on a centre line: the host statement of cilqr_frenet_rows and
-// cilqr_cartesian_points.
+// cilqr_cartesian_points.  Between the two, the carry rule on top of EvaluateTime: the host statement of cilqr_carry_rows.
 // Header-only, C++14, no HIP.  The rules are stated once, in include/cilqr.h ("resample", "frenet"); this file follows
 // them step by step.
 #ifndef CILQR_TRAJECTORY_QUERIES_HPP_
@@ -114,6 +114,57 @@ inline void resample_rows(int layout, const double* rows, int n_knots, int key, 
     interpolate(c, kc, rows + (size_t)(i - 1) * c.fields, rows + (size_t)i * c.fields, queries[m],
                 out + (size_t)m * c.fields);
   }
+}
+
+// ---- carry: a trajectory of the previous cycle as the coarse trajectory of the next: the host statement of cilqr_carry_rows
+// and cilqr_carry_rows_batch.  The rule is stated in include/cilqr.h ("carry").
+constexpr int kCoarseFields = 9;   // time s x y theta kappa velocity a delta
+// where a layout keeps x y theta kappa velocity a delta, in that order (the columns 2 ... 8 of a coarse row)
+inline const int* carry_columns(int layout) {
+  static const int traj[7] = {1, 2, 3, 7, 4, 5, 6}, plan[7] = {2, 3, 4, 5, 6, 7, 8};
+  return layout == 0 ? traj : plan;
+}
+
+// rows [n_rows][fields] -> coarse9 [n_knots][9], coarse6 [n_knots][6], knots3 [n_knots][3], station [n_knots] (each may be
+// null); returns the state (0 kept, 1 not asked, 2 refused).  The arguments are taken as checked (cilqr_carry_rows).
+inline int carry_rows(int layout, const double* rows, int n_rows, double advance, double max_advance, int n_knots,
+                      double delta_t, double* coarse9, double* coarse6, double* knots3, double* station) {
+  const Columns c = columns_of(layout);
+  const int* from = carry_columns(layout);
+  int state = 0;
+  if (advance < 0.0) state = 1;
+  else if (!(advance <= max_advance)) state = 2;                                          // a NaN, or above the limit
+  else if (!(rows[(size_t)(n_rows - 1) * c.fields + c.time] - rows[c.time] > 0.0)) state = 2;
+  double nine[256 * kCoarseFields];   // CILQR_DP_MAX_KNOTS rows
+  if (state == 0) {
+    const double first = rows[c.time] + advance;
+    double r[11], s = 0.0;
+    bool finite = true;
+    for (int k = 0; k < n_knots; ++k) {
+      const double q = first + k * delta_t;
+      const int i = bracket(rows, c.fields, c.time, n_rows, q);
+      interpolate(c, c.time, rows + (size_t)(i - 1) * c.fields, rows + (size_t)i * c.fields, q, r);
+      double* o = nine + (size_t)k * kCoarseFields;
+      o[0] = delta_t * k;
+      for (int e = 0; e < 7; ++e) std::memcpy(o + 2 + e, r + from[e], sizeof(double));
+      if (k > 0) s = s + std::hypot(o[2] - o[2 - kCoarseFields], o[3] - o[3 - kCoarseFields]);
+      o[1] = s;
+      finite = finite && std::isfinite(o[2]) && std::isfinite(o[3]) && std::isfinite(o[4]) && std::isfinite(o[6]) &&
+               std::isfinite(o[7]) && std::isfinite(o[8]);
+    }
+    if (!finite) state = 2;
+  }
+  if (state != 0) std::memset(nine, 0, sizeof(double) * (size_t)n_knots * kCoarseFields);
+  static const int six[6] = {2, 3, 4, 6, 7, 8};
+  for (int k = 0; k < n_knots; ++k) {
+    const double* o = nine + (size_t)k * kCoarseFields;
+    if (coarse9 != nullptr) std::memcpy(coarse9 + (size_t)k * kCoarseFields, o, sizeof(double) * kCoarseFields);
+    if (coarse6 != nullptr)
+      for (int e = 0; e < 6; ++e) std::memcpy(coarse6 + (size_t)k * 6 + e, o + six[e], sizeof(double));
+    if (knots3 != nullptr) std::memcpy(knots3 + (size_t)k * 3, o + 2, sizeof(double) * 3);
+    if (station != nullptr) station[k] = o[1];
+  }
+  return state;
 }
 
 // ---- the Frenet frame of a centre line (DiscretizedTrajectory::GetProjection / GetCartesian, cpp:138-196): the host
