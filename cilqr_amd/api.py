@@ -82,6 +82,12 @@ class WarmStart(C.Structure):
     _fields_ = [("memory", C.c_int32), ("layout", C.c_int32), ("rows", C.c_void_p), ("shift", C.c_void_p)]
 
 
+class SearchSeed(C.Structure):
+    """cilqr_search_seed: the test door of include/cilqr.h"""
+    _fields_ = [("memory", C.c_int32), ("batch", C.c_int32), ("cost_old", C.c_void_p), ("lambda_", C.c_void_p),
+                ("dlambda", C.c_void_p), ("iter", C.c_void_p)]
+
+
 class Carry(C.Structure):
     """cilqr_carry (include/cilqr.h): the previous cycle's rows and the time driven since, for cilqr_plan_scenes_batch_carry."""
     _fields_ = [("memory", C.c_int32), ("layout", C.c_int32), ("n_rows", C.c_int32), ("reserved0", C.c_int32),
@@ -184,7 +190,7 @@ EXPORTS = [
     "cilqr_set_option", "cilqr_get_option", "cilqr_set_profiling", "cilqr_get_profile", "cilqr_device_bytes", "cilqr_solve_batch",
     "cilqr_submit", "cilqr_wait", "cilqr_device_math", "cilqr_stage_load", "cilqr_stage_init_guess", "cilqr_stage_set_trajectory",
     "cilqr_stage_total_cost", "cilqr_stage_quadratize", "cilqr_stage_backward", "cilqr_stage_forward",
-    "cilqr_stage_read", "cilqr_stage_nearest_lane", "cilqr_open_loop_rollout", "cilqr_error_string",
+    "cilqr_stage_read", "cilqr_stage_nearest_lane", "cilqr_set_search_seed", "cilqr_open_loop_rollout", "cilqr_error_string",
     "cilqr_default_corridor_config", "cilqr_build_corridors", "cilqr_lane_constraints",
     "cilqr_default_dp_config", "cilqr_dp_plan", "cilqr_dp_plan_batch", "cilqr_scene_points_batch", "cilqr_plan_scenes_batch",
     "cilqr_check_collisions", "cilqr_check_collisions_batch", "cilqr_resample_rows", "cilqr_resample_rows_batch",
@@ -258,6 +264,7 @@ def lib():
         L.cilqr_stage_quadratize.argtypes = [C.c_void_p]
         L.cilqr_stage_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.cilqr_stage_forward.argtypes = [C.c_void_p, C.c_double]
+        L.cilqr_set_search_seed.argtypes = [C.c_void_p, C.POINTER(SearchSeed)]
         L.cilqr_stage_read.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
         L.cilqr_stage_nearest_lane.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_int32, C.c_int32]
@@ -608,11 +615,40 @@ class BatchIlqrOptimizer:
                             _ptr(r["alpha_trace"]))
         return sol, r
 
-    def submit(self, scene: dict, max_iter_trajs: int = 0, alpha_trace: bool = False, warm=None):
-        """Asynchronous plan(): returns a ticket; collect(ticket) -- oldest first -- waits and returns plan()'s dict."""
+    def set_search_seed(self, seed: "dict | None"):
+        """Test door (cilqr_set_search_seed): seed = dict(cost_old=, lam=, dlam=, iter=), each a [B] array or absent / None,
+        taken by the next solve on the handle; None disarms.  The arrays are NumPy arrays (host memory) or, all of them,
+        contiguous torch device tensors (float64; iter int32): the call copies them either way."""
+        if seed is None:
+            self._chk(self.L.cilqr_set_search_seed(self.h, None), "set_search_seed")
+            return
+        given = {k: seed.get(k) for k in ("cost_old", "lam", "dlam", "iter") if seed.get(k) is not None}
+        if given and all(_is_device_tensor(v) for v in given.values()):
+            for k, v in given.items():
+                if not v.is_cuda or not v.is_contiguous() or str(v.dtype) != ("torch.int32" if k == "iter" else "torch.float64"):
+                    raise ValueError("a search seed on the device: contiguous float64 tensors, iter int32")
+            sizes = {int(v.numel()) for v in given.values()}
+            if len(sizes) != 1:
+                raise ValueError("a search seed needs at least one array, and all of one length")
+            s = SearchSeed(MEM_DEVICE, sizes.pop(), *(given[k].data_ptr() if k in given else None for k in ("cost_old", "lam", "dlam", "iter")))
+            self._chk(self.L.cilqr_set_search_seed(self.h, C.byref(s)), "set_search_seed")
+            return
+        a = {k: (None if seed.get(k) is None else _f64(seed[k]).ravel()) for k in ("cost_old", "lam", "dlam")}
+        a["iter"] = None if seed.get("iter") is None else np.ascontiguousarray(seed["iter"], dtype=np.int32).ravel()
+        sizes = {v.size for v in a.values() if v is not None}
+        if len(sizes) != 1:
+            raise ValueError("a search seed needs at least one array, and all of one length")
+        s = SearchSeed(MEM_HOST, sizes.pop(), *(None if a[k] is None else a[k].ctypes.data for k in ("cost_old", "lam", "dlam", "iter")))
+        self._chk(self.L.cilqr_set_search_seed(self.h, C.byref(s)), "set_search_seed")
+
+    def submit(self, scene: dict, max_iter_trajs: int = 0, alpha_trace: bool = False, warm=None, seed=None):
+        """Asynchronous plan(): returns a ticket; collect(ticket) -- oldest first -- waits and returns plan()'s dict.
+        seed: see set_search_seed (a test door; only with nothing else submitted on the handle)."""
         prob, keep = self._host_problem(scene)
         w, wkeep = make_warm(warm, self.N)
         sol, r = self._plan_solution(prob.batch, max_iter_trajs, alpha_trace)
+        if seed is not None:
+            self.set_search_seed(seed)
         rc = self.submit_raw(prob, sol, w)
         if rc != OK:
             raise CilqrError(rc, "in cilqr_submit")
@@ -627,8 +663,9 @@ class BatchIlqrOptimizer:
             return dict(rc=rc)
         return dict(rc=rc, **ticket["result"])
 
-    def plan(self, scene: dict, max_iter_trajs: int = 0, check: bool = True, alpha_trace: bool = False, warm=None):
+    def plan(self, scene: dict, max_iter_trajs: int = 0, check: bool = True, alpha_trace: bool = False, warm=None, seed=None):
         """scene: dict from cilqr_amd.scenario.generate (problem-major numpy arrays).
+        seed=dict(cost_old=, lam=, dlam=, iter=): the test door set_search_seed, for this solve.
         alpha_trace=True adds "alpha_trace" [B, max_iter] int8: the accepted step-size index of every
         iteration (-1 all rejected, -2 left before the line search, -3 not run).
         warm=(rows, shift=None, layout=ROWS_TRAJ): start from the controls of earlier trajectories (make_warm,
@@ -637,6 +674,8 @@ class BatchIlqrOptimizer:
             prob, keep = self._host_problem(scene)
             w, wkeep = make_warm(warm, self.N)
             sol, r = self._plan_solution(prob.batch, max_iter_trajs, alpha_trace)
+            if seed is not None:             # armed last: nothing between here and the solve can raise and leave it behind
+                self.set_search_seed(seed)
             rc = self.solve_raw(prob, sol, w)
             del keep, wkeep
             if rc != OK:
@@ -657,6 +696,8 @@ class BatchIlqrOptimizer:
         at = np.full((B, M), -3, np.int8) if alpha_trace else None
         sol = SolutionBatch(MEM_HOST, max_iter_trajs, _ptr(traj), _ptr(hist), _ptr(n_cost), _ptr(status),
                             _ptr(n_iter), _ptr(it), _ptr(n_it), _ptr(at))
+        if seed is not None:
+            self.set_search_seed(seed)
         rc = self.solve_raw(prob, sol)
         del keep
         if rc != OK:

@@ -315,6 +315,28 @@ void launch_init_cost_commit(const DeviceState& s, int n, hipStream_t st) {
   hipLaunchKernelGGL(k_init_cost_commit, dim3((n + 255) / 256), dim3(256), 0, st, s, n);
 }
 
+// test door (cilqr_set_search_seed): the search state Optimize() starts with, by problem; a null array keeps what the load
+// and k_init_cost_commit left.  The iterations below a seeded count never ran, and k_export_hist copies every alpha_trace row
+// below n_iter from atrace (it writes -3 itself only from n_iter on): those rows are set to -3 here.
+__global__ void k_search_seed(DeviceState s, int n, const double* __restrict__ cost_old, const double* __restrict__ lambda,
+                              const double* __restrict__ dlambda, const int* __restrict__ iter) {
+  const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= n) return;
+  const int pb = s.pid[slot];
+  if (cost_old) s.cost_old[slot] = cost_old[pb];
+  if (lambda) s.lambda[slot] = lambda[pb];
+  if (dlambda) s.dlambda[slot] = dlambda[pb];
+  if (iter) {
+    const int it = iter[pb];
+    s.iter[pb] = it;
+    for (int r = 0; r < it; ++r) s.atrace[(size_t)r * s.Pcap + pb] = (signed char)-3;
+  }
+}
+void launch_search_seed(const DeviceState& s, int n, const double* cost_old, const double* lambda, const double* dlambda,
+                        const int* iter, hipStream_t st) {
+  hipLaunchKernelGGL(k_search_seed, dim3((n + 255) / 256), dim3(256), 0, st, s, n, cost_old, lambda, dlambda, iter);
+}
+
 #ifndef CILQR_QUAD_OCC
 #define CILQR_QUAD_OCC 4
 #endif

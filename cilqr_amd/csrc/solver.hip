@@ -963,6 +963,13 @@ static int solve_groups(cilqr_solver* h, cilqr_job& j, const cilqr_problem_batch
                         cilqr_solution_batch* out) {
   if (in == nullptr || in->n_lane_groups <= 1) return solve_one(h, j, in, warm, out);   // j.prof: published by the caller's thread
   // problems grouped by lane table: one solve per group on contiguous sub-ranges of every array
+  {   // (the test door's seed is for a batch with one lane table: include/cilqr.h)
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->seed_armed) {
+      h->seed_armed = false;
+      return CILQR_ERR_ARG;
+    }
+  }
   if (in->lane_group_start == nullptr || in->lane_group_left == nullptr || in->lane_group_right == nullptr ||
       in->left_lane == nullptr || in->right_lane == nullptr)
     return CILQR_ERR_CONSTRAINTS;
@@ -1061,6 +1068,34 @@ bool host_out_is_big(const cilqr_solver* h, int B, const cilqr_solution_batch* o
   const size_t K = (size_t)h->cfg.n_steps + 1;
   const size_t n_itr = out->iter_trajs ? (size_t)B * (size_t)std::max(out->max_iter_trajs, 0) * K * 10 : 0;
   return out_head_bytes(h, B, out) + n_itr * 8 > kSmallTransfer;
+}
+
+// test door (cilqr_set_search_seed): the armed seed, if any, goes to the device and over the search state of the solve that
+// begins (behind k_init_cost_commit); the stream is waited for, so that the host copies can go
+int apply_search_seed(cilqr_solver* h, const DeviceState& d, int B, hipStream_t st) {
+  std::vector<double> co, lam, dl;
+  std::vector<int> it;
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->seed_armed) return CILQR_OK;
+    h->seed_armed = false;
+    if (h->seed_batch != B) return CILQR_ERR_ARG;
+    co.swap(h->seed_cost_old); lam.swap(h->seed_lambda); dl.swap(h->seed_dlambda); it.swap(h->seed_iter);
+  }
+  const size_t n = (size_t)B;
+  HIP_TRY(h->seed_dev.grow(n * (3 * sizeof(double) + sizeof(int)), &h->grown_bytes));
+  double* base = h->seed_dev.as<double>();
+  double* d_co = base, *d_lam = base + n, *d_dl = base + 2 * n;
+  int* d_it = reinterpret_cast<int*>(base + 3 * n);
+  if (!co.empty()) HIP_TRY(hipMemcpyAsync(d_co, co.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
+  if (!lam.empty()) HIP_TRY(hipMemcpyAsync(d_lam, lam.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
+  if (!dl.empty()) HIP_TRY(hipMemcpyAsync(d_dl, dl.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
+  if (!it.empty()) HIP_TRY(hipMemcpyAsync(d_it, it.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
+  launch_search_seed(d, B, co.empty() ? nullptr : d_co, lam.empty() ? nullptr : d_lam, dl.empty() ? nullptr : d_dl,
+                     it.empty() ? nullptr : d_it, st);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  return CILQR_OK;
 }
 
 // Arguments, staging, load, init guess and its cost (cc:64-78, 141-173), on the first stage's stream.
@@ -1171,6 +1206,7 @@ int job_begin(cilqr_solver* h, cilqr_job& j) {
   j.first_quad = h->fuse_first && !to_tail && launch_quadratize_first(j.d, B, st);
   if (!j.first_quad) launch_cost_only(j.d, nullptr, B, 0, st, 1);
   launch_init_cost_commit(j.d, B, st);                 // cc:170,173
+  if (int src = apply_search_seed(h, j.d, B, st)) return src;   // test door: nothing is launched unless a seed is armed
   if (j.o_it) launch_export_iter_traj(j.d, nullptr, B, j.o_it, out->max_iter_trajs, st);
   if (j.tm.end()) return CILQR_ERR_DEVICE;
 
@@ -1843,6 +1879,42 @@ int cilqr_stage_backward(cilqr_handle h, const double* lambda, int32_t memory) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   h->stage |= 8;
+  return CILQR_OK;
+}
+
+int cilqr_set_search_seed(cilqr_handle h, const cilqr_search_seed* seed) {
+  if (h == nullptr) return CILQR_ERR_NULL;
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->job_count != 0) return CILQR_ERR_STATE;
+    if (seed == nullptr) {
+      h->seed_armed = false;
+      return CILQR_OK;
+    }
+  }
+  if (seed->batch < 1 || seed->batch > h->capacity) return CILQR_ERR_ARG;
+  if (seed->memory != CILQR_MEM_HOST && seed->memory != CILQR_MEM_DEVICE) return CILQR_ERR_ARG;
+  const size_t n = (size_t)seed->batch;
+  std::vector<double> co, lam, dl;
+  std::vector<int> it;
+  if (seed->memory == CILQR_MEM_HOST) {
+    if (seed->cost_old) co.assign(seed->cost_old, seed->cost_old + n);
+    if (seed->lambda) lam.assign(seed->lambda, seed->lambda + n);
+    if (seed->dlambda) dl.assign(seed->dlambda, seed->dlambda + n);
+    if (seed->iter) it.assign(seed->iter, seed->iter + n);
+  } else {
+    HIP_TRY(hipSetDevice(h->device));
+    if (seed->cost_old) { co.resize(n); HIP_TRY(hipMemcpy(co.data(), seed->cost_old, n * sizeof(double), hipMemcpyDeviceToHost)); }
+    if (seed->lambda) { lam.resize(n); HIP_TRY(hipMemcpy(lam.data(), seed->lambda, n * sizeof(double), hipMemcpyDeviceToHost)); }
+    if (seed->dlambda) { dl.resize(n); HIP_TRY(hipMemcpy(dl.data(), seed->dlambda, n * sizeof(double), hipMemcpyDeviceToHost)); }
+    if (seed->iter) { it.resize(n); HIP_TRY(hipMemcpy(it.data(), seed->iter, n * sizeof(int), hipMemcpyDeviceToHost)); }
+  }
+  for (int v : it)
+    if (v < 0 || v >= h->cfg.max_iter) return CILQR_ERR_ARG;
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->seed_cost_old.swap(co); h->seed_lambda.swap(lam); h->seed_dlambda.swap(dl); h->seed_iter.swap(it);
+  h->seed_batch = seed->batch;
+  h->seed_armed = true;
   return CILQR_OK;
 }
 

@@ -199,6 +199,13 @@ struct cilqr_solver {
   int stage = 0;           // bit0 loaded, bit1 iterate, bit2 quadratized, bit3 gains
   bool stage_warm_all = false;   // ... without a shift array: every problem is warm-started, the init guess is not launched
   bool stage_warm = false; // the load in force was cilqr_stage_load_warm with a warm start: sets[0].warm_shift is current
+  // test door (cilqr_set_search_seed), under mu: the seed the next job_begin takes -- host copies of the caller's arrays
+  // (an empty vector: that value is not seeded) -- and the device block they are applied from
+  bool seed_armed = false;
+  int seed_batch = 0;
+  std::vector<double> seed_cost_old, seed_lambda, seed_dlambda;
+  std::vector<int> seed_iter;
+  cilqr::dev_mem seed_dev;
   int spec_threshold = 8192;  // active sets up to this size evaluate all 11 step sizes at once (cilqr_solve_batch)
   // ... and for solves submitted with cilqr_submit: other solves share the GPU then, and eleven candidates per problem
   // where two or three would do is throughput taken from them (measured: pool of two 1.90 -> 1.98 M solves/s, one handle

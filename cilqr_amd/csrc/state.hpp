@@ -233,6 +233,9 @@ void launch_spec_cost(const DeviceState& s, const int* list, const int* n_ptr, i
 int spec_open_capacity(const DeviceState& s);   // most active problems an all-eleven-step-sizes pass can take (kernels_search.hip)
 void launch_round_cost(const DeviceState& s, int r0, int group, int n_max, int n_grid, hipStream_t st);
 void launch_init_cost_commit(const DeviceState& s, int n, hipStream_t st);
+// test door (cilqr_set_search_seed): device arrays [n] by problem, each nullable
+void launch_search_seed(const DeviceState& s, int n, const double* cost_old, const double* lambda, const double* dlambda,
+                        const int* iter, hipStream_t st);
 void launch_quadratize(const DeviceState& s, const int* list, int n, int only_upd, hipStream_t st);
 void launch_backward(const DeviceState& s, const int* list, int n, const double* lambda_override,
                      int team_threshold, int wave_threshold, hipStream_t st, hipEvent_t ev_start = nullptr,

@@ -392,6 +392,33 @@ int cilqr_stage_forward(cilqr_handle h, double alpha);
 #define CILQR_T_GNORM 16     /* [B] */
 int cilqr_stage_read(cilqr_handle h, int32_t tensor, double* dst, int32_t memory);
 
+/* ---- test door: the search state a solve starts with (no product path calls this) ----
+ * Optimize() begins with cost_old = TotalCost(first iterate), lambda = dlambda = 1 and iteration 0 (cc:172, 180-186), so which
+ * step size a solve accepts, which clause rejects the others and which exit it takes cannot be chosen from outside.  A seed
+ * overwrites those four per-problem values of the NEXT solve on the handle (cilqr_solve_batch[_warm], or the next cilqr_submit
+ * to begin), right after the first iterate's cost was committed; everything after that is the ordinary solve -- every line-search
+ * schedule, compaction, the finishing arena, the tail kernel.  The first iterate itself is chosen with a warm start, shift 0.
+ *   cost_old, lambda, dlambda  [batch] doubles, each may be NULL (that value keeps its start).  ANY bits are taken, non-finite
+ *                              ones included: they are test cases.
+ *   iter                       [batch], NULL or values in [0, max_iter): the iteration count the problem starts at, so that
+ *                              iter = max_iter - n gives a solve of at most n iterations.  n_iter counts from it; alpha_trace
+ *                              entries below it read -3 (not run).
+ * Row 0 of cost_hist stays the TRUE cost of the first iterate, whatever cost_old was seeded; n_cost / n_iter_trajs start at 1.
+ * The arrays are copied by the call (device arrays with a synchronous copy).  The seed is consumed by the solve that takes it,
+ * whose batch must equal `batch` (CILQR_ERR_ARG from that solve otherwise).  A seed is for batches with one lane table: a batch with several lane groups is
+ * refused while a seed is armed (CILQR_ERR_ARG, the seed disarmed).
+ * seed == NULL disarms.  CILQR_ERR_NULL for a NULL handle; CILQR_ERR_ARG for batch < 1 or above the handle's capacity, an
+ * unknown memory flag, an iter outside [0, max_iter); CILQR_ERR_STATE while solves are submitted on the handle. */
+typedef struct cilqr_search_seed {
+  int32_t memory;          /* CILQR_MEM_* of the four arrays */
+  int32_t batch;
+  const double*  cost_old; /* [batch] or NULL */
+  const double*  lambda;   /* [batch] or NULL */
+  const double*  dlambda;  /* [batch] or NULL */
+  const int32_t* iter;     /* [batch] or NULL */
+} cilqr_search_seed;
+int cilqr_set_search_seed(cilqr_handle h, const cilqr_search_seed* seed);
+
 /* FindNeastLaneSegment (cc:605-618) for n arbitrary points xy[n][2]: index of the nearest left /
  * right lane segment.  use_grid = 1: the accelerated lookup the solver uses; 0: the reference's
  * linear scan.  Both must agree everywhere (test hook). */

@@ -718,6 +718,10 @@ struct Oracle {
     double lambda, dlambda;
     int iter;
     bool stop_after_accept;
+    // the cost the first acceptance test measures against (cc:254); NaN: TotalCost(X, U), as Optimize() has it.  Row 0 of the
+    // cost history stays TotalCost(X, U) either way.
+    double cost_old = std::numeric_limits<double>::quiet_NaN();
+    bool seeded = false;   // cost_old is given (a NaN included: a seed may be any bits)
   };
 
   // ---- cc:154-320 ----
@@ -757,6 +761,7 @@ struct Oracle {
     double dV[2];
     int iter = 0;
     if (warm) { lambda = warm->lambda; dlambda = warm->dlambda; iter = warm->iter; }
+    if (warm && warm->seeded) cost_old = warm->cost_old;
     const int iter_first = iter;
     bool stopped = false;
     for (; iter < cfg.max_iter; ++iter) {
@@ -915,6 +920,19 @@ int oracle_replay(void* h, const double* X, const double* U, double lambda, doub
   if (!o->has_problem) return -1;
   Oracle::Warm w{X, U, lambda, dlambda, iter, true};
   return o->Plan(traj, cost_hist, n_cost, status, n_iter, nullptr, 0, nullptr, trace, nullptr, &w, nullptr,
+                 lambda_out);
+}
+
+/* oracle_replay with the search state of tests/search_reference.py: cost_old as given when `seeded` (any bits; otherwise
+ * TotalCost(X, U)), and -- stop_after_accept = 0 -- on to the end of the solve, so that iter = max_iter - n replays n iterations.
+ * n_iter_trajs counts the iterates from (X, U), as a solve does. */
+int oracle_replay_seeded(void* h, const double* X, const double* U, double lambda, double dlambda, int iter,
+                         double cost_old, int seeded, int stop_after_accept, double* traj, double* cost_hist, int* n_cost,
+                         int* status, int* n_iter, int* n_iter_trajs, double* trace, double* lambda_out) {
+  Oracle* o = static_cast<Oracle*>(h);
+  if (!o->has_problem) return -1;
+  Oracle::Warm w{X, U, lambda, dlambda, iter, stop_after_accept != 0, cost_old, seeded != 0};
+  return o->Plan(traj, cost_hist, n_cost, status, n_iter, nullptr, 0, n_iter_trajs, trace, nullptr, &w, nullptr,
                  lambda_out);
 }
 

@@ -88,6 +88,14 @@ int oracle_replay(void* h, const double* X, const double* U, double lambda, doub
                   double* traj, double* cost_hist, int* n_cost, int* status, int* n_iter, double* trace,
                   double* lambda_out);
 
+/* oracle_replay with a seeded search state (tests/search_reference.py): when `seeded`, cost_old -- any bits, a NaN included --
+ * replaces TotalCost(X, U) as what the first acceptance test measures against (row 0 of cost_hist stays TotalCost(X, U));
+ * stop_after_accept = 0 replays to the end of the solve, so that iter = max_iter - n runs n iterations.  n_iter_trajs counts
+ * the iterates from (X, U) on. */
+int oracle_replay_seeded(void* h, const double* X, const double* U, double lambda, double dlambda, int iter,
+                         double cost_old, int seeded, int stop_after_accept, double* traj, double* cost_hist, int* n_cost,
+                         int* status, int* n_iter, int* n_iter_trajs, double* trace, double* lambda_out);
+
 /* ---- stage entry points (same arithmetic as inside oracle_plan) ---- */
 void oracle_get_constraints(void* h, double* goals /*K*6*/, double* corridor /*K*cmax*3*/,
                             double* left_abc /*SL*3*/, double* right_abc /*SR*3*/, double* disc_radius);

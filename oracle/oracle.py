@@ -226,27 +226,37 @@ class Oracle:
                     trace=trace[:n_iter.value] if trace is not None else None,
                     min_margin=margin.value)
 
-    def replay(self, X, U, lam: float, dlam: float, it: int):
+    def replay(self, X, U, lam: float, dlam: float, it: int, cost_old=None, to_the_end: bool = False):
         """Optimize() re-entered at iteration `it` from the iterate (X, U) with regularisation state
         (lam, dlam): runs until one iteration is accepted or the solve ends.  Returns dict(cost0 = cost
         row of (X, U), cost1 = accepted row or None, traj = iterate afterwards [K,10], status, n_iter
         = next iteration index, decisions = accepted alpha index per replayed iteration (-1 rejected,
-        -2 gradient-norm exit), margins, lam, dlam afterwards)."""
+        -2 gradient-norm exit), margins, lam, dlam afterwards).
+        cost_old (any double, NaN included; None: TotalCost(X, U)) is what the first acceptance test measures against -- the
+        seed of tests/search_reference.py; to_the_end: do not stop at the first accepted iteration.  With either, the dict
+        also has cost_hist [n_cost, 5], n_cost and n_iter_trajs."""
         X, U = _f64(X), _f64(U)
         K, M = self.K, self.cfg.max_iter
         traj = np.zeros((K, 10))
         hist = np.zeros((M + 1, 5))
-        n_cost, status, n_iter = C.c_int(), C.c_int(), C.c_int()
+        n_cost, status, n_iter, n_it = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         trace = np.zeros((max(1, M - it), 10))
         lo = np.zeros(2)
-        rc = self.L.oracle_replay(self.h, _p(X), _p(U), C.c_double(lam), C.c_double(dlam), C.c_int(it), _p(traj),
-                                  _p(hist), C.byref(n_cost), C.byref(status), C.byref(n_iter), _p(trace), _p(lo))
+        if cost_old is None and not to_the_end:
+            rc = self.L.oracle_replay(self.h, _p(X), _p(U), C.c_double(lam), C.c_double(dlam), C.c_int(it), _p(traj),
+                                      _p(hist), C.byref(n_cost), C.byref(status), C.byref(n_iter), _p(trace), _p(lo))
+        else:
+            rc = self.L.oracle_replay_seeded(self.h, _p(X), _p(U), C.c_double(lam), C.c_double(dlam), C.c_int(it),
+                                             C.c_double(0.0 if cost_old is None else cost_old), C.c_int(cost_old is not None),
+                                             C.c_int(0 if to_the_end else 1), _p(traj), _p(hist), C.byref(n_cost),
+                                             C.byref(status), C.byref(n_iter), C.byref(n_it), _p(trace), _p(lo))
         if rc != 0:
             raise RuntimeError("oracle_replay: no problem set")
         n = n_iter.value - it
         return dict(cost0=hist[0].copy(), cost1=hist[1].copy() if n_cost.value > 1 else None, traj=traj,
                     status=status.value, n_iter=n_iter.value, decisions=trace[:n, 0].astype(int),
-                    margins=trace[:n, 8].copy(), lam=float(lo[0]), dlam=float(lo[1]))
+                    margins=trace[:n, 8].copy(), lam=float(lo[0]), dlam=float(lo[1]),
+                    cost_hist=hist[:n_cost.value].copy(), n_cost=n_cost.value, n_iter_trajs=n_it.value)
 
     # ---- stages ----
     def constraints(self):
