@@ -97,6 +97,23 @@ extern "C" void cilqr_debug_cost_profile(unsigned long long* out, int reset) {  
 }
 #endif
 
+// Knot cost of candidate alpha_r at arena position j (cost_reduce.hpp: the candidate arena).  The three kernels below differ in
+// how a thread finds its (r, j, slot) -- a measured choice each, see their comments -- and in nothing else.
+// knot 0 from the first-knot cache: only the control is the candidate's (the state's loads are dead)
+CILQR_DEV void candidate_knot0_cost(const DeviceState& s, int r, int j, int slot) {
+  const size_t cap = (size_t)s.spec_cap;
+  double x[6], u[2];
+  load_candidate_knot(s, cap, r, 0, j, x, u);
+  knot0_cost_cached(s, slot, u, candidate_parts(s, cap, r, 0, j), cap);
+}
+template <int D, bool EX>
+CILQR_DEV void candidate_knot_cost(const DeviceState& s, const double* lanes, int r, int i, int j, int slot) {
+  const size_t cap = (size_t)s.spec_cap;
+  double x[6], u[2];
+  load_candidate_knot(s, cap, r, i, j, x, u);
+  knot_cost<D, EX>(s, lanes, i, slot, x, u, candidate_parts(s, cap, r, i, j), cap);
+}
+
 // speculative line search: knot i of candidate alpha_{r0 + blockIdx.z} of list entry j
 template <int D, bool EX>
 __global__ __launch_bounds__(256) CILQR_COST_ATTR void k_spec_cost(DeviceState s, const int* __restrict__ list,
@@ -104,18 +121,12 @@ __global__ __launch_bounds__(256) CILQR_COST_ATTR void k_spec_cost(DeviceState s
   extern __shared__ double lds[];
   const int n = list_count(s, n_ptr, off, n_max);   // `list` points at entry `off` already
   if ((int)(blockIdx.x * blockDim.x) >= n) return;
-  const size_t cap = (size_t)s.spec_cap;
   if (blockIdx.y == 0 && s.knot0 != nullptr) {   // knot 0 from the first-knot cache (block-uniform; no lane tables)
     const int r = r0 + blockIdx.z;
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
       const int slot = list[j];
       if (s.acc_idx[slot] != -1) continue;
-      double u[2] = {0.0, 0.0};
-      if (0 < s.p.N) {
-        const double2 q = s.Us[(size_t)r * s.p.N * cap + j];
-        u[0] = q.x; u[1] = q.y;
-      }
-      knot0_cost_cached(s, slot, u, s.parts + (size_t)r * s.p.K * kPartPairs * cap + j, cap);
+      candidate_knot0_cost(s, r, j, slot);
     }
     return;
   }
@@ -124,15 +135,7 @@ __global__ __launch_bounds__(256) CILQR_COST_ATTR void k_spec_cost(DeviceState s
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
     const int slot = list[j];
     if (s.acc_idx[slot] != -1) continue;   // left at the gradient-norm exit
-    const double2* xb = s.Xs + ((size_t)r * s.p.K + i) * 3 * cap + j;
-    const double2 p0 = xb[0], p1 = xb[cap], p2 = xb[2 * cap];
-    const double x[6] = {p0.x, p0.y, p1.x, p1.y, p2.x, p2.y};
-    double u[2] = {0.0, 0.0};
-    if (i < s.p.N) {
-      const double2 q = s.Us[((size_t)r * s.p.N + i) * cap + j];
-      u[0] = q.x; u[1] = q.y;
-    }
-    knot_cost<D, EX>(s, lanes, i, slot, x, u, s.parts + ((size_t)r * s.p.K + i) * kPartPairs * cap + j, cap);
+    candidate_knot_cost<D, EX>(s, lanes, r, i, j, slot);
   }
 }
 // The same with P consecutive lanes per problem: knot i of candidates alpha_{r0} .. alpha_{r_end-1} of list entry j; the lanes
@@ -149,19 +152,13 @@ __global__ __launch_bounds__(256) CILQR_COST_ATTR void k_spec_cost_packed(Device
   const int n = list_count(s, n_ptr, off, n_max);
   constexpr int per_block = 256 / P;
   if ((int)(blockIdx.x * per_block) >= n) return;
-  const size_t cap = (size_t)s.spec_cap;
   if (blockIdx.y == 0 && s.knot0 != nullptr) {   // knot 0 from the first-knot cache (block-uniform; no lane tables)
     const int r = r0 + (int)(threadIdx.x % P);
     if (r >= r_end) return;
     for (int j = blockIdx.x * per_block + threadIdx.x / P; j < n; j += gridDim.x * per_block) {
       const int slot = list[j];
       if (s.acc_idx[slot] != -1) continue;
-      double u[2] = {0.0, 0.0};
-      if (0 < s.p.N) {
-        const double2 q = s.Us[(size_t)r * s.p.N * cap + j];
-        u[0] = q.x; u[1] = q.y;
-      }
-      knot0_cost_cached(s, slot, u, s.parts + (size_t)r * s.p.K * kPartPairs * cap + j, cap);
+      candidate_knot0_cost(s, r, j, slot);
     }
     return;
   }
@@ -171,15 +168,7 @@ __global__ __launch_bounds__(256) CILQR_COST_ATTR void k_spec_cost_packed(Device
   for (int j = blockIdx.x * per_block + threadIdx.x / P; j < n; j += gridDim.x * per_block) {
     const int slot = list[j];
     if (s.acc_idx[slot] != -1) continue;   // left at the gradient-norm exit
-    const double2* xb = s.Xs + ((size_t)r * s.p.K + i) * 3 * cap + j;
-    const double2 p0 = xb[0], p1 = xb[cap], p2 = xb[2 * cap];
-    const double x[6] = {p0.x, p0.y, p1.x, p1.y, p2.x, p2.y};
-    double u[2] = {0.0, 0.0};
-    if (i < s.p.N) {
-      const double2 q = s.Us[((size_t)r * s.p.N + i) * cap + j];
-      u[0] = q.x; u[1] = q.y;
-    }
-    knot_cost<D, EX>(s, lanes, i, slot, x, u, s.parts + ((size_t)r * s.p.K + i) * kPartPairs * cap + j, cap);
+    candidate_knot_cost<D, EX>(s, lanes, r, i, j, slot);
   }
 }
 
@@ -222,41 +211,26 @@ void launch_spec_cost(const DeviceState& s, const int* list, const int* n_ptr, i
 template <int D, int G, bool EX>
 __global__ __launch_bounds__(256) CILQR_COST_ATTR void k_round_cost(DeviceState s, int r0, int n_max) {
   extern __shared__ double lds[];
-  const int* __restrict__ list = s.pend + (size_t)r0 * s.Bcap;
-  const int n = (r0 == 0) ? active_count(s, n_max) : min(s.counters[r0], n_max);
+  const int n = round_count(s, r0, n_max);
   constexpr int per_block = 256 / G;
   if ((int)(blockIdx.x * per_block) >= n) return;
-  const size_t cap = (size_t)s.spec_cap;
   if (blockIdx.y == 0 && s.knot0 != nullptr) {   // knot 0 from the first-knot cache (block-uniform; no lane tables)
     const int r = r0 + (int)(threadIdx.x % G);
     for (int e = blockIdx.x * per_block + threadIdx.x / G; e < n; e += gridDim.x * per_block) {
-      const int j = (r0 == 0) ? e : list[e];
-      const int slot = s.act[j];
+      int slot;
+      const int j = round_entry(s, r0, e, slot);
       if (s.acc_idx[slot] != -1) continue;
-      double u[2] = {0.0, 0.0};
-      if (0 < s.p.N) {
-        const double2 q = s.Us[(size_t)r * s.p.N * cap + j];
-        u[0] = q.x; u[1] = q.y;
-      }
-      knot0_cost_cached(s, slot, u, s.parts + (size_t)r * s.p.K * kPartPairs * cap + j, cap);
+      candidate_knot0_cost(s, r, j, slot);
     }
     return;
   }
   const double* lanes = stage_lanes(s, lds);
   const int i = blockIdx.y, r = r0 + (int)(threadIdx.x % G);
   for (int e = blockIdx.x * per_block + threadIdx.x / G; e < n; e += gridDim.x * per_block) {
-    const int j = (r0 == 0) ? e : list[e];
-    const int slot = s.act[j];
+    int slot;
+    const int j = round_entry(s, r0, e, slot);
     if (s.acc_idx[slot] != -1) continue;
-    const double2* xb = s.Xs + ((size_t)r * s.p.K + i) * 3 * cap + j;
-    const double2 p0 = xb[0], p1 = xb[cap], p2 = xb[2 * cap];
-    const double x[6] = {p0.x, p0.y, p1.x, p1.y, p2.x, p2.y};
-    double u[2] = {0.0, 0.0};
-    if (i < s.p.N) {
-      const double2 q = s.Us[((size_t)r * s.p.N + i) * cap + j];
-      u[0] = q.x; u[1] = q.y;
-    }
-    knot_cost<D, EX>(s, lanes, i, slot, x, u, s.parts + ((size_t)r * s.p.K + i) * kPartPairs * cap + j, cap);
+    candidate_knot_cost<D, EX>(s, lanes, r, i, j, slot);
   }
 }
 

@@ -1,9 +1,12 @@
 // Forward pass, 11-step line search and the per-problem state machine of Optimize().
 //
 // Reference behaviour (algorithm/ilqr/ilqr_optimizer.cc):
-//   Forward cc:392-415; line search + acceptance test cc:243-270 (alpha list cc:197,
-//   beta in (1e-4, 10), dcost > 0); regularisation schedule and exits cc:272-308, 312-319;
-//   gradient-norm exit cc:235-241.
+//   Forward cc:392-415; line search cc:243-270 (alpha list cc:197); regularisation schedule and exits
+//   cc:272-308, 312-319; gradient-norm exit cc:235-241.
+// The kernels here are the schedules: which candidates are rolled out, costed and tested when, and on which list a rejection
+// is queued.  What they evaluate is stated elsewhere, once: the acceptance test, the control law and the state machine in
+// search_core.hpp (accepts_step, control_law, update_state); a candidate's rows, its total and a round's entries in
+// cost_reduce.hpp.
 //
 // Lockstep design: every trial of the line search depends only on the pre-trial iterate, so
 // round r evaluates alpha_r for exactly the problems that rejected alpha_0..alpha_{r-1}:
@@ -60,21 +63,18 @@ __global__ __launch_bounds__(64) CILQR_ROLL_ATTR void k_search_open(DeviceState 
 // out alpha_{r+1} and queue the slot for the next round.
 __global__ __launch_bounds__(64) CILQR_ROLL_ATTR void k_search_round(DeviceState s, int r, int n_max, int roll_next) {
   const int* __restrict__ list = (r == 0) ? s.act : s.pend + (size_t)r * s.Bcap;
-  const int n = (r == 0) ? active_count(s, n_max) : min(s.counters[r], n_max);
+  const int n = round_count(s, r, n_max);
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
     const int slot = list[j];
     if (s.acc_idx[slot] != -1) continue;   // left at the gradient-norm exit
     double c5[5];
     reduce_cost(s, slot, 1, c5);
-    const double alpha = kAlpha[r];
-    const double dcost = s.cost_old[slot] - c5[0];                                  // cc:254
-    const double expected = -alpha * (s.dV[slot] + alpha * s.dV[(size_t)s.Bcap + slot]);  // cc:255
-    const double z = dcost / expected;                                              // cc:257
+    const StepVerdict v = accepts_step(s.cost_old[slot], c5[0], kAlpha[r], s.dV[slot], s.dV[(size_t)s.Bcap + slot]);
 #pragma unroll
     for (int c = 0; c < 5; ++c) s.trial[(size_t)c * s.Bcap + slot] = c5[c];
-    if ((z > 1e-4 && z < 10.0) && dcost > 0.0) {                                    // cc:258
+    if (v.accepted) {
       s.acc_idx[slot] = r;
-      s.dcost[slot] = dcost;
+      s.dcost[slot] = v.dcost;
       s.cur[slot] ^= 1;   // the candidate becomes the iterate
     } else if (r + 1 < kNumAlpha) {
       if (roll_next) forward_problem(s, slot, kAlpha[r + 1]);
@@ -128,42 +128,16 @@ __global__ __launch_bounds__(64) void k_spec_reduce(DeviceState s, const int* __
   const int n = list_count(s, n_ptr, off, n_max);
   const int r = r0 + blockIdx.y;
   const size_t cap = (size_t)s.spec_cap;
-  const int K = s.p.K, N = s.p.N;
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
     const int slot = list[j];
     if (open) {   // acc_idx is written by the r == 0 lanes of k_spec_forward, already complete here
       if (s.acc_idx[slot] != -1) continue;
     }
-    double* t = s.spec_tot + (size_t)r * 5 * cap + j;
-#ifdef CILQR_REF_ORDER
     double c5[5];
-    spec_total_cost(s, slot, r, j, c5);
-    t[0] = c5[0];
-    t[cap] = c5[1]; t[2 * cap] = c5[2]; t[3 * cap] = c5[3]; t[4 * cap] = c5[4];
-    (void)K; (void)N;
-#else
-    double jj = 0.0, dx = 0.0, du = 0.0, cc = 0.0, lc = 0.0;
-    const double2* pb = s.parts + (size_t)r * K * kPartPairs * cap + j;
-    // loads of several knots in flight; the sums stay in knot order
-#pragma unroll 8
-    for (int i = 0; i < K; ++i) {
-      const double2* o = pb + (size_t)i * kPartPairs * cap;
-      const double2 a = o[0], c = o[2 * cap];     // (J, bounds) of the state; (corridor, lane): quad_core.hpp, knot_cost
-      jj += a.x;
-      dx += a.y;
-      cc += c.x;
-      lc += c.y;
-    }
-#pragma unroll 8
-    for (int i = 0; i < N; ++i) {
-      const double2 b = pb[((size_t)i * kPartPairs + 1) * cap];   // (J, bounds) of the control
-      jj += b.x;
-      du += b.y;
-    }
-    const double dyn = dx + du;
-    t[0] = jj + dyn + cc + lc;
-    t[cap] = jj; t[2 * cap] = dyn; t[3 * cap] = cc; t[4 * cap] = lc;
-#endif
+    candidate_total(s, slot, r, j, c5);
+    double* t = s.spec_tot + (size_t)r * 5 * cap + j;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) t[c * cap] = c5[c];
   }
 }
 
@@ -185,11 +159,9 @@ __global__ __launch_bounds__(64) void k_spec_pick(DeviceState s, const int* __re
 #pragma unroll
     for (int r = 0; r < kNumAlpha; ++r) {
       if (r < r0) continue;
-      const double alpha = kAlpha[r];
-      dcost = cost_old - tot[r];
-      const double expected = -alpha * (dV0 + alpha * dV1);
-      const double z = dcost / expected;
-      if ((z > 1e-4 && z < 10.0) && dcost > 0.0) {
+      const StepVerdict v = accepts_step(cost_old, tot[r], kAlpha[r], dV0, dV1);
+      dcost = v.dcost;
+      if (v.accepted) {
         acc = r;
         last = r;
         break;
@@ -210,27 +182,18 @@ __global__ __launch_bounds__(256) void k_spec_copy(DeviceState s, const int* __r
                                                    const int* __restrict__ n_ptr, int off, int n_max, int r0) {
   const int n = list_count(s, n_ptr, off, n_max);
   const int i = blockIdx.y;
-  const size_t cap = (size_t)s.spec_cap;
-  const int K = s.p.K, N = s.p.N, Bc = s.Bcap;
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
     const int slot = list[j];
     const int acc = s.acc_idx[slot];
     if (acc < r0) continue;   // not accepted (or accepted in an earlier sequential round)
-    const int nb = s.cur[slot];
-    const double2* xb = s.Xs + ((size_t)acc * K + i) * 3 * cap + j;
-    double2* o = s.X + ((size_t)nb * K + i) * 3 * Bc + slot;
-    o[0] = xb[0];
-    o[(size_t)Bc] = xb[cap];
-    o[(size_t)2 * Bc] = xb[2 * cap];
-    if (i < N) s.U[((size_t)nb * N + i) * Bc + slot] = s.Us[((size_t)acc * N + i) * cap + j];
+    adopt_candidate_knot(s, (size_t)s.spec_cap, (size_t)s.Bcap, acc, i, j, s.cur[slot], slot);
   }
 }
 
 // ---- pre-rolled rounds: alpha_0 .. alpha_{G-1} of every active problem are rolled out in one pass
 // (forward_multi), then evaluated round by round: round r costs and tests only the problems that
 // rejected alpha_0 .. alpha_{r-1}.  The arena position of a problem is its position j in the active
-// list; pending lists 1 .. G-1 hold such positions, the last one (problems that rejected all G)
-// holds slots, which is what the speculative pass over the remaining step sizes takes.
+// list (what the pending lists hold: cost_reduce.hpp, round_entry).
 constexpr int kMaxPreRolled = 6;
 // The same rollouts with one (problem, step size) per lane: P neighbouring lanes share a problem's nominal
 // trajectory and gains (same addresses), four times the waves of k_multi_forward at a third of its registers, so
@@ -274,54 +237,24 @@ __global__ __launch_bounds__(64) void k_multi_forward(DeviceState s, int n) {
 // order) and acceptance test (cc:252-261), IN LIST ORDER and stopping at the first that passes -- what the
 // sequential loop does; rejected all G -> pending list r0 + G (positions, or slots when `last`)
 __global__ __launch_bounds__(64) void k_round_pick(DeviceState s, int r0, int G, int n_max, int last) {
-  const int* __restrict__ list = s.pend + (size_t)r0 * s.Bcap;
-  const int n = (r0 == 0) ? active_count(s, n_max) : min(s.counters[r0], n_max);
-  const size_t cap = (size_t)s.spec_cap;
-  const int K = s.p.K, N = s.p.N;
+  const int n = round_count(s, r0, n_max);
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
-    const int j = (r0 == 0) ? e : list[e];
-    const int slot = s.act[j];
+    int slot;
+    const int j = round_entry(s, r0, e, slot);
     if (s.acc_idx[slot] != -1) continue;   // left at the gradient-norm exit
     const double cost_old = s.cost_old[slot], dV0 = s.dV[slot], dV1 = s.dV[(size_t)s.Bcap + slot];
     bool accepted = false;
     for (int r = r0; r < r0 + G && !accepted; ++r) {
-#ifdef CILQR_REF_ORDER
       double c5[5];
-      spec_total_cost(s, slot, r, j, c5);
-      (void)K; (void)N; (void)cap;
-#else
-      double jj = 0.0, dx = 0.0, du = 0.0, cc = 0.0, lc = 0.0;
-      const double2* pb = s.parts + (size_t)r * K * kPartPairs * cap + j;
-      // loads of several knots in flight; the sums stay in knot order
-#pragma unroll 8
-      for (int i = 0; i < K; ++i) {
-        const double2* o = pb + (size_t)i * kPartPairs * cap;
-        const double2 a = o[0], c = o[2 * cap];     // (J, bounds) of the state; (corridor, lane): quad_core.hpp, knot_cost
-        jj += a.x;
-        dx += a.y;
-        cc += c.x;
-        lc += c.y;
-      }
-#pragma unroll 8
-      for (int i = 0; i < N; ++i) {
-        const double2 b = pb[((size_t)i * kPartPairs + 1) * cap];   // (J, bounds) of the control
-        jj += b.x;
-        du += b.y;
-      }
-      const double dyn = dx + du;
-      const double c5[5] = {jj + dyn + cc + lc, jj, dyn, cc, lc};
-#endif
-      const double alpha = kAlpha[r];
-      const double dcost = cost_old - c5[0];                                          // cc:254
-      const double expected = -alpha * (dV0 + alpha * dV1);                           // cc:255
-      const double z = dcost / expected;                                              // cc:257
+      candidate_total(s, slot, r, j, c5);
+      const StepVerdict v = accepts_step(cost_old, c5[0], kAlpha[r], dV0, dV1);
 #pragma unroll
       for (int c = 0; c < 5; ++c) s.trial[(size_t)c * s.Bcap + slot] = c5[c];
-      if ((z > 1e-4 && z < 10.0) && dcost > 0.0) {                                    // cc:258
-        s.acc_idx[slot] = r;
-        s.dcost[slot] = dcost;
-        s.cur[slot] ^= 1;   // k_multi_copy fills the new current buffer
+      if (v.accepted) {
         accepted = true;
+        s.acc_idx[slot] = r;
+        s.dcost[slot] = v.dcost;
+        s.cur[slot] ^= 1;   // k_multi_copy fills the new current buffer
       }
     }
     if (!accepted && r0 + G < kNumAlpha) {
@@ -338,8 +271,6 @@ constexpr int kCopyKnots = 4;
 __global__ __launch_bounds__(256) void k_multi_copy(DeviceState s, int n_max, int G) {
   const int n = active_count(s, n_max);
   const int i0 = blockIdx.y * kCopyKnots;
-  const size_t cap = (size_t)s.spec_cap;
-  const int K = s.p.K, N = s.p.N, Bc = s.Bcap;
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
     const int slot = s.act[j];
     const int acc = s.acc_idx[slot];
@@ -348,13 +279,8 @@ __global__ __launch_bounds__(256) void k_multi_copy(DeviceState s, int n_max, in
 #pragma unroll
     for (int d = 0; d < kCopyKnots; ++d) {
       const int i = i0 + d;
-      if (i >= K) break;
-      const double2* xb = s.Xs + ((size_t)acc * K + i) * 3 * cap + j;
-      double2* o = s.X + ((size_t)nb * K + i) * 3 * Bc + slot;
-      o[0] = xb[0];
-      o[(size_t)Bc] = xb[cap];
-      o[(size_t)2 * Bc] = xb[2 * cap];
-      if (i < N) s.U[((size_t)nb * N + i) * Bc + slot] = s.Us[((size_t)acc * N + i) * cap + j];
+      if (i >= s.p.K) break;
+      adopt_candidate_knot(s, (size_t)s.spec_cap, (size_t)s.Bcap, acc, i, j, nb, slot);
     }
   }
 }
@@ -385,7 +311,6 @@ static int spec_entries(const DeviceState& s, int n_steps_sizes) {
 static DeviceState spec_view(const DeviceState& s, int row0, int stride) {
   DeviceState v = s;
   if (s.spec_rows >= kNumAlpha) return v;          // the plain layout: rows are step sizes, stride is the capacity
-  const size_t K = (size_t)s.p.K, N = (size_t)s.p.N;
   // The base pointers move back by row0 rows of the new stride: rows below row0 are never addressed (every kernel of a pass
   // starts at r0 = row0), and rows row0..10 at that stride must lie inside the cells the arena owns.  Checked here, on the
   // host, for every launch (nothing else holds these three facts together).
@@ -394,9 +319,11 @@ static DeviceState spec_view(const DeviceState& s, int row0, int stride) {
     std::abort();
   }
   v.spec_cap = stride;
-  v.Xs = reinterpret_cast<double2*>(reinterpret_cast<uintptr_t>(s.Xs) - (uintptr_t)row0 * K * 3 * (size_t)stride * sizeof(double2));
-  v.Us = reinterpret_cast<double2*>(reinterpret_cast<uintptr_t>(s.Us) - (uintptr_t)row0 * N * (size_t)stride * sizeof(double2));
-  v.parts = reinterpret_cast<double2*>(reinterpret_cast<uintptr_t>(s.parts) - (uintptr_t)row0 * K * kPartPairs * (size_t)stride * sizeof(double2));
+  // (integers, not pointers: the moved base may lie below the allocation)
+  auto back = [](double2* base, size_t pairs) { return reinterpret_cast<double2*>(reinterpret_cast<uintptr_t>(base) - pairs * sizeof(double2)); };
+  v.Xs = back(s.Xs, cand_x_at(s.p, (size_t)stride, row0, 0, 0));
+  v.Us = back(s.Us, cand_u_at(s.p, (size_t)stride, row0, 0, 0));
+  v.parts = back(s.parts, cand_parts_at(s.p, (size_t)stride, row0, 0, 0));
   return v;
 }
 // most problems an all-eleven pass over the ACTIVE list can take (launch_linesearch falls back to rounds above it)

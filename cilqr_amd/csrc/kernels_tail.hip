@@ -12,9 +12,10 @@
 // leaves at once instead of waiting for the slowest one of its iteration.
 //
 // Same arithmetic.  Every phase calls the device function the lockstep kernels call (knot_quadratize,
-// backward_wave_problem, forward_core, knot_cost, update_state) on a view of the state in which the problem is
-// the only one: the block copies its problem's working set into a private, contiguous arena and runs the functions
-// with Bcap = 1, slot = 0.  Results are bit-identical to the lockstep path (tested with the tail switched off).
+// backward_wave_problem, forward_core, knot_cost, sum_partials, accepts_step, adopt_candidate_knot, update_state) on a
+// view of the state in which the problem is the only one: the block copies its problem's working set into a private,
+// contiguous arena and runs the functions with Bcap = 1, slot = 0 (the candidate rows with the literal stride 1: cost_reduce.hpp).
+// Results are bit-identical to the lockstep path (tested with the tail switched off).
 //
 // Phases of one iteration (256 threads; `|` = __syncthreads):
 //   quadratize (four lanes share a knot's planes | one lane per knot adds their sums up in plane order while another wave
@@ -196,19 +197,11 @@ template <int D, bool EX, bool InLds>
 __device__ __attribute__((noinline)) void tail_knot_cost(int off_view, int r, int i) {
   extern __shared__ double lds[];
   const DeviceState& t = *reinterpret_cast<const DeviceState*>(reinterpret_cast<const char*>(lds) + off_view);
-  const int K = t.p.K, N = t.p.N;
-  const double2* xb = t.Xs + ((size_t)r * K + i) * 3;
-  assume_lds<InLds>(xb);
-  const double2 p0 = xb[0], p1 = xb[1], p2 = xb[2];
-  const double x[6] = {p0.x, p0.y, p1.x, p1.y, p2.x, p2.y};
-  double u[2] = {0.0, 0.0};
-  if (i < N) {
-    const double2* ub = t.Us + (size_t)r * N + i;
-    assume_lds<InLds>(ub);
-    const double2 q = *ub;
-    u[0] = q.x; u[1] = q.y;
-  }
-  knot_cost<D, EX, InLds>(t, lds, i, 0, x, u, t.parts + ((size_t)r * K + i) * kPartPairs, 1);
+  assume_lds<InLds>(t.Xs);
+  assume_lds<InLds>(t.Us);
+  double x[6], u[2];
+  load_candidate_knot(t, 1, r, i, 0, x, u);
+  knot_cost<D, EX, InLds>(t, lds, i, 0, x, u, candidate_parts(t, 1, r, i, 0), 1);
 }
 
 #ifdef CILQR_TAIL_PROFILE
@@ -337,41 +330,19 @@ __global__ __launch_bounds__(kTailThreads) CILQR_TAIL_ATTR void k_tail(DeviceSta
         }
         __syncthreads();
         TP(3);
-        if (tid < nr) {   // total of candidate r: knot partials in index order (k_spec_reduce)
+        if (tid < nr) {   // total of candidate r
           const int r = r0 + tid;
-          double jj = 0.0, dx = 0.0, du = 0.0, cc = 0.0, lc = 0.0;
-          const double2* pp = t.parts + (size_t)r * K * kPartPairs;
-#pragma unroll 8
-          for (int i = 0; i < K; ++i) {
-            const double2* o = pp + (size_t)i * kPartPairs;
-            const double2 aa = o[0], c2 = o[2];     // (J, bounds) of the state; (corridor, lane)
-            jj += aa.x;
-            dx += aa.y;
-            cc += c2.x;
-            lc += c2.y;
-          }
-#pragma unroll 8
-          for (int i = 0; i < N; ++i) {
-            const double2 bb = pp[(size_t)i * kPartPairs + 1];   // (J, bounds) of the control
-            jj += bb.x;
-            du += bb.y;
-          }
-          const double dyn = dx + du;
-          double* tr = tot + r * 5;
-          tr[0] = jj + dyn + cc + lc;
-          tr[1] = jj; tr[2] = dyn; tr[3] = cc; tr[4] = lc;
+          sum_partials(candidate_parts(t, 1, r, 0, 0), 1, K, N, tot + r * 5);
         }
         __syncthreads();
-        if (tid == 0) {   // first passing step size of the chunk (cc:252-261, k_spec_pick)
+        if (tid == 0) {   // first passing step size of the chunk (cc:246-261)
           const double cost_old = t.cost_old[0], dV0 = t.dV[0], dV1 = t.dV[1];
           int won = -1;
           double dcost = 0.0;
           for (int r = r0; r < r0 + nr; ++r) {
-            const double alpha = kAlpha[r];
-            dcost = cost_old - tot[r * 5];
-            const double expected = -alpha * (dV0 + alpha * dV1);
-            const double z = dcost / expected;
-            if ((z > 1e-4 && z < 10.0) && dcost > 0.0) {
+            const StepVerdict v = accepts_step(cost_old, tot[r * 5], kAlpha[r], dV0, dV1);
+            dcost = v.dcost;
+            if (v.accepted) {
               won = r;
               break;
             }
@@ -395,14 +366,7 @@ __global__ __launch_bounds__(kTailThreads) CILQR_TAIL_ATTR void k_tail(DeviceSta
       }
       if (acc >= 0) {   // the accepted candidate becomes the iterate
         const int nb = t.cur[0];
-        for (int i = tid; i < K; i += kTailThreads) {
-          const double2* xb = t.Xs + ((size_t)acc * K + i) * 3;
-          double2* o = t.X + ((size_t)nb * K + i) * 3;
-          o[0] = xb[0];
-          o[1] = xb[1];
-          o[2] = xb[2];
-          if (i < N) t.U[(size_t)nb * N + i] = t.Us[(size_t)acc * N + i];
-        }
+        for (int i = tid; i < K; i += kTailThreads) adopt_candidate_knot(t, 1, 1, acc, i, 0, nb, 0);
       }
     }
     __syncthreads();

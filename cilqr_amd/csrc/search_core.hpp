@@ -1,7 +1,7 @@
 // Forward pass and per-problem state machine (device functions shared by kernels_search.hip and kernels_tail.hip).
 //
 // Reference behaviour (algorithm/ilqr/ilqr_optimizer.cc): Forward cc:392-415; alpha list cc:197; gradient-norm
-// exit cc:235-241; regularisation schedule and exits cc:272-308, 312-319.
+// exit cc:235-241; acceptance test cc:252-261; regularisation schedule and exits cc:272-308, 312-319.
 #pragma once
 #include "cost_reduce.hpp"
 
@@ -23,13 +23,13 @@ struct OutSpec {
   int r, j;
   CILQR_DEV void x(int i, const double* v) const {
     const size_t cap = (size_t)s.spec_cap;
-    double2* b = s.Xs + ((size_t)r * s.p.K + i) * 3 * cap + j;
+    double2* b = s.Xs + cand_x_at(s.p, cap, r, i, j);
     b[0] = make_double2(v[0], v[1]);
     b[cap] = make_double2(v[2], v[3]);
     b[2 * cap] = make_double2(v[4], v[5]);
   }
   CILQR_DEV void u(int i, const double* v) const {
-    s.Us[((size_t)r * s.p.N + i) * (size_t)s.spec_cap + j] = make_double2(v[0], v[1]);
+    s.Us[cand_u_at(s.p, (size_t)s.spec_cap, r, i, j)] = make_double2(v[0], v[1]);
   }
 };
 
@@ -37,9 +37,9 @@ struct OutSpec {
 // candidate's rows are contiguous, so a store is a pointer plus a compile-time offset
 template <bool InLds>
 struct OutSpecSolo {
-  double2* xs;   // Xs + r K 3
-  double2* us;   // Us + r N
-  CILQR_DEV OutSpecSolo(const DeviceState& s, int r) : xs(s.Xs + (size_t)r * s.p.K * 3), us(s.Us + (size_t)r * s.p.N) {
+  double2* xs;   // knot 0 of row r of Xs
+  double2* us;   // ... of Us
+  CILQR_DEV OutSpecSolo(const DeviceState& s, int r) : xs(s.Xs + cand_x_at(s.p, 1, r, 0, 0)), us(s.Us + cand_u_at(s.p, 1, r, 0, 0)) {
     assume_lds<InLds>(xs);
     assume_lds<InLds>(us);
   }
@@ -77,6 +77,22 @@ CILQR_DEV void load_fwd_step(const FwdSrc& q, int i, FwdStep& f) {
   const double2* g = q.gains + (size_t)i * kGainPairs * q.Bc;
 #pragma unroll
   for (int r = 0; r < kGainPairs; ++r) f.kk[r] = g[(size_t)r * q.Bc];
+}
+
+// control of a rollout step (cc:407): the nominal control, the feedback on dx = x - xs, and alpha times the feed-forward term
+CILQR_DEV void control_law(const FwdStep& c, const double* dx, double alpha, double* u) {
+  const double us[2] = {c.u.x, c.u.y};
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    double acc = c.kk[r * 3].x * dx[0];
+    acc += c.kk[r * 3].y * dx[1];
+    acc += c.kk[r * 3 + 1].x * dx[2];
+    acc += c.kk[r * 3 + 1].y * dx[3];
+    acc += c.kk[r * 3 + 2].x * dx[4];
+    acc += c.kk[r * 3 + 2].y * dx[5];
+    const double kff = (r == 0) ? c.kk[6].x : c.kk[6].y;
+    u[r] = (us[r] + acc) + alpha * kff;                           // cc:407
+  }
 }
 
 // roll the closed-loop policy out from goals_[0] (cc:392-415).  kAhead: steps whose operands are requested ahead of
@@ -117,22 +133,11 @@ CILQR_DEV void forward_core(const DeviceState& s, int slot, double alpha, const 
         const FwdStep c = pf[d];
         if (i + kAhead < N) load_fwd_step(src, i + kAhead, pf[d]);
         const double xs[6] = {c.x0.x, c.x0.y, c.x1.x, c.x1.y, c.x2.x, c.x2.y};
-        const double us[2] = {c.u.x, c.u.y};
         double dx[6];
 #pragma unroll
         for (int e = 0; e < 6; ++e) dx[e] = x[e] - xs[e];
         double u[2];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          double acc = c.kk[r * 3].x * dx[0];
-          acc += c.kk[r * 3].y * dx[1];
-          acc += c.kk[r * 3 + 1].x * dx[2];
-          acc += c.kk[r * 3 + 1].y * dx[3];
-          acc += c.kk[r * 3 + 2].x * dx[4];
-          acc += c.kk[r * 3 + 2].y * dx[5];
-          const double kff = (r == 0) ? c.kk[6].x : c.kk[6].y;
-          u[r] = (us[r] + acc) + alpha * kff;                           // cc:407
-        }
+        control_law(c, dx, alpha, u);
         // the straight-line step where a wavefront is alone with its chain (the tail kernel), the branchy one where several
         // waves per SIMD fill each other's gaps (the lockstep rollout kernels: 139 against 161 us per bulk launch, r04 log 11)
         closed_loop_step<Solo>(p, x, u, x);                               // cc:408-410
@@ -179,24 +184,13 @@ CILQR_DEV void forward_multi(const DeviceState& s, int slot, int j) {
         const FwdStep c = pf[d];
         if (i + kFwdAhead < N) load_fwd_step(src, i + kFwdAhead, pf[d]);
         const double xs[6] = {c.x0.x, c.x0.y, c.x1.x, c.x1.y, c.x2.x, c.x2.y};
-        const double us[2] = {c.u.x, c.u.y};
 #pragma unroll
         for (int r = 0; r < G; ++r) {
           double dx[6];
 #pragma unroll
           for (int e = 0; e < 6; ++e) dx[e] = x[r][e] - xs[e];
           double u[2];
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            double acc = c.kk[q * 3].x * dx[0];
-            acc += c.kk[q * 3].y * dx[1];
-            acc += c.kk[q * 3 + 1].x * dx[2];
-            acc += c.kk[q * 3 + 1].y * dx[3];
-            acc += c.kk[q * 3 + 2].x * dx[4];
-            acc += c.kk[q * 3 + 2].y * dx[5];
-            const double kff = (q == 0) ? c.kk[6].x : c.kk[6].y;
-            u[q] = (us[q] + acc) + kAlpha[r] * kff;                         // cc:407
-          }
+          control_law(c, dx, kAlpha[r], u);
           closed_loop_step<false>(p, x[r], u, x[r]);                        // cc:408-410
           const OutSpec out{s, r, j};
           out.u(i, u);
@@ -218,6 +212,20 @@ CILQR_DEV bool leaves_before_search(const DeviceState& s, int slot, bool write) 
     return true;
   }
   return false;
+}
+
+// The acceptance test of one step size (cc:252-261): the candidate's total cost against the iterate's and against the
+// decrease the backward pass expects of alpha (dV0, dV1: delta_V_).  Every schedule's pick calls this; what differs between
+// them is which candidates they test and in which kernel.
+struct StepVerdict {
+  bool accepted;
+  double dcost;   // the decrease, also of a rejected candidate
+};
+CILQR_DEV StepVerdict accepts_step(double cost_old, double total, double alpha, double dV0, double dV1) {
+  const double dcost = cost_old - total;                                           // cc:254
+  const double expected = -alpha * (dV0 + alpha * dV1);                            // cc:255
+  const double z = dcost / expected;                                               // cc:257
+  return StepVerdict{(z > 1e-4 && z < 10.0) && dcost > 0.0, dcost};                // cc:258
 }
 
 // Per-problem bookkeeping after the line search (cc:272-308, 312-319).  `s` holds the slot-indexed state, `g` the

@@ -162,7 +162,8 @@ struct DeviceState {
   // for small arenas, FOUR per slot for the big ones (kernels_search.hip, launch_linesearch: the pre-rolled rounds use rows
   // 0..3 at stride capacity; what they leave dead is then re-strided for the remaining step sizes of the problems that
   // rejected them all, or -- small active sets -- for all eleven of every active problem).  A launch sees ONE such view:
-  // spec_cap and the three pointers are set per launch by the host (spec_view below), the kernels index as they always did.
+  // spec_cap and the three pointers are set per launch by the host (kernels_search.hip, spec_view); the kernels index through
+  // the one statement of the layout in cost_reduce.hpp (cand_x_at, cand_u_at, cand_parts_at).
   int spec_cap;
   int spec_rows;     // candidates per slot the allocation holds (4 or 11); the allocation's capacity is Bcap
   double2* Xs;       // [rows][K][3][spec_cap]
