@@ -34,41 +34,21 @@ extern "C" int cilqr_clearance_rows_batch(cilqr_handle h, const cilqr_dp_config*
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = h->stream;
   const size_t B = (size_t)sb.batch, K = (size_t)n_knots;
-  // ---- work space of the handle (grown, never shrunk): the count; HOST arrays: one block in, one block out
-  block_layout l_tab, l_out;
-  const slot s_count = l_tab.add(4);
-  const AuditInput in(sb, n_knots, P.rows);
-  const slot s_clear = l_out.add(clearance ? B * K * CILQR_CLEARANCE_FIELDS * 8 : 0);
-  const slot s_near = l_out.add(nearest ? B * K * CILQR_CLEARANCE_FIELDS * 4 : 0);
-  const slot s_min = l_out.add(B * 8), s_knot = l_out.add(B * 4);
-  HIP_TRY(h->cl_tab_host.grow(l_tab.bytes() + 256));
-  HIP_TRY(h->cl_tab.grow(l_tab.bytes() + 256, &h->grown_bytes));
-  if (on_host) {
-    HIP_TRY(h->cl_in.grow(in.l.bytes() + 256, &h->grown_bytes));
-    HIP_TRY(h->cl_out.grow(l_out.bytes() + 256, &h->grown_bytes));
-  }
-  int* d_count = s_count.in<int>(h->cl_tab.as<char>());
-  HIP_TRY(hipMemsetAsync(d_count, 0, 4, st));
-
-  cilqr_scene_batch dv = sb;
-  const double* d_rows = rows;
-  double *d_clear = clearance, *d_min = min_clearance;
-  int *d_near = nearest, *d_knot = min_knot;
-  char* bo = h->cl_out.as<char>();
-  if (on_host) {
-    if (int rc = in.upload(sb, rows, h->cl_in.as<char>(), st, &d_rows, &dv)) return rc;
-    if (clearance) d_clear = s_clear.in<double>(bo);
-    if (nearest) d_near = s_near.in<int>(bo);
-    d_min = s_min.in<double>(bo);
-    d_knot = s_knot.in<int>(bo);
-  }
+  // ---- the count and, HOST arrays, a block in and a block out: the handle's work space (grown, never shrunk)
+  staged_call c(h, h->cl, on_host, st);
+  cilqr_scene_batch dv;
+  const double* d_rows;
+  double *d_clear, *d_min;
+  int *d_near, *d_knot, *d_count;
+  c.counter(&d_count);
+  c.in(rows, B * K * P.rows.fields, &d_rows);
+  c.scenes(sb, &dv);
+  c.out(clearance, B * K * CILQR_CLEARANCE_FIELDS, &d_clear);
+  c.out(nearest, B * K * CILQR_CLEARANCE_FIELDS, &d_near);
+  c.out(min_clearance, B, &d_min);
+  c.out(min_knot, B, &d_knot);
+  if (int rc = c.stage()) return rc;
   launch_clearance(P, dv, d_rows, d_clear, d_near, d_min, d_knot, d_count, st);
   HIP_TRY(hipGetLastError());
-  if (on_host) {
-    if (int rc = copy_out(clearance, bo, s_clear, st)) return rc;
-    if (int rc = copy_out(nearest, bo, s_near, st)) return rc;
-    if (int rc = copy_out(min_clearance, bo, s_min, st)) return rc;
-    if (int rc = copy_out(min_knot, bo, s_knot, st)) return rc;
-  }
-  return wait_and_fetch_count(d_count, s_count.in<int>(h->cl_tab_host.as<char>()), st, n_below);
+  return c.finish(n_below);
 }

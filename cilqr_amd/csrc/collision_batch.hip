@@ -34,46 +34,21 @@ extern "C" int cilqr_check_collisions_batch(cilqr_handle h, const cilqr_dp_confi
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = h->stream;
   const size_t B = (size_t)sb.batch, K = (size_t)n_knots;
-  // ---- work space of the handle (grown, never shrunk): the table and the count; HOST arrays: one block in, one block out
-  block_layout l_tab, l_out;
-  const slot s_barrier = l_tab.add(barrier.size() * 2 * 8), s_count = l_tab.add(4);
-  const AuditInput in(sb, n_knots, P.rows);
-  const slot s_mask = l_out.add(mask ? B * K : 0), s_first = l_out.add(B * 4), s_nhit = l_out.add(n_hit ? B * 4 : 0);
-  HIP_TRY(h->cc_tab_host.grow(l_tab.bytes() + 256));
-  HIP_TRY(h->cc_tab.grow(l_tab.bytes() + 256, &h->grown_bytes));
-  if (on_host) {
-    HIP_TRY(h->cc_in.grow(in.l.bytes() + 256, &h->grown_bytes));
-    HIP_TRY(h->cc_out.grow(l_out.bytes() + 256, &h->grown_bytes));
-  }
-
-  // ---- table: pinned block -> device (the stream is waited for at the end of every call, so the block is free again)
-  char* th = h->cc_tab_host.as<char>();
-  char* td = h->cc_tab.as<char>();
-  if (s_barrier.bytes) {
-    std::memcpy(th + s_barrier.off, barrier.data(), s_barrier.bytes);
-    HIP_TRY(hipMemcpyAsync(td + s_barrier.off, th + s_barrier.off, s_barrier.bytes, hipMemcpyHostToDevice, st));
-  }
-  P.barrier = s_barrier.in<const double>(td);
-  int* d_count = s_count.in<int>(td);
-  HIP_TRY(hipMemsetAsync(d_count, 0, 4, st));
-
-  cilqr_scene_batch dv = sb;
-  const double* d_rows = rows;
-  uint8_t* d_mask = mask;
-  int *d_first = first_hit, *d_nhit = n_hit;
-  char* bo = h->cc_out.as<char>();
-  if (on_host) {
-    if (int rc = in.upload(sb, rows, h->cc_in.as<char>(), st, &d_rows, &dv)) return rc;
-    if (mask) d_mask = s_mask.in<uint8_t>(bo);
-    d_first = s_first.in<int>(bo);
-    if (n_hit) d_nhit = s_nhit.in<int>(bo);
-  }
+  // ---- the count, the table and, HOST arrays, a block in and a block out: the handle's work space (grown, never shrunk)
+  staged_call c(h, h->cc, on_host, st);
+  cilqr_scene_batch dv;
+  const double* d_rows;
+  uint8_t* d_mask;
+  int *d_first, *d_nhit, *d_count;
+  c.table(reinterpret_cast<const double*>(barrier.data()), barrier.size() * 2, &P.barrier);
+  c.counter(&d_count);
+  c.in(rows, B * K * P.rows.fields, &d_rows);
+  c.scenes(sb, &dv);
+  c.out(mask, B * K, &d_mask);
+  c.out(first_hit, B, &d_first);
+  c.out(n_hit, B, &d_nhit);
+  if (int rc = c.stage()) return rc;
   launch_check_collisions(P, dv, d_rows, d_mask, d_first, d_nhit, d_count, st);
   HIP_TRY(hipGetLastError());
-  if (on_host) {
-    if (int rc = copy_out(mask, bo, s_mask, st)) return rc;
-    if (int rc = copy_out(first_hit, bo, s_first, st)) return rc;
-    if (int rc = copy_out(n_hit, bo, s_nhit, st)) return rc;
-  }
-  return wait_and_fetch_count(d_count, s_count.in<int>(th), st, n_colliding);
+  return c.finish(n_colliding);
 }

@@ -33,48 +33,32 @@ int cilqr_build_corridors(cilqr_handle h, const cilqr_corridor_config* cfg, int3
   const size_t n = (size_t)batch * n_knots;
   CorridorParams cp{cfg->max_diff_x, cfg->max_diff_y, cfg->radius, cfg->max_axis_x, cfg->max_axis_y,
                     cfg->is_multiple_sample ? 6 : 2};
-  // the failure counter and its landing place on the host belong to the handle: a hipMalloc / hipFree per call is a
-  // device-wide synchronisation, i.e. a producer that runs beside solves in flight (other handles, a pool) would wait for
-  // all of them
-  if (h->cor_fail.get() == nullptr) HIP_TRY(h->cor_fail.alloc(256));
-  if (h->cor_fail_host.get() == nullptr) HIP_TRY(h->cor_fail_host.alloc(64));
   if (h->cor_done.get() == nullptr) HIP_TRY(h->cor_done.create());
-  int* t_fail = h->cor_fail.as<int>();
   if (n_failed) *n_failed = 0;   // what a call that fails from here on reports
   // (a producer beside solves in flight -- bench.py: end_to_end -- runs on the handle's own stream at normal priority: on a
   // low-priority stream the call took 25 ms instead of 16.5 and the pipeline lost 1.5 %, r06 log 7)
   hipStream_t cst = h->stream;
-  const double *d_knots = knots, *d_pts = points;
-  const int* d_cnt = point_count;
-  double *d_cor = corridor, *d_poly = polygons;
-  int* d_ccnt = corridor_count;
-  HIP_TRY(hipMemsetAsync(t_fail, 0, 4, cst));
-  // HOST arrays: one block in, one block out, both of this call alone
-  const bool on_host = memory == CILQR_MEM_HOST;
-  block_layout l_in, l_out;
-  const slot s_knots = l_in.add(n * 3 * 8), s_pts = l_in.add(n * (size_t)max_points * 2 * 8), s_cnt = l_in.add(n * 4);
-  const slot s_cor = l_out.add(n * (size_t)cmax * 3 * 8), s_ccnt = l_out.add(n * 4);
-  const slot s_poly = l_out.add(polygons ? n * (size_t)cmax * 2 * 8 : 0);
-  dev_mem t_in, t_out;
-  if (on_host) {
-    HIP_TRY(t_in.alloc(l_in.bytes() + 256));
-    HIP_TRY(t_out.alloc(l_out.bytes() + 256));
-    if (int rc = copy_in(t_in.get(), s_knots, knots, cst)) return rc;
-    if (int rc = copy_in(t_in.get(), s_pts, points, cst)) return rc;
-    if (int rc = copy_in(t_in.get(), s_cnt, point_count, cst)) return rc;
-    d_knots = s_knots.in<const double>(t_in.get()); d_pts = s_pts.in<const double>(t_in.get());
-    d_cnt = s_cnt.in<const int>(t_in.get());
-    d_cor = s_cor.in<double>(t_out.get()); d_ccnt = s_ccnt.in<int>(t_out.get());
-    if (polygons) d_poly = s_poly.in<double>(t_out.get());
-  }
+  // The failure count and its landing place on the host belong to the handle: a hipMalloc / hipFree per call is a
+  // device-wide synchronisation, i.e. a producer that runs beside solves in flight (other handles, a pool) would wait for
+  // all of them.  HOST arrays: one block in, one block out, both of this call alone.
+  call_blocks own;
+  staged_call c(h, h->cor, memory == CILQR_MEM_HOST, cst);
+  c.io_blocks(own);
+  const double *d_knots, *d_pts;
+  const int* d_cnt;
+  double *d_cor, *d_poly;
+  int *d_ccnt, *t_fail;
+  c.counter(&t_fail);
+  c.in(knots, n * 3, &d_knots);
+  c.in(points, n * max_points * 2, &d_pts);
+  c.in(point_count, n, &d_cnt);
+  c.out(corridor, n * cmax * 3, &d_cor);
+  c.out(corridor_count, n, &d_ccnt);
+  c.out(polygons, n * cmax * 2, &d_poly);
+  if (int rc = c.stage()) return rc;
   launch_build_corridors((int)n, cp, d_knots, d_pts, d_cnt, max_points, d_cor, d_ccnt, cmax, t_fail, d_poly, cst);
   HIP_TRY(hipGetLastError());
-  if (on_host) {
-    if (int rc = copy_out(corridor, t_out.get(), s_cor, cst)) return rc;
-    if (int rc = copy_out(corridor_count, t_out.get(), s_ccnt, cst)) return rc;
-    if (int rc = copy_out(polygons, t_out.get(), s_poly, cst)) return rc;
-  }
-  HIP_TRY(hipMemcpyAsync(h->cor_fail_host.get(), t_fail, 4, hipMemcpyDeviceToHost, cst));
+  if (int rc = c.fetch()) return rc;
   // a large batch is milliseconds of kernel time: the caller's thread naps through it instead of spinning (it usually has
   // solves in flight whose worker threads want the cores); a small one is waited for the short way
   if (n >= (size_t)1 << 18) {
@@ -83,7 +67,7 @@ int cilqr_build_corridors(cilqr_handle h, const cilqr_corridor_config* cfg, int3
   } else {
     HIP_TRY(hipStreamSynchronize(cst));
   }
-  if (n_failed) *n_failed = *h->cor_fail_host.as<int>();
+  if (n_failed) *n_failed = c.count();
   return CILQR_OK;
 }
 

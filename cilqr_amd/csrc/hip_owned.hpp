@@ -59,6 +59,14 @@ class hip_mem {
 using dev_mem = hip_mem<false>;
 using pinned_mem = hip_mem<true>;
 
+// The blocks of ONE entry point that takes HOST or DEVICE arrays (staging.hpp: staged_call): the tables it builds on the
+// host on their way to the device, with the landing place of its count; their device twin, with the count and any scratch
+// behind them; the staging of HOST inputs and of HOST outputs.  All grow to the largest call and never shrink.
+struct call_blocks {
+  pinned_mem tab_host;
+  dev_mem tab, in, out;
+};
+
 // A hipEvent_t or hipStream_t.
 template <typename H, hipError_t (*Destroy)(H)>
 class hip_handle {

@@ -6,7 +6,7 @@
 #include <vector>
 
 #include "../../include/cilqr/constraint_margins.hpp"
-#include "audit_batch.hpp"
+#include "scene_batch.hpp"
 #include "margins.hpp"
 
 using namespace cilqr;
@@ -99,7 +99,6 @@ extern "C" int cilqr_constraint_margins_batch(cilqr_handle h, const cilqr_proble
   std::vector<LaneGroup> groups;
   if (int rc = check_margin_call(in, layout, rows, min_margin, min_knot, tol, violated, h->cmax, h->smax, &groups)) return rc;
   if (solves_in_flight(h)) return CILQR_ERR_STATE;
-  const bool on_host = in->memory == CILQR_MEM_HOST;
 
   MarginParams P;
   std::memset(&P, 0, sizeof(P));
@@ -118,68 +117,35 @@ extern "C" int cilqr_constraint_margins_batch(cilqr_handle h, const cilqr_proble
     n_left += (size_t)g.nl;
     n_right += (size_t)g.nr;
   }
-  // ---- work space of the handle (grown, never shrunk): the count and the lane tables (raw on their way in, prepared);
-  // HOST arrays: one block in, one block out
-  block_layout l_tab, l_in, l_out;
-  const slot s_count = l_tab.add(4);
-  const slot s_left = l_tab.add(n_left * CILQR_LANE_FIELDS * 8), s_right = l_tab.add(n_right * CILQR_LANE_FIELDS * 8);
-  const size_t tab_host_bytes = l_tab.bytes();   // what travels: the pinned block ends here
-  const slot s_prepared = l_tab.add((n_left + n_right) * kLaneFields * 8);
-  const slot s_rows = l_in.add(B * K * F * 8), s_cor = l_in.add(B * K * C * 3 * 8), s_cnt = l_in.add(B * K * 4);
-  const slot s_marg = l_out.add(margins ? B * K * CILQR_MARGIN_FIELDS * 8 : 0);
-  const slot s_which = l_out.add(which ? B * K * CILQR_MARGIN_WHICH_FIELDS * 4 : 0);
-  const slot s_min = l_out.add(B * CILQR_MARGIN_FIELDS * 8), s_knot = l_out.add(B * CILQR_MARGIN_FIELDS * 4);
-  const slot s_viol = l_out.add(B * 4);
-  HIP_TRY(h->mg_tab_host.grow(tab_host_bytes + 256));
-  HIP_TRY(h->mg_tab.grow(l_tab.bytes() + 256, &h->grown_bytes));
-  if (on_host) {
-    HIP_TRY(h->mg_in.grow(l_in.bytes() + 256, &h->grown_bytes));
-    HIP_TRY(h->mg_out.grow(l_out.bytes() + 256, &h->grown_bytes));
-  }
-  char* th = h->mg_tab_host.as<char>();
-  char* td = h->mg_tab.as<char>();
-  // pinned block -> device (the stream is waited for at the end of every call, so the block is free again)
-  std::memcpy(th + s_left.off, in->left_lane, s_left.bytes);
-  std::memcpy(th + s_right.off, in->right_lane, s_right.bytes);
-  std::memset(th + s_count.off, 0, 4);
-  HIP_TRY(hipMemcpyAsync(td, th, tab_host_bytes, hipMemcpyHostToDevice, st));
-  int* d_count = s_count.in<int>(td);
-
-  const double *d_rows = rows, *d_cor = in->corridor;
-  const int* d_cnt = in->corridor_count;
-  double *d_marg = margins, *d_min = min_margin;
-  int *d_which = which, *d_knot = min_knot;
-  uint32_t* d_viol = violated;
-  char* bo = h->mg_out.as<char>();
-  if (on_host) {
-    char* bi = h->mg_in.as<char>();
-    if (int rc = copy_in(bi, s_rows, rows, st)) return rc;
-    if (int rc = copy_in(bi, s_cor, in->corridor, st)) return rc;
-    if (int rc = copy_in(bi, s_cnt, in->corridor_count, st)) return rc;
-    d_rows = s_rows.in<const double>(bi);
-    d_cor = s_cor.in<const double>(bi);
-    d_cnt = s_cnt.in<const int>(bi);
-    if (margins) d_marg = s_marg.in<double>(bo);
-    if (which) d_which = s_which.in<int>(bo);
-    d_min = s_min.in<double>(bo);
-    d_knot = s_knot.in<int>(bo);
-    d_viol = s_viol.in<uint32_t>(bo);
-  }
+  // ---- the count, the lane tables (raw on their way in, prepared behind them) and, HOST arrays, a block in and a block
+  // out: the handle's work space (grown, never shrunk)
+  staged_call c(h, h->mg, in->memory == CILQR_MEM_HOST, st);
+  const double *d_rows, *d_cor, *d_left, *d_right;
+  const int* d_cnt;
+  double *d_marg, *d_min, *d_prepared;
+  int *d_which, *d_knot, *d_count;
+  uint32_t* d_viol;
+  c.counter(&d_count);
+  c.table(in->left_lane, n_left * CILQR_LANE_FIELDS, &d_left);
+  c.table(in->right_lane, n_right * CILQR_LANE_FIELDS, &d_right);
+  c.scratch((n_left + n_right) * kLaneFields, &d_prepared);
+  c.in(rows, B * K * F, &d_rows);
+  c.in(in->corridor, B * K * C * 3, &d_cor);
+  c.in(in->corridor_count, B * K, &d_cnt);
+  c.out(margins, B * K * CILQR_MARGIN_FIELDS, &d_marg);
+  c.out(which, B * K * CILQR_MARGIN_WHICH_FIELDS, &d_which);
+  c.out(min_margin, B * CILQR_MARGIN_FIELDS, &d_min);
+  c.out(min_knot, B * CILQR_MARGIN_FIELDS, &d_knot);
+  c.out(violated, B, &d_viol);
+  if (int rc = c.stage()) return rc;
   for (const LaneGroup& g : groups) {
     if (g.b1 == g.b0) continue;
-    double* prepared = s_prepared.in<double>(td) + (g.l0 + g.r0) * kLaneFields;
-    launch_margin_lanes(s_left.in<const double>(td) + g.l0 * CILQR_LANE_FIELDS, g.nl,
-                        s_right.in<const double>(td) + g.r0 * CILQR_LANE_FIELDS, g.nr, P.p.shrink_lane, prepared, st);
+    double* prepared = d_prepared + (g.l0 + g.r0) * kLaneFields;
+    launch_margin_lanes(d_left + g.l0 * CILQR_LANE_FIELDS, g.nl, d_right + g.r0 * CILQR_LANE_FIELDS, g.nr, P.p.shrink_lane,
+                        prepared, st);
     const MarginGroup G{g.b0, g.b1 - g.b0, g.nl, g.nr, prepared};
     launch_margins(P, G, d_rows, d_cor, d_cnt, d_marg, d_which, d_min, d_knot, d_viol, d_count, st);
   }
   HIP_TRY(hipGetLastError());
-  if (on_host) {
-    if (int rc = copy_out(margins, bo, s_marg, st)) return rc;
-    if (int rc = copy_out(which, bo, s_which, st)) return rc;
-    if (int rc = copy_out(min_margin, bo, s_min, st)) return rc;
-    if (int rc = copy_out(min_knot, bo, s_knot, st)) return rc;
-    if (int rc = copy_out(violated, bo, s_viol, st)) return rc;
-  }
-  return wait_and_fetch_count(d_count, s_count.in<int>(th), st, n_violating);
+  return c.finish(n_violating);
 }

@@ -79,13 +79,9 @@ int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const 
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = h->stream;
   const size_t B = (size_t)sb.batch, K = (size_t)n_knots;
-  // ---- work space of the handle (grown, never shrunk: nothing is allocated once the largest call has been seen)
-  cilqr::block_layout l_tab, l_placed, l_in, l_out;
-  const cilqr::slot s_center = l_tab.add((size_t)sb.n_center * 7 * 8), s_barrier = l_tab.add(barrier.size() * 2 * 8);
-  HIP_TRY(h->dp_tab_host.grow(l_tab.bytes() + 256));
-  HIP_TRY(h->dp_tab.grow(l_tab.bytes() + 256, &h->grown_bytes));
-  if (h->dp_fail.get() == nullptr) HIP_TRY(h->dp_fail.alloc(256));
-  if (h->dp_fail_host.get() == nullptr) HIP_TRY(h->dp_fail_host.alloc(64));
+  // ---- work space of the handle (grown, never shrunk: nothing is allocated once the largest call has been seen): the
+  // placed polygons of a chunk; the count, the road's tables and, HOST arrays, a block in and a block out
+  cilqr::block_layout l_placed;
   const size_t rec = 4 + 2 * (size_t)sb.max_vertices;
   const size_t per_scene = (size_t)P.nq * sb.max_dynamic * (rec * 8 + 4);
   size_t chunk = B;
@@ -93,45 +89,23 @@ int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const 
   const cilqr::slot s_placed = l_placed.add(chunk * (size_t)P.nq * sb.max_dynamic * rec * 8);
   const cilqr::slot s_placed_n = l_placed.add(chunk * (size_t)P.nq * sb.max_dynamic * 4);
   HIP_TRY(h->dp_placed.grow(l_placed.bytes() + 256, &h->grown_bytes));
-  // HOST arrays: one block in, one block out
-  const cilqr::slot s_start = l_in.add(B * 3 * 8);
-  const cilqr::SceneImage im(l_in, sb);
-  const cilqr::slot s_c9 = l_out.add(coarse9 ? B * K * CILQR_COARSE_FIELDS * 8 : 0), s_c6 = l_out.add(coarse6 ? B * K * 6 * 8 : 0);
-  const cilqr::slot s_k3 = l_out.add(knots3 ? B * K * 3 * 8 : 0), s_stn = l_out.add(station ? B * K * 8 : 0);
-  const cilqr::slot s_found = l_out.add(B * 4);
-  if (on_host) {
-    HIP_TRY(h->dp_in.grow(l_in.bytes() + 256, &h->grown_bytes));
-    HIP_TRY(h->dp_out.grow(l_out.bytes() + 256, &h->grown_bytes));
-  }
-
-  // ---- tables: pinned block -> device (the stream is waited for at the end of every call, so the block is free again)
-  char* th = h->dp_tab_host.as<char>();
-  char* td = h->dp_tab.as<char>();
-  std::memcpy(th, sb.center, s_center.bytes);
-  if (s_barrier.bytes) std::memcpy(th + s_barrier.off, barrier.data(), s_barrier.bytes);
+  cilqr::staged_call c(h, h->dp, on_host, st);
+  cilqr_scene_batch dv;
+  const double* d_start;
+  double *d_c9, *d_c6, *d_k3, *d_stn;
+  int *d_found, *d_fail;
   static_assert(sizeof(cilqr::DpPoint2) == 16, "the barrier table travels as [n][2] doubles");
-  HIP_TRY(hipMemcpyAsync(td, th, s_barrier.off + s_barrier.bytes, hipMemcpyHostToDevice, st));
-  P.center = s_center.in<const double>(td);
-  P.barrier = s_barrier.in<const double>(td);
-  int* d_fail = h->dp_fail.as<int>();
-  HIP_TRY(hipMemsetAsync(d_fail, 0, 4, st));
-
-  cilqr_scene_batch dv = sb;
-  const double* d_start = start3;
-  double *d_c9 = coarse9, *d_c6 = coarse6, *d_k3 = knots3, *d_stn = station;
-  int* d_found = found;
-  char* bo = h->dp_out.as<char>();
-  if (on_host) {
-    char* bi = h->dp_in.as<char>();
-    if (int rc = cilqr::copy_in(bi, s_start, start3, st)) return rc;
-    if (int rc = im.upload(sb, bi, st, &dv)) return rc;
-    d_start = s_start.in<const double>(bi);
-    if (coarse9) d_c9 = s_c9.in<double>(bo);
-    if (coarse6) d_c6 = s_c6.in<double>(bo);
-    if (knots3) d_k3 = s_k3.in<double>(bo);
-    if (station) d_stn = s_stn.in<double>(bo);
-    d_found = s_found.in<int>(bo);
-  }
+  c.table(sb.center, (size_t)sb.n_center * 7, &P.center);
+  c.table(reinterpret_cast<const double*>(barrier.data()), barrier.size() * 2, &P.barrier);
+  c.counter(&d_fail);
+  c.in(start3, B * 3, &d_start);
+  c.scenes(sb, &dv);
+  c.out(coarse9, B * K * CILQR_COARSE_FIELDS, &d_c9);
+  c.out(coarse6, B * K * 6, &d_c6);
+  c.out(knots3, B * K * 3, &d_k3);
+  c.out(station, B * K, &d_stn);
+  c.out(found, B, &d_found);
+  if (int rc = c.stage()) return rc;
 
   double* placed = s_placed.in<double>(h->dp_placed.get());
   int* placed_n = s_placed_n.in<int>(h->dp_placed.get());
@@ -141,16 +115,7 @@ int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const 
     cilqr::launch_dp_plan(P, dv, (int)first, n, d_start, placed, placed_n, d_c9, d_c6, d_k3, d_stn, d_found, d_fail, st);
   }
   HIP_TRY(hipGetLastError());
-  if (on_host) {
-    if (int rc = cilqr::copy_out(coarse9, bo, s_c9, st)) return rc;
-    if (int rc = cilqr::copy_out(coarse6, bo, s_c6, st)) return rc;
-    if (int rc = cilqr::copy_out(knots3, bo, s_k3, st)) return rc;
-    if (int rc = cilqr::copy_out(station, bo, s_stn, st)) return rc;
-    if (int rc = cilqr::copy_out(found, bo, s_found, st)) return rc;
-  }
-  HIP_TRY(hipMemcpyAsync(h->dp_fail_host.get(), d_fail, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));   // this stream alone: solves on other handles go on
-  if (n_not_found) *n_not_found = *h->dp_fail_host.as<int>();
+  if (int rc = c.finish(n_not_found)) return rc;
   if (times_out)   // k_dp_plan's time column: knots past the path's samples stay zero
     for (int k = 0; k < n_knots; ++k) times_out[k] = k < P.nq ? P.delta_t * k : 0.0;
   return CILQR_OK;

@@ -51,26 +51,15 @@ extern "C" int cilqr_resample_rows_batch(cilqr_handle h, int32_t batch, int32_t 
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = h->stream;
   const size_t B = (size_t)batch, K = (size_t)n_knots, M = (size_t)n_queries, F = (size_t)P.fields;
-  const double *d_rows = rows, *d_queries = queries;
-  double* d_out = out;
-  const bool on_host = memory == CILQR_MEM_HOST;
-  block_layout l_in, l_out;
-  const slot s_rows = l_in.add(B * K * F * 8), s_queries = l_in.add((per_problem ? B : 1) * M * 8);
-  const slot s_out = l_out.add(B * M * F * 8);
-  if (on_host) {   // work space of the handle (grown, never shrunk): one block in, one block out
-    HIP_TRY(h->rs_in.grow(l_in.bytes() + 256, &h->grown_bytes));
-    HIP_TRY(h->rs_out.grow(l_out.bytes() + 256, &h->grown_bytes));
-    char* bi = h->rs_in.as<char>();
-    if (int rc = copy_in(bi, s_rows, rows, st)) return rc;
-    if (int rc = copy_in(bi, s_queries, queries, st)) return rc;
-    d_rows = s_rows.in<const double>(bi);
-    d_queries = s_queries.in<const double>(bi);
-    d_out = s_out.in<double>(h->rs_out.as<char>());
-  }
+  // HOST arrays: a block in and a block out of the handle's work space (grown, never shrunk)
+  staged_call c(h, h->rs, memory == CILQR_MEM_HOST, st);
+  const double *d_rows, *d_queries;
+  double* d_out;
+  c.in(rows, B * K * F, &d_rows);
+  c.in(queries, (per_problem ? B : 1) * M, &d_queries);
+  c.out(out, B * M * F, &d_out);
+  if (int rc = c.stage()) return rc;
   launch_resample(P, d_rows, d_queries, d_out, st);
   HIP_TRY(hipGetLastError());
-  if (on_host)
-    if (int rc = copy_out(out, h->rs_out.as<char>(), s_out, st)) return rc;
-  HIP_TRY(hipStreamSynchronize(st));   // this stream alone: solves on other handles go on
-  return CILQR_OK;
+  return c.finish();
 }

@@ -1,7 +1,9 @@
 // Private to cilqr_amd/csrc: what the entry points that take a cilqr_scene_batch (planner_batch.hip, scene_pipeline.hip,
 // collision_batch.hip, clearance_batch.hip; frenet_batch.hip and resample_batch.hip for the checks on the handle) share --
-// the checks on the batch, in the order every one of them makes them, and the device image of a HOST batch -- and what
-// they and the calls on one scene (host_planner.hip) hand to the host planner's classes: its configuration and its road.
+// the checks on the batch, in the order every one of them makes them -- and what they and the calls on one scene
+// (host_planner.hip) hand to the host planner's classes: its configuration and its road.  The six arrays of a batch reach
+// the device through staged_call::scenes (staging.hpp); SceneImage lays them out for the two pipelines, which keep them in
+// a work block of their own beside their intermediates.
 #pragma once
 #include <array>
 #include <vector>
@@ -67,14 +69,14 @@ inline bool solves_in_flight(cilqr_solver* h) {
   return h->job_count != 0;   // submitted solves not collected yet (cilqr_wait)
 }
 
-// The device image of a HOST scene batch: its six per-problem arrays as six slots of the caller's block.
+// The six per-problem arrays of a scene batch as six slots of the caller's block (scene_pipeline.hip: a HOST batch on its
+// way to the device; carry_pipeline.hip: the gathered scenes of a chunk).
 struct SceneImage {
-  slot sp, sc, dp, dpc, dt, dtc;
+  slot sp, sc, dp, dpc, dt, dtc;   // named: carry_pipeline.hip gathers into each of them
   SceneImage(block_layout& L, const cilqr_scene_batch& sb) {
-    const size_t B = (size_t)sb.batch;
-    sp = L.add(B * sb.max_static * sb.max_vertices * 2 * 8); sc = L.add(B * sb.max_static * 4);
-    dp = L.add(B * sb.max_dynamic * sb.max_vertices * 2 * 8); dpc = L.add(B * sb.max_dynamic * 4);
-    dt = L.add(B * sb.max_dynamic * sb.max_samples * 4 * 8); dtc = L.add(B * sb.max_dynamic * 4);
+    slot* const s[] = {&sp, &sc, &dp, &dpc, &dt, &dtc};   // the order of scene_arrays, which states the sizes
+    int i = 0;
+    scene_arrays(sb, [&](auto member, size_t n) { *s[i++] = L.add(n * sizeof(*(sb.*member))); });
   }
   // the arrays of `sb` (HOST) into `block`; `view` = the batch with its arrays there
   int upload(const cilqr_scene_batch& sb, char* block, hipStream_t st, cilqr_scene_batch* view) const {

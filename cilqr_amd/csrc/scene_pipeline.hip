@@ -35,9 +35,9 @@ const HostBlock kHost;
 // the knot times: pinned block -> device table (the stream is waited for at the end of every call, so the block is free again)
 int upload_times(cilqr_solver* h, const double* times, int n_knots, hipStream_t st) {
   HIP_TRY(h->sp_host.grow(kHost.l.bytes()));
-  HIP_TRY(h->sp_tab.grow(kHost.times.bytes, &h->grown_bytes));
+  HIP_TRY(h->sp.tab.grow(kHost.times.bytes, &h->grown_bytes));
   std::memcpy(h->sp_host.get(), times, (size_t)n_knots * 8);
-  HIP_TRY(hipMemcpyAsync(h->sp_tab.get(), h->sp_host.get(), (size_t)n_knots * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h->sp.tab.get(), h->sp_host.get(), (size_t)n_knots * 8, hipMemcpyHostToDevice, st));
   return CILQR_OK;
 }
 
@@ -61,32 +61,22 @@ extern "C" int cilqr_scene_points_batch(cilqr_handle h, const cilqr_scene_batch*
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = h->stream;
   const size_t B = (size_t)sb.batch, K = (size_t)n_knots;
-  if (int rc = upload_times(h, knot_times, n_knots, st)) return rc;
   const ScenePointsParams P = points_params(sb, n_knots, max_points, per_vertex);
-  const double* d_times = h->sp_tab.as<double>();
-  if (!on_host) {
-    launch_scene_points(P, sb, 0, sb.batch, d_times, points, point_count, scene_ok, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));   // this stream alone: solves on other handles go on
-    return CILQR_OK;
-  }
-  // HOST arrays: the scenes in, the caller's points in as well (what lies behind point_count stays as it is), all out
-  block_layout l_in, l_out;
-  const SceneImage im(l_in, sb);
-  const slot s_pts = l_out.add(B * K * (size_t)max_points * 2 * 8), s_cnt = l_out.add(B * K * 4), s_ok = l_out.add(B * 4);
-  HIP_TRY(h->sp_in.grow(l_in.bytes() + 256, &h->grown_bytes));
-  HIP_TRY(h->sp_out.grow(l_out.bytes() + 256, &h->grown_bytes));
+  // the knot times and, HOST arrays, a block in and a block out: the handle's work space (grown, never shrunk)
+  staged_call c(h, h->sp, on_host, st);
   cilqr_scene_batch dv;
-  if (int rc = im.upload(sb, h->sp_in.as<char>(), st, &dv)) return rc;
-  char* bo = h->sp_out.as<char>();
-  if (int rc = copy_in(bo, s_pts, points, st)) return rc;
-  launch_scene_points(P, dv, 0, sb.batch, d_times, s_pts.in<double>(bo), s_cnt.in<int>(bo), s_ok.in<int>(bo), st);
+  const double* d_times;
+  double* d_pts;
+  int *d_cnt, *d_ok;
+  c.table(knot_times, K, &d_times);
+  c.scenes(sb, &dv);
+  c.inout(points, B * K * max_points * 2, &d_pts);   // what lies behind point_count stays as it is
+  c.out(point_count, B * K, &d_cnt);
+  c.out(scene_ok, B, &d_ok);
+  if (int rc = c.stage()) return rc;
+  launch_scene_points(P, dv, 0, sb.batch, d_times, d_pts, d_cnt, d_ok, st);
   HIP_TRY(hipGetLastError());
-  if (int rc = copy_out(points, bo, s_pts, st)) return rc;
-  if (int rc = copy_out(point_count, bo, s_cnt, st)) return rc;
-  if (int rc = copy_out(scene_ok, bo, s_ok, st)) return rc;
-  HIP_TRY(hipStreamSynchronize(st));
-  return CILQR_OK;
+  return c.finish();
 }
 
 // the body of the pipeline entry points; `warm` NULL: the plain call (cilqr_solve_batch_warm with NULL is cilqr_solve_batch);
@@ -207,7 +197,7 @@ int cilqr::plan_scenes(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilq
   int* d_pcnt = s_pcnt.in<int>(h->ps_points.get());
   for (size_t first = 0; first < B; first += chunk) {
     const int n = (int)std::min(chunk, B - first);
-    launch_scene_points(P, dv, (int)first, n, h->sp_tab.as<double>(), d_pts, d_pcnt, nullptr, st);
+    launch_scene_points(P, dv, (int)first, n, h->sp.tab.as<double>(), d_pts, d_pcnt, nullptr, st);
     HIP_TRY(hipGetLastError());
     if (int rc = cilqr_build_corridors(h, corridor_cfg, n, n_knots, d_k3 + first * K * 3, d_pts, d_pcnt, max_points,
                                        d_cor + first * K * cmax * 3, d_ccnt + first * K, (int32_t)cmax, CILQR_MEM_DEVICE,

@@ -3,7 +3,7 @@
 #include <climits>
 #include <cmath>
 
-#include "audit_batch.hpp"
+#include "scene_batch.hpp"
 #include "scene_window.hpp"
 
 using namespace cilqr;
@@ -36,44 +36,21 @@ extern "C" int cilqr_window_scenes_batch(cilqr_handle h, const cilqr_scene_batch
 
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = h->stream;
-  // ---- work space of the handle (grown, never shrunk): the count; HOST arrays: a block in, a block out
-  block_layout l_tab, l_in, l_out;
-  const slot s_count = l_tab.add(4);
-  const slot s_src = l_in.add(B * D * (size_t)sb.max_samples * 4 * 8), s_scnt = l_in.add(B * D * 4), s_t0 = l_in.add(B * 8);
-  const slot s_win = l_out.add(B * D * (size_t)out_samples * 4 * 8), s_wcnt = l_out.add(B * D * 4), s_ok = l_out.add(B * 4);
-  HIP_TRY(h->sw_tab_host.grow(l_tab.bytes() + 256));
-  HIP_TRY(h->sw_tab.grow(l_tab.bytes() + 256, &h->grown_bytes));
-  if (on_host) {
-    HIP_TRY(h->sw_in.grow(l_in.bytes() + 256, &h->grown_bytes));
-    HIP_TRY(h->sw_out.grow(l_out.bytes() + 256, &h->grown_bytes));
-  }
-  int* d_count = s_count.in<int>(h->sw_tab.as<char>());
-  HIP_TRY(hipMemsetAsync(d_count, 0, 4, st));
-
-  const double *d_src = sb.dynamic_trajectories, *d_t0 = t0;
-  const int* d_scnt = sb.dynamic_trajectory_counts;
-  double* d_win = trajectories;
-  int *d_wcnt = counts, *d_ok = ok;
-  char* bo = h->sw_out.as<char>();
-  if (on_host) {   // the caller's windows go in as well: what lies behind a count stays as it is
-    char* bi = h->sw_in.as<char>();
-    if (int rc = copy_in(bi, s_src, sb.dynamic_trajectories, st)) return rc;
-    if (int rc = copy_in(bi, s_scnt, sb.dynamic_trajectory_counts, st)) return rc;
-    if (int rc = copy_in(bi, s_t0, t0, st)) return rc;
-    if (int rc = copy_in(bo, s_win, trajectories, st)) return rc;
-    d_src = s_src.in<const double>(bi);
-    d_scnt = s_scnt.in<const int>(bi);
-    d_t0 = s_t0.in<const double>(bi);
-    d_win = s_win.in<double>(bo);
-    d_wcnt = s_wcnt.in<int>(bo);
-    d_ok = s_ok.in<int>(bo);
-  }
+  // ---- the count and, HOST arrays, a block in and a block out: the handle's work space (grown, never shrunk)
+  staged_call c(h, h->sw, on_host, st);
+  const double *d_src, *d_t0;
+  const int* d_scnt;
+  double* d_win;
+  int *d_wcnt, *d_ok, *d_count;
+  c.counter(&d_count);
+  c.in(sb.dynamic_trajectories, B * D * sb.max_samples * 4, &d_src);
+  c.in(sb.dynamic_trajectory_counts, B * D, &d_scnt);
+  c.in(t0, B, &d_t0);
+  c.inout(trajectories, B * D * out_samples * 4, &d_win);   // what lies behind a count stays as it is
+  c.out(counts, B * D, &d_wcnt);
+  c.out(ok, B, &d_ok);
+  if (int rc = c.stage()) return rc;
   launch_scene_window(P, d_src, d_scnt, d_t0, d_win, d_wcnt, d_ok, d_count, st);
   HIP_TRY(hipGetLastError());
-  if (on_host) {
-    if (int rc = copy_out(trajectories, bo, s_win, st)) return rc;
-    if (int rc = copy_out(counts, bo, s_wcnt, st)) return rc;
-    if (int rc = copy_out(ok, bo, s_ok, st)) return rc;
-  }
-  return wait_and_fetch_count(d_count, s_count.in<int>(h->sw_tab_host.as<char>()), st, n_overflow);
+  return c.finish(n_overflow);
 }

@@ -243,55 +243,38 @@ struct cilqr_solver {
   int profiling_level = 1;
   cilqr_profile prof;         // of the last solve that completed
   cilqr_comm* comm = nullptr;   // multi-GPU results gather (cilqr_comm_create)
-  cilqr::dev_mem cor_fail;        // cilqr_build_corridors (corridor_batch.hip): failure counter on the device, where it lands on the host, its event
-  cilqr::pinned_mem cor_fail_host;
-  cilqr::hip_event cor_done;
+  // The entry points that take HOST or DEVICE arrays (staging.hpp) have a set of blocks each: one of them calls another while
+  // its own blocks hold live data (scene_pipeline.hip, carry_pipeline.hip).  What a call needs besides is named beside its set.
+  cilqr::call_blocks cor;         // cilqr_build_corridors (corridor_batch.hip): the failure count alone -- its HOST arrays go
+  cilqr::hip_event cor_done;      // through blocks of the call's own -- and the event a large call naps on
   cilqr::TrackerParams tracker;   // CILQR_INIT_TRACKER
-  // cilqr_dp_plan_batch (planner_batch.hip): blocks that grow to the largest call -- the road's tables on their way to the
-  // device, the placed dynamic polygons of a chunk of scenes, the staging of HOST arrays -- and the count's way back
-  cilqr::pinned_mem dp_tab_host;
-  cilqr::dev_mem dp_tab, dp_placed, dp_in, dp_out;
-  cilqr::dev_mem dp_fail;
-  cilqr::pinned_mem dp_fail_host;
-  // cilqr_scene_points_batch / cilqr_plan_scenes_batch (scene_pipeline.hip), grown likewise: the knot times on their way to
-  // the device and the outcome counts' way back, the staging of HOST scenes and HOST outputs, the intermediates of the
-  // pipeline (coarse trajectory, corridors, ...) and the obstacle points of the chunk of scenes in flight
+  cilqr::call_blocks dp;          // cilqr_dp_plan_batch (planner_batch.hip): the road's tables
+  cilqr::dev_mem dp_placed;       // ... and the placed dynamic polygons of a chunk of scenes
+  // cilqr_scene_points_batch and cilqr_plan_scenes_batch (scene_pipeline.hip).  Both read the knot times from sp.tab, and
+  // each sends them there its own way: the call through sp.tab_host like any table, the pipeline through sp_host, which
+  // also lands its two outcome counts (upload_times), so sp.tab is as large as the larger of the two asks.  Then the
+  // pipeline's intermediates (coarse trajectory, corridors, ..., HOST scenes and outputs) and the obstacle points of the
+  // chunk of scenes in flight.
+  cilqr::call_blocks sp;
   cilqr::pinned_mem sp_host;
-  cilqr::dev_mem sp_tab, sp_in, sp_out, ps_work, ps_points;
+  cilqr::dev_mem ps_work, ps_points;
   int scene_chunk = 0;            // CILQR_OPT_SCENE_CHUNK
-  // cilqr_check_collisions_batch (collision_batch.hip), grown likewise: the barrier table on its way to the device with the
-  // count of colliding scenes on its way back, the staging of HOST scenes and rows, of HOST masks and counts
-  cilqr::pinned_mem cc_tab_host;
-  cilqr::dev_mem cc_tab, cc_in, cc_out;
-  // cilqr_resample_rows_batch (resample_batch.hip), grown likewise: the staging of HOST rows and queries, of HOST output rows
-  cilqr::dev_mem rs_in, rs_out;
-  // cilqr_frenet_rows_batch / cilqr_cartesian_points_batch (frenet_batch.hip), grown likewise: the centre line's tables on
-  // their way to the device, the staging of HOST rows / pairs and of HOST results
-  cilqr::pinned_mem fr_tab_host;
-  cilqr::dev_mem fr_tab, fr_in, fr_out;
-  // cilqr_clearance_rows_batch (clearance_batch.hip), grown likewise: the count of scenes below the threshold and its way
-  // back, the staging of HOST scenes and rows, of HOST results
-  cilqr::pinned_mem cl_tab_host;
-  cilqr::dev_mem cl_tab, cl_in, cl_out;
-  // cilqr_constraint_margins_batch (margins_batch.hip), grown likewise: the count of violating problems and the raw lane
-  // tables on their way to the device (the prepared lane rows behind them), the staging of HOST rows, planes and counts,
-  // of HOST results.  Nothing of the staged or solver state is read or written by that call.
-  cilqr::pinned_mem mg_tab_host;
-  cilqr::dev_mem mg_tab, mg_in, mg_out;
-  // cilqr_track_rows_batch (track_batch.hip), grown likewise: the count of failed problems and its way back, the follow
-  // table of the call (track.hpp), the staging of HOST rows and start states, of HOST driven rows and flags
-  cilqr::pinned_mem tk_tab_host;
-  cilqr::dev_mem tk_tab, tk_work, tk_in, tk_out;
-  // cilqr_window_scenes_batch (scene_window_batch.hip), grown likewise: the count of failed scenes and its way back, the
-  // staging of HOST source trajectories, counts and t0, of HOST windows, counts and flags
-  cilqr::pinned_mem sw_tab_host;
-  cilqr::dev_mem sw_tab, sw_in, sw_out;
-  // cilqr_carry_rows_batch (carry_batch.hip), grown likewise: the count of kept trajectories and its way back, the staging
-  // of HOST rows and advances, of HOST coarse trajectories and states; cilqr_plan_scenes_batch_carry (carry_pipeline.hip):
-  // the intermediates of its coarse stage (states, hits, the list, the gathered scenes and their plans), the list's length
+  cilqr::call_blocks cc;          // cilqr_check_collisions_batch (collision_batch.hip): the barrier table
+  cilqr::call_blocks rs;          // cilqr_resample_rows_batch (resample_batch.hip)
+  cilqr::call_blocks fr;          // cilqr_frenet_rows_batch / cilqr_cartesian_points_batch (frenet_batch.hip): the centre line
+  cilqr::call_blocks cl;          // cilqr_clearance_rows_batch (clearance_batch.hip)
+  // cilqr_constraint_margins_batch (margins_batch.hip): the raw lane tables, the prepared lane rows behind them.  Nothing of
+  // the staged or solver state is read or written by that call.
+  cilqr::call_blocks mg;
+  cilqr::call_blocks tk;          // cilqr_track_rows_batch (track_batch.hip)
+  cilqr::dev_mem tk_work;         // ... and the follow table of the call (track.hpp)
+  cilqr::call_blocks sw;          // cilqr_window_scenes_batch (scene_window_batch.hip)
+  // cilqr_carry_rows_batch (carry_batch.hip); cilqr_plan_scenes_batch_carry (carry_pipeline.hip): the intermediates of its
+  // coarse stage (states, hits, the list, HOST rows and advances), the gathered scenes and their plans, the list's length
   // on its way back
-  cilqr::pinned_mem cy_tab_host, cy_sel_host;
-  cilqr::dev_mem cy_tab, cy_in, cy_out, cy_work, cy_chunk;
+  cilqr::call_blocks cy;
+  cilqr::pinned_mem cy_sel_host;
+  cilqr::dev_mem cy_work, cy_chunk;
 };
 
 namespace cilqr {

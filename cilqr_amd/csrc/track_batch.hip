@@ -2,7 +2,7 @@
 // the host side of the batched one -- argument checks, the follow table in the handle's work space, staging of HOST arrays,
 // the two launches of kernels_track.hip, the count's way back.
 #include "../../include/cilqr/tracker.hpp"
-#include "audit_batch.hpp"
+#include "scene_batch.hpp"
 #include "track.hpp"
 
 using namespace cilqr;
@@ -57,44 +57,22 @@ extern "C" int cilqr_track_rows_batch(cilqr_handle h, int32_t batch, int32_t lay
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = h->stream;
   const size_t B = (size_t)batch, K = (size_t)n_knots, D = (size_t)n_drive, F = (size_t)P.fields;
-  const bool on_host = memory == CILQR_MEM_HOST;
-  // ---- work space of the handle (grown, never shrunk): the count and the follow table; HOST arrays: a block in, a block out
-  block_layout l_tab, l_work, l_in, l_out;
-  const slot s_count = l_tab.add(4);
-  const slot s_table = l_work.add(follow_table_bytes(batch, n_knots));
-  const slot s_rows = l_in.add(B * K * F * 8), s_start = l_in.add(start6 ? B * 6 * 8 : 0);
-  const slot s_driven = l_out.add(B * D * CILQR_TRAJ_FIELDS * 8), s_ok = l_out.add(B * 4);
-  HIP_TRY(h->tk_tab_host.grow(l_tab.bytes() + 256));
-  HIP_TRY(h->tk_tab.grow(l_tab.bytes() + 256, &h->grown_bytes));
-  HIP_TRY(h->tk_work.grow(l_work.bytes() + 256, &h->grown_bytes));
-  if (on_host) {
-    HIP_TRY(h->tk_in.grow(l_in.bytes() + 256, &h->grown_bytes));
-    HIP_TRY(h->tk_out.grow(l_out.bytes() + 256, &h->grown_bytes));
-  }
-  int* d_count = s_count.in<int>(h->tk_tab.as<char>());
-  HIP_TRY(hipMemsetAsync(d_count, 0, 4, st));
-
-  const double *d_rows = rows, *d_start = start6;
-  double* d_driven = driven;
-  int* d_ok = ok;
-  char* bo = h->tk_out.as<char>();
-  if (on_host) {
-    char* bi = h->tk_in.as<char>();
-    if (int rc = copy_in(bi, s_rows, rows, st)) return rc;
-    if (int rc = copy_in(bi, s_start, start6, st)) return rc;
-    d_rows = s_rows.in<const double>(bi);
-    if (start6) d_start = s_start.in<const double>(bi);
-    d_driven = s_driven.in<double>(bo);
-    d_ok = s_ok.in<int>(bo);
-  }
-  const FollowTable tab = follow_table_in(s_table.in<char>(h->tk_work.as<char>()), batch, n_knots);
+  // ---- the count, the follow table and, HOST arrays, a block in and a block out: the handle's work space (grown, never shrunk)
+  HIP_TRY(h->tk_work.grow(follow_table_bytes(batch, n_knots) + 256, &h->grown_bytes));
+  staged_call c(h, h->tk, memory == CILQR_MEM_HOST, st);
+  const double *d_rows, *d_start;
+  double* d_driven;
+  int *d_ok, *d_count;
+  c.counter(&d_count);
+  c.in(rows, B * K * F, &d_rows);
+  c.in(start6, B * 6, &d_start);
+  c.out(driven, B * D * CILQR_TRAJ_FIELDS, &d_driven);
+  c.out(ok, B, &d_ok);
+  if (int rc = c.stage()) return rc;
+  const FollowTable tab = follow_table_in(h->tk_work.as<char>(), batch, n_knots);
   launch_track_gather(P, d_rows, d_start, tab, st);
   HIP_TRY(hipGetLastError());
   launch_track_rows(P, h->ds.p, h->tracker, tab, d_driven, d_ok, d_count, st);
   HIP_TRY(hipGetLastError());
-  if (on_host) {
-    if (int rc = copy_out(driven, bo, s_driven, st)) return rc;
-    if (int rc = copy_out(ok, bo, s_ok, st)) return rc;
-  }
-  return wait_and_fetch_count(d_count, s_count.in<int>(h->tk_tab_host.as<char>()), st, n_failed);
+  return c.finish(n_failed);
 }
