@@ -110,13 +110,10 @@ int cilqr_multi_solve_warm(cilqr_multi_handle m, const cilqr_problem_batch* in, 
                            cilqr_solution_batch* out) {
   if (m == nullptr || in == nullptr || out == nullptr) return CILQR_ERR_NULL;
   if (const int wrc = cilqr_check_warm(in, warm)) return wrc;
-  int wstride = 0, wrows = 0, wcol = 0;
-  if (warm != nullptr) (void)cilqr_warm_geometry(warm->layout, in->n_knots, &wstride, &wrows, &wcol);
   if (in->batch <= 0) return CILQR_ERR_ARG;
   if (in->batch > m->capacity) return CILQR_ERR_CAPACITY;
   if (in->n_lane_groups > 1) return CILQR_ERR_ARG;   // one lane table per call: the groups would straddle the shards
   const int n = (int)m->shard.size();
-  const size_t K = (size_t)in->n_knots, M1 = (size_t)m->max_iter + 1;
   std::vector<cilqr_problem_batch> pin(n);
   std::vector<cilqr_solution_batch> pout(n);
   std::vector<cilqr_warm_start> pwarm(n);
@@ -126,30 +123,10 @@ int cilqr_multi_solve_warm(cilqr_multi_handle m, const cilqr_problem_batch* in, 
     int b0, b1;
     shard_range(in->batch, k, n, &b0, &b1);
     if (b1 <= b0) continue;
-    cilqr_problem_batch& pi = pin[k];
-    pi = *in;
-    pi.batch = b1 - b0;
-    pi.start = in->start ? in->start + (size_t)b0 * 4 : nullptr;
-    pi.coarse = in->coarse ? in->coarse + (size_t)b0 * K * 6 : nullptr;
-    pi.corridor = in->corridor ? in->corridor + (size_t)b0 * K * in->cmax * 3 : nullptr;
-    pi.corridor_count = in->corridor_count ? in->corridor_count + (size_t)b0 * K : nullptr;
-    pi.coarse_station = in->coarse_station ? in->coarse_station + (size_t)b0 * K : nullptr;
-    cilqr_solution_batch& po = pout[k];
-    po = *out;
-    po.traj = out->traj ? out->traj + (size_t)b0 * K * CILQR_TRAJ_FIELDS : nullptr;
-    po.cost_hist = out->cost_hist ? out->cost_hist + (size_t)b0 * M1 * CILQR_COST_FIELDS : nullptr;
-    po.n_cost = out->n_cost ? out->n_cost + b0 : nullptr;
-    po.status = out->status ? out->status + b0 : nullptr;
-    po.n_iter = out->n_iter ? out->n_iter + b0 : nullptr;
-    po.iter_trajs = out->iter_trajs ? out->iter_trajs + (size_t)b0 * out->max_iter_trajs * K * CILQR_TRAJ_FIELDS : nullptr;
-    po.n_iter_trajs = out->n_iter_trajs ? out->n_iter_trajs + b0 : nullptr;
-    po.alpha_trace = out->alpha_trace ? out->alpha_trace + (size_t)b0 * m->max_iter : nullptr;
-    if (warm != nullptr) {   // the shard's rows of the warm arrays
-      pwarm[k] = *warm;
-      pwarm[k].rows = warm->rows + (size_t)b0 * wrows * wstride;
-      pwarm[k].shift = warm->shift ? warm->shift + b0 : nullptr;
-    }
-    rc = cilqr_submit_warm(m->shard[k], &pi, warm ? &pwarm[k] : nullptr, &po);   // the shard's own host threads drive its device from here on
+    pin[k] = cilqr::slice(*in, b0, b1);
+    pout[k] = cilqr::slice(*out, b0, b1, in->n_knots, m->max_iter);
+    if (warm != nullptr) pwarm[k] = cilqr::slice(*warm, b0, in->n_knots);   // the shard's rows of the warm arrays
+    rc = cilqr_submit_warm(m->shard[k], &pin[k], warm ? &pwarm[k] : nullptr, &pout[k]);   // the shard's own host threads drive its device from here on
     if (rc == CILQR_OK) submitted[k] = 1;
   }
   for (int k = 0; k < n; ++k) {

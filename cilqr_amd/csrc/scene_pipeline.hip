@@ -97,13 +97,11 @@ int cilqr::plan_scenes(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilq
   if ((int32_t)(dp_cfg->tf / dp_cfg->delta_t + 1) != n_knots || n_knots != h->cfg.n_steps + 1) return CILQR_ERR_KNOTS;
   if (beyond_limits(sb, n_knots) || sb.batch > h->capacity) return CILQR_ERR_CAPACITY;
   // the warm start against the problem batch the solve will get: n_knots knots, its arrays where the scenes are
-  int w_stride = 0, w_rows = 0, w_col = 0;
   if (warm != nullptr) {
     cilqr_problem_batch like;
     std::memset(&like, 0, sizeof(like));
     like.batch = sb.batch; like.n_knots = n_knots; like.memory = sb.memory;
     if (int rc = cilqr_check_warm(&like, warm)) return rc;
-    cilqr_warm_geometry(warm->layout, n_knots, &w_stride, &w_rows, &w_col);
   }
   const int per_vertex = corridor_cfg->is_multiple_sample ? 6 : 1;
   const int max_points = worst_case_points(sb, per_vertex);
@@ -140,7 +138,7 @@ int cilqr::plan_scenes(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilq
   const SceneImage im(l_work, sb);
   const slot s_s4 = l_work.add(B * 4 * 8), s_plan = l_work.add(plan ? B * K * CILQR_PLAN_FIELDS * 8 : 0);
   const slot s_c9 = l_work.add(coarse9 ? B * K * CILQR_COARSE_FIELDS * 8 : 0), s_outcome = l_work.add(outcome ? B * 4 : 0);
-  const slot s_wrows = l_work.add(warm ? B * (size_t)w_rows * w_stride * 8 : 0), s_wshift = l_work.add(warm && warm->shift ? B * 4 : 0);
+  const slot s_wrows = l_work.add(warm ? B * widths(*warm, n_knots).rows * 8 : 0), s_wshift = l_work.add(warm && warm->shift ? B * 4 : 0);
   HIP_TRY(h->ps_work.grow((on_host ? l_work.bytes() : b_device) + 256, &h->grown_bytes));
   const size_t per_scene = K * ((size_t)max_points * 2 * 8 + 4);
   size_t chunk = std::min(B, std::max<size_t>(1, kPointsBytesCap / per_scene));

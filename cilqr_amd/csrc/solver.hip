@@ -42,8 +42,7 @@ hipError_t dev_alloc(cilqr_solver* h, T** p, size_t count) {
   return hipSuccess;
 }
 
-constexpr int64_t kTailMaxProblems = 8192;
-constexpr size_t kSmallTransfer = (size_t)4 << 20;   // host batches up to this many bytes travel as one pinned block each way   // CILQR_OPT_TAIL_THRESHOLD is clamped to this
+constexpr int64_t kTailMaxProblems = 8192;   // CILQR_OPT_TAIL_THRESHOLD is clamped to this
 
 void fill_params(const cilqr_config& c, Params* p) {
   std::memset(p, 0, sizeof(*p));
@@ -77,15 +76,6 @@ void fill_params(const cilqr_config& c, Params* p) {
 }
 
 }  // namespace
-
-bool cilqr_warm_geometry(int32_t layout, int32_t n_knots, int* stride, int* rows_per, int* col) {
-  switch (layout) {
-    case CILQR_ROWS_TRAJ: *stride = CILQR_TRAJ_FIELDS; *rows_per = n_knots; *col = 8; return true;
-    case CILQR_ROWS_PLAN: *stride = CILQR_PLAN_FIELDS; *rows_per = n_knots; *col = 9; return true;
-    case CILQR_ROWS_CONTROLS: *stride = CILQR_NU; *rows_per = n_knots - 1; *col = 0; return true;
-    default: return false;   // CILQR_ROWS_COARSE carries no controls
-  }
-}
 
 int cilqr_check_warm(const cilqr_problem_batch* in, const cilqr_warm_start* warm) {
   if (warm == nullptr) return CILQR_OK;
@@ -163,108 +153,55 @@ void release_in_buffer(cilqr_solver* h, int k, hipStream_t st) {   // behind the
   h->cv.notify_all();
 }
 
-// doubles of the warm rows and ints of the shift array that travel with a batch of B problems (0, 0: no warm start)
-void warm_counts(const cilqr_problem_batch* in, const cilqr_warm_start* warm, size_t* n_rows, size_t* n_shift) {
-  *n_rows = 0;
-  *n_shift = 0;
-  int stride = 0, rows_per = 0, col = 0;
-  if (warm == nullptr || !cilqr_warm_geometry(warm->layout, in->n_knots, &stride, &rows_per, &col)) return;
-  *n_rows = (size_t)in->batch * rows_per * stride;
-  *n_shift = warm->shift ? (size_t)in->batch : 0;
-}
-
-size_t input_payload_bytes(const cilqr_solver* h, const cilqr_problem_batch* in, const cilqr_warm_start* warm) {
-  const size_t B = (size_t)in->batch, K = (size_t)in->n_knots;
-  const bool want_station = h->cfg.init_guess == CILQR_INIT_TRACKER && in->coarse_station != nullptr;
-  size_t n_wrows, n_wshift;
-  warm_counts(in, warm, &n_wrows, &n_wshift);
-  return (B * 4 + B * K * 6 + B * K * in->cmax * 3 + (want_station ? B * K : 0) + n_wrows) * sizeof(double) +
-         (B * K + n_wshift) * sizeof(int);
-}
-
 // Where the kernels find the problem-major inputs: the caller's own arrays (device memory), or a copy of them in the job
 // set's staging block, enqueued on `st` (host memory).  A small batch travels through one pinned block in one copy; a large
 // one array by array -- from pageable memory the runtime's own staged path sustains 51 GB/s on these boxes (57 from pinned
 // memory; tools/host_path_probe.cc), so nothing is gained by copying through a ring of our own first.
-// `warm` (nullable, checked by the caller: cilqr_check_warm) is one more per-problem input and travels the same way.
-int stage_inputs(cilqr_solver* h, const cilqr_problem_batch* in, const cilqr_warm_start* warm, cilqr_in_buffer* ib, hipStream_t st,
-                 ProblemView* out_pv, WarmView* out_wv) {
-  const int B = in->batch, K = in->n_knots;
-  ProblemView pv;
-  WarmView wv;
-  size_t n_wrows, n_wshift;
-  warm_counts(in, warm, &n_wrows, &n_wshift);
-  if (warm != nullptr && !cilqr_warm_geometry(warm->layout, K, &wv.stride, &wv.rows_per, &wv.col)) return CILQR_ERR_ARG;
+// `warm` (nullable, checked by the caller: cilqr_check_warm) travels the same way.  `lay`: the block as solve_io.hpp lays it
+// out -- the object the caller has asked whether the batch is small.
+int stage_inputs(cilqr_solver* h, const cilqr_problem_batch* in, const cilqr_warm_start* warm, const solve_in_layout& lay,
+                 cilqr_in_buffer* ib, hipStream_t st, ProblemView* out_pv, WarmView* out_wv) {
+  ProblemView& pv = *out_pv;
+  WarmView& wv = *out_wv = WarmView();
+  if (warm != nullptr && !cilqr_warm_geometry(warm->layout, in->n_knots, &wv.stride, &wv.rows_per, &wv.col)) return CILQR_ERR_ARG;
   pv.cmax_in = in->cmax;
-  const size_t n_start = (size_t)B * 4, n_coarse = (size_t)B * K * 6,
-               n_cor = (size_t)B * K * in->cmax * 3, n_cnt = (size_t)B * K;
-  const bool want_station = h->cfg.init_guess == CILQR_INIT_TRACKER && in->coarse_station != nullptr;
-  const size_t n_sta = want_station ? (size_t)B * K : 0;
-  pv.station = nullptr;
-  if (in->memory == CILQR_MEM_HOST) {
-    const size_t payload = (n_start + n_coarse + n_cor + n_sta + n_wrows) * sizeof(double) + (n_cnt + n_wshift) * sizeof(int);
-    const size_t bytes = payload + 1024;
+  const bool on_host = in->memory == CILQR_MEM_HOST, small = on_host && lay.is_small();
+  char *block = nullptr, *pinned = nullptr;
+  if (on_host) {
     // (a small batch lands in a block of its own: it is staged by the solving thread on the solve's stream, so the next
     // small batch's copy is ordered behind this one's load kernels by the stream itself)
-    const bool small = payload <= kSmallTransfer;
     if (!small && ib == nullptr) return CILQR_ERR_STATE;
-    dev_mem& block = small ? h->in_small : ib->p;
-    HIP_TRY(block.grow(small ? kSmallTransfer + 1024 : bytes, &h->grown_bytes));
-    double* d = block.as<double>();
-    if (small) {
-      // a small batch (the drop-in call is a batch of one): the five arrays go through ONE pinned block and ONE copy --
-      // five pageable copies cost ~10 us each before the first kernel can start
-      if (h->in_pinned.get() == nullptr) HIP_TRY(h->in_pinned.alloc(kSmallTransfer));
-      if (h->in_pinned_ev.get() == nullptr) HIP_TRY(h->in_pinned_ev.create());
-      else HIP_TRY(hipEventSynchronize(h->in_pinned_ev.get()));   // the previous load's copy has left the block
-      char* q = h->in_pinned.as<char>();
-      std::memcpy(q, in->start, n_start * 8); q += n_start * 8;
-      std::memcpy(q, in->coarse, n_coarse * 8); q += n_coarse * 8;
-      std::memcpy(q, in->corridor, n_cor * 8); q += n_cor * 8;
-      if (want_station) { std::memcpy(q, in->coarse_station, n_sta * 8); q += n_sta * 8; }
-      if (n_wrows) { std::memcpy(q, warm->rows, n_wrows * 8); q += n_wrows * 8; }
-      std::memcpy(q, in->corridor_count, n_cnt * 4); q += n_cnt * 4;
-      if (n_wshift) std::memcpy(q, warm->shift, n_wshift * 4);
-      HIP_TRY(hipMemcpyAsync(d, h->in_pinned.get(), payload, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipEventRecord(h->in_pinned_ev.get(), st));
-      pv.start = d; d += n_start;
-      pv.coarse = d; d += n_coarse;
-      pv.corridor = d; d += n_cor;
-      if (want_station) { pv.station = d; d += n_sta; }
-      if (n_wrows) { wv.rows = d; d += n_wrows; }
-      pv.ccount = reinterpret_cast<const int*>(d);
-      if (n_wshift) wv.shift = pv.ccount + n_cnt;
-    } else {
-      HIP_TRY(hipMemcpyAsync(d, in->start, n_start * 8, hipMemcpyHostToDevice, st));
-      pv.start = d; d += n_start;
-      HIP_TRY(hipMemcpyAsync(d, in->coarse, n_coarse * 8, hipMemcpyHostToDevice, st));
-      pv.coarse = d; d += n_coarse;
-      HIP_TRY(hipMemcpyAsync(d, in->corridor, n_cor * 8, hipMemcpyHostToDevice, st));
-      pv.corridor = d; d += n_cor;
-      if (want_station) {
-        HIP_TRY(hipMemcpyAsync(d, in->coarse_station, n_sta * 8, hipMemcpyHostToDevice, st));
-        pv.station = d; d += n_sta;
-      }
-      if (n_wrows) {
-        HIP_TRY(hipMemcpyAsync(d, warm->rows, n_wrows * 8, hipMemcpyHostToDevice, st));
-        wv.rows = d; d += n_wrows;
-      }
-      HIP_TRY(hipMemcpyAsync(d, in->corridor_count, n_cnt * 4, hipMemcpyHostToDevice, st));
-      pv.ccount = reinterpret_cast<const int*>(d);
-      if (n_wshift) {
-        int* ds = reinterpret_cast<int*>(d) + n_cnt;
-        HIP_TRY(hipMemcpyAsync(ds, warm->shift, n_wshift * 4, hipMemcpyHostToDevice, st));
-        wv.shift = ds;
-      }
-    }
-  } else {
-    pv.start = in->start; pv.coarse = in->coarse; pv.corridor = in->corridor;
-    pv.ccount = in->corridor_count;
-    if (want_station) pv.station = in->coarse_station;
-    if (n_wrows) { wv.rows = warm->rows; wv.shift = warm->shift; }
+    dev_mem& b = small ? h->in_small : ib->p;
+    HIP_TRY(b.grow(small ? kSmallTransfer + 1024 : lay.payload_bytes() + 1024, &h->grown_bytes));
+    block = b.as<char>();
   }
-  *out_pv = pv;
-  *out_wv = wv;
+  if (small) {
+    // a small batch (the drop-in call is a batch of one): the arrays go through ONE pinned block and ONE copy --
+    // five pageable copies cost ~10 us each before the first kernel can start
+    if (h->in_pinned.get() == nullptr) HIP_TRY(h->in_pinned.alloc(kSmallTransfer));
+    if (h->in_pinned_ev.get() == nullptr) HIP_TRY(h->in_pinned_ev.create());
+    else HIP_TRY(hipEventSynchronize(h->in_pinned_ev.get()));   // the previous load's copy has left the block
+    pinned = h->in_pinned.as<char>();
+  }
+  const void* dev[solve_in_layout::kArrays];   // where the kernels find each array (NULL: it does not travel)
+  for (int i = 0; i < solve_in_layout::kArrays; ++i) {
+    const solve_in_layout::entry& e = lay.a[i];
+    dev[i] = !e.s.bytes ? nullptr : on_host ? block + e.s.off : e.host;   // DEVICE arrays: the caller's own pointers
+    if (!on_host || !e.s.bytes) continue;
+    if (small) std::memcpy(pinned + e.s.off, e.host, e.s.bytes);
+    else HIP_TRY(hipMemcpyAsync(block + e.s.off, e.host, e.s.bytes, hipMemcpyHostToDevice, st));
+  }
+  if (small) {
+    HIP_TRY(hipMemcpyAsync(block, pinned, lay.payload_bytes(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(h->in_pinned_ev.get(), st));
+  }
+  pv.start = static_cast<const double*>(dev[solve_in_layout::kStart]);
+  pv.coarse = static_cast<const double*>(dev[solve_in_layout::kCoarse]);
+  pv.corridor = static_cast<const double*>(dev[solve_in_layout::kCorridor]);
+  pv.station = static_cast<const double*>(dev[solve_in_layout::kStation]);
+  pv.ccount = static_cast<const int*>(dev[solve_in_layout::kCount]);
+  wv.rows = static_cast<const double*>(dev[solve_in_layout::kWarmRows]);
+  wv.shift = static_cast<const int*>(dev[solve_in_layout::kWarmShift]);
   return CILQR_OK;
 }
 
@@ -287,13 +224,14 @@ int do_load(cilqr_solver* h, const cilqr_problem_batch* in, const cilqr_warm_sta
     pv = *staged;
     if (staged_warm) wv = *staged_warm;
   } else {
-    if (in->memory == CILQR_MEM_HOST && input_payload_bytes(h, in, warm) > kSmallTransfer) {
+    const solve_in_layout lay(h->cfg, *in, warm);
+    if (in->memory == CILQR_MEM_HOST && !lay.is_small()) {
       // (never refused: the transfer thread uploads for a solve only once every solve before it is past its load, so at
       // most one buffer is ever ahead of the solve that stages here)
       buf = acquire_in_buffer(h, false);
       if (buf < 0) return buf == -1 ? CILQR_ERR_STATE : CILQR_ERR_DEVICE;
     }
-    rc = stage_inputs(h, in, warm, buf >= 0 ? &h->in_bufs[buf] : nullptr, st, &pv, &wv);
+    rc = stage_inputs(h, in, warm, lay, buf >= 0 ? &h->in_bufs[buf] : nullptr, st, &pv, &wv);
   }
   if (rc == CILQR_OK) rc = load_kernels(h, in, js, v, st, pv, wv);
   release_in_buffer(h, buf, st);
@@ -974,7 +912,6 @@ static int solve_groups(cilqr_solver* h, cilqr_job& j, const cilqr_problem_batch
       in->left_lane == nullptr || in->right_lane == nullptr)
     return CILQR_ERR_CONSTRAINTS;
   if (in->lane_group_start[0] != 0 || in->lane_group_start[in->n_lane_groups] != in->batch) return CILQR_ERR_ARG;
-  const size_t K = (size_t)in->n_knots, M1 = (size_t)h->cfg.max_iter + 1;
   int wstride = 0, wrows = 0, wcol = 0;
   if (warm != nullptr && !cilqr_warm_geometry(warm->layout, in->n_knots, &wstride, &wrows, &wcol)) return CILQR_ERR_ARG;
   size_t lrow = 0, rrow = 0;
@@ -984,33 +921,15 @@ static int solve_groups(cilqr_solver* h, cilqr_job& j, const cilqr_problem_batch
     const int b0 = in->lane_group_start[g], b1 = in->lane_group_start[g + 1];
     if (b1 < b0 || in->lane_group_left[g] <= 0 || in->lane_group_right[g] <= 0) return CILQR_ERR_ARG;
     if (b1 > b0) {
-      cilqr_problem_batch pi = *in;
+      cilqr_problem_batch pi = slice(*in, b0, b1);
       pi.n_lane_groups = 0;
-      pi.batch = b1 - b0;
-      pi.start = in->start ? in->start + (size_t)b0 * 4 : nullptr;
-      pi.coarse = in->coarse ? in->coarse + (size_t)b0 * K * 6 : nullptr;
-      pi.corridor = in->corridor ? in->corridor + (size_t)b0 * K * in->cmax * 3 : nullptr;
-      pi.corridor_count = in->corridor_count ? in->corridor_count + (size_t)b0 * K : nullptr;
-      pi.coarse_station = in->coarse_station ? in->coarse_station + (size_t)b0 * K : nullptr;
       pi.n_left = in->lane_group_left[g];
       pi.n_right = in->lane_group_right[g];
       pi.left_lane = in->left_lane + lrow * CILQR_LANE_FIELDS;
       pi.right_lane = in->right_lane + rrow * CILQR_LANE_FIELDS;
-      cilqr_solution_batch po = *out;
-      po.traj = out->traj ? out->traj + (size_t)b0 * K * CILQR_TRAJ_FIELDS : nullptr;
-      po.cost_hist = out->cost_hist ? out->cost_hist + (size_t)b0 * M1 * CILQR_COST_FIELDS : nullptr;
-      po.n_cost = out->n_cost ? out->n_cost + b0 : nullptr;
-      po.status = out->status ? out->status + b0 : nullptr;
-      po.n_iter = out->n_iter ? out->n_iter + b0 : nullptr;
-      po.iter_trajs = out->iter_trajs ? out->iter_trajs + (size_t)b0 * out->max_iter_trajs * K * CILQR_TRAJ_FIELDS : nullptr;
-      po.n_iter_trajs = out->n_iter_trajs ? out->n_iter_trajs + b0 : nullptr;
-      po.alpha_trace = out->alpha_trace ? out->alpha_trace + (size_t)b0 * h->cfg.max_iter : nullptr;
+      cilqr_solution_batch po = slice(*out, b0, b1, in->n_knots, h->cfg.max_iter);
       cilqr_warm_start wi;
-      if (warm != nullptr) {
-        wi = *warm;
-        wi.rows = warm->rows ? warm->rows + (size_t)b0 * wrows * wstride : nullptr;
-        wi.shift = warm->shift ? warm->shift + b0 : nullptr;
-      }
+      if (warm != nullptr) wi = slice(*warm, b0, in->n_knots);
       const int rc = solve_one(h, j, &pi, warm ? &wi : nullptr, &po);
       if (rc != CILQR_OK) return rc;
       acc.iterations += j.prof.iterations;
@@ -1054,20 +973,6 @@ DeviceState twin_of(const DeviceState& own, const DeviceState& tw) {
   t.act = tw.act; t.act_next = tw.act_next; t.posn = tw.posn;
   t.knot0 = own.knot0 ? tw.knot0 : nullptr;
   return t;
-}
-
-// bytes of the output staging block in front of the iterates, and whether host outputs of this size travel through the
-// small pinned block (one copy, handed out on the host) or ragged (job_finish)
-size_t out_head_bytes(const cilqr_solver* h, int B, const cilqr_solution_batch* out) {
-  const size_t K = (size_t)h->cfg.n_steps + 1, M = (size_t)h->cfg.max_iter;
-  const size_t n_traj = (size_t)B * K * 10, n_hist = (size_t)B * (M + 1) * 5, n_at = out->alpha_trace ? (size_t)B * M : 0;
-  return (n_traj + n_hist) * 8 + (((size_t)4 * B * 4 + n_at + 7) & ~(size_t)7);
-}
-bool host_out_is_big(const cilqr_solver* h, int B, const cilqr_solution_batch* out) {
-  if (out->memory != CILQR_MEM_HOST) return false;
-  const size_t K = (size_t)h->cfg.n_steps + 1;
-  const size_t n_itr = out->iter_trajs ? (size_t)B * (size_t)std::max(out->max_iter_trajs, 0) * K * 10 : 0;
-  return out_head_bytes(h, B, out) + n_itr * 8 > kSmallTransfer;
 }
 
 // test door (cilqr_set_search_seed): the armed seed, if any, goes to the device and over the search state of the solve that
@@ -1150,45 +1055,23 @@ int job_begin(cilqr_solver* h, cilqr_job& j) {
   h->cv.notify_all();
   if (rc != CILQR_OK) return rc;
   h->stage = 0;   // the main arena no longer holds what cilqr_stage_load put there
-  const int B = in->batch, K = in->n_knots, M = h->cfg.max_iter;
+  const int B = in->batch, M = h->cfg.max_iter;
   j.B = B;
   // two views of the device state: `d` is the arena the active problems live in, `o` the other one
   j.d = j.gmain;
   j.o = twin_of(j.gmain, h->twin);
 
-  // output staging when the caller's buffers live in host memory
-  j.o_traj = out->traj; j.o_hist = out->cost_hist; j.o_it = out->iter_trajs;
-  j.o_nc = out->n_cost; j.o_st = out->status; j.o_ni = out->n_iter; j.o_nit = out->n_iter_trajs;
-  j.o_at = reinterpret_cast<signed char*>(out->alpha_trace);
-  j.n_traj = (size_t)B * K * 10; j.n_hist = (size_t)B * (M + 1) * 5;
-  j.n_itr = out->iter_trajs ? (size_t)B * out->max_iter_trajs * K * 10 : 0;
-  j.n_at = out->alpha_trace ? (size_t)B * M : 0;
-  j.n_head = 0;
-  j.small_out = false;
-  j.big_out = false;
-  if (out->memory == CILQR_MEM_HOST) {
-    // staging block: traj | cost_hist | n_cost, status, n_iter, n_iter_trajs | alpha_trace | (8-byte pad) | iter_trajs --
-    // the iterates last, so that a small batch can fetch everything else (and the first few iterates) in one short copy
-    j.n_head = out_head_bytes(h, B, out);
-    const size_t bytes = j.n_head + j.n_itr * 8 + 1024;
-    HIP_TRY(js.out_stage.grow(bytes, &h->grown_bytes));
-    double* p = js.out_stage.as<double>();
-    j.o_traj = p; p += j.n_traj;
-    j.o_hist = p; p += j.n_hist;
-    int* q = reinterpret_cast<int*>(p);
-    j.o_nc = q; j.o_st = q + B; j.o_ni = q + 2 * B; j.o_nit = q + 3 * B;
-    j.o_at = out->alpha_trace ? reinterpret_cast<signed char*>(q + 4 * B) : nullptr;
-    j.o_it = out->iter_trajs ? reinterpret_cast<double*>(js.out_stage.as<char>() + j.n_head) : nullptr;
-    j.big_out = host_out_is_big(h, B, out);
-    j.small_out = !j.big_out;
+  // output staging when the caller's buffers live in host memory (the block's layout: solve_io.hpp)
+  const solve_out_layout lay(h->cfg, B, *out);
+  if (lay.on_host) HIP_TRY(js.out_stage.grow(lay.total_bytes() + 1024, &h->grown_bytes));
+  j.res = solve_outputs(lay, *out, js.out_stage.get());
+  if (j.res.where == solve_outputs::kLargeHost) {
     // The staging buffer is reused between solves.  Its Cost rows reach the caller through the live rows only, on either
     // path (a small batch is handed out row by row in job_finish, a large one downloads them packed); the iterates of a large
     // batch travel as the dense block they are, so the entries the kernels do not write (>= n_iter_trajs) are cleared here
-    if (j.big_out && j.n_itr) HIP_TRY(hipMemsetAsync(j.o_it, 0, j.n_itr * 8, st));
-    if (j.big_out) {
-      HIP_TRY(js.row_off.grow(((size_t)B + 1) * sizeof(long long), &h->grown_bytes));
-      HIP_TRY(js.host_counts.grow((size_t)4 * B * sizeof(int)));
-    }
+    if (lay.iter_trajs.bytes) HIP_TRY(hipMemsetAsync(j.res.dev.iter_trajs, 0, lay.iter_trajs.bytes, st));
+    HIP_TRY(js.row_off.grow(((size_t)B + 1) * sizeof(long long), &h->grown_bytes));
+    HIP_TRY(js.host_counts.grow(lay.counts_bytes()));
   }
 
   // the first iterate: the configured init guess, except for the problems a warm start covers (shift >= 0; without a shift
@@ -1207,7 +1090,7 @@ int job_begin(cilqr_solver* h, cilqr_job& j) {
   if (!j.first_quad) launch_cost_only(j.d, nullptr, B, 0, st, 1);
   launch_init_cost_commit(j.d, B, st);                 // cc:170,173
   if (int src = apply_search_seed(h, j.d, B, st)) return src;   // test door: nothing is launched unless a seed is armed
-  if (j.o_it) launch_export_iter_traj(j.d, nullptr, B, j.o_it, out->max_iter_trajs, st);
+  if (j.res.dev.iter_trajs) launch_export_iter_traj(j.d, nullptr, B, j.res.dev.iter_trajs, out->max_iter_trajs, st);
   if (j.tm.end()) return CILQR_ERR_DEVICE;
 
   while ((int)js.iter_ev.size() < M) {   // (an event joins the list once it exists)
@@ -1231,7 +1114,7 @@ int job_begin(cilqr_solver* h, cilqr_job& j) {
   // rows >= n_cost of the caller's cost_hist are zero on every host path (include/cilqr.h).  A large batch receives its live
   // rows only, so the array is cleared on the host -- by the transfer thread for a submitted solve, here (behind the first
   // kernels, which keep the GPU busy meanwhile) for the synchronous call
-  if (j.big_out && j.zero_inline) std::memset(out->cost_hist, 0, j.n_hist * 8);
+  if (j.res.where == solve_outputs::kLargeHost && j.zero_inline) std::memset(out->cost_hist, 0, lay.cost_hist.bytes);
   j.n_hint = B;   // upper bound of the active count of the iteration being enqueued
   j.span = B;     // slots occupied in the current arena (upper bound)
   return CILQR_OK;
@@ -1325,7 +1208,7 @@ int job_iterate(cilqr_solver* h, cilqr_job& j, int stage) {
       void* ws = (stage == 1 && !j.handed) ? h->tail_ws1.get() : h->tail_ws.get();
       if (j.tm.begin(4)) return CILQR_ERR_DEVICE;
       HIP_TRY(hipMemsetAsync(js.tail_iter_dev, 0, sizeof(int), st));
-      launch_tail(d, ws, n_hint, j.o_traj, j.o_it, j.out.max_iter_trajs, js.tail_iter_dev, j.tail_lds_limit, st);
+      launch_tail(d, ws, n_hint, j.res.dev.traj, j.res.dev.iter_trajs, j.out.max_iter_trajs, js.tail_iter_dev, j.tail_lds_limit, st);
       HIP_TRY(hipMemcpyAsync(h_count + M + 32, js.tail_iter_dev, sizeof(int), hipMemcpyDeviceToHost, st));
       if (j.tm.end()) return CILQR_ERR_DEVICE;
       j.tail_used = true;
@@ -1347,8 +1230,8 @@ int job_iterate(cilqr_solver* h, cilqr_job& j, int stage) {
     j.bwd_iter.push_back(it);
     launch_linesearch(d, n_hint, j.spec_threshold, h->seq_rounds, h->round_group, st);  // cc:235-270
     launch_update(d, n_hint, st);                      // cc:272-308
-    launch_export_done(d, n_hint, j.o_traj, st);       // cc:238,285,303,319
-    if (j.o_it) launch_export_iter_traj(d, d.act, n_hint, j.o_it, j.out.max_iter_trajs, st);
+    launch_export_done(d, n_hint, j.res.dev.traj, st);       // cc:238,285,303,319
+    if (j.res.dev.iter_trajs) launch_export_iter_traj(d, d.act, n_hint, j.res.dev.iter_trajs, j.out.max_iter_trajs, st);
     if (j.tm.end()) return CILQR_ERR_DEVICE;
     HIP_TRY(hipEventRecord(js.iter_ev[it].get(), st));
     if (h->compaction && (int64_t)100 * n_hint <= (int64_t)h->compact_percent * j.span) {
@@ -1375,14 +1258,15 @@ int job_finish(cilqr_solver* h, cilqr_job& j) {
   j.tm.stream = st;
   // (no wait here: the export and the copy out are enqueued behind the solve's last kernel, ONE host round trip for all of it)
   if (j.tm.begin(3)) return CILQR_ERR_DEVICE;
-  const bool big_out = out->memory == CILQR_MEM_HOST && j.big_out;
-  launch_export_hist(j.gmain, B, big_out ? nullptr : j.o_hist, j.o_nc, j.o_st, j.o_ni, j.o_nit, j.o_at, st);
-  if (big_out) launch_export_hist_rows(j.gmain, B, js.row_off.as<long long>(), j.o_hist, st);   // the live rows, packed, where the dense block used to go
+  const cilqr_solution_batch& r = j.res.dev;   // where the kernels have written
+  const solve_out_layout& lay = j.res.lay;
+  const bool big_out = j.res.where == solve_outputs::kLargeHost, small_out = j.res.where == solve_outputs::kSmallHost;
+  launch_export_hist(j.gmain, B, big_out ? nullptr : r.cost_hist, r.n_cost, r.status, r.n_iter, r.n_iter_trajs, reinterpret_cast<signed char*>(r.alpha_trace), st);
+  if (big_out) launch_export_hist_rows(j.gmain, B, js.row_off.as<long long>(), r.cost_hist, st);   // the live rows, packed, where the dense block used to go
   if (j.tm.end()) return CILQR_ERR_DEVICE;
   HIP_TRY(hipGetLastError());
-  const bool small_out = out->memory == CILQR_MEM_HOST && j.small_out;
-  const size_t one_traj = ((size_t)h->cfg.n_steps + 1) * 10 * 8;                 // bytes of one iterate
-  const size_t per = out->iter_trajs ? (size_t)out->max_iter_trajs * one_traj : 0;   // iterate block of one problem
+  const size_t one_traj = lay.w.traj * 8;                               // bytes of one iterate
+  const size_t per = out->iter_trajs ? lay.w.iter_trajs * 8 : 0;        // iterate block of one problem
   // a batch of one (the drop-in call) fetches its first iterates with the head: 8-9 exist on average, the capacity is
   // max_iter + 1 (820 KB, 20 us of copy for 36 KB of data)
   constexpr int kFirstIterates = 16;
@@ -1391,7 +1275,7 @@ int job_finish(cilqr_solver* h, cilqr_job& j) {
     // a small batch: the head of the staging block in one copy into pinned memory, handed out on the host below (seven
     // pageable copies cost ~25 us each after the last kernel); the iterates that exist follow once their counts are known
     if (js.out_pinned.get() == nullptr) HIP_TRY(js.out_pinned.alloc(kSmallTransfer));
-    HIP_TRY(hipMemcpyAsync(js.out_pinned.get(), js.out_stage.get(), j.n_head + first, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(js.out_pinned.get(), js.out_stage.get(), lay.head_bytes() + first, hipMemcpyDeviceToHost, st));
   } else if (big_out) {
     // A large batch: everything is downloaded on the handle's download stream, so that the kernels of the NEXT solve's
     // finishing stage do not queue behind 0.3 GB of copies.  First the counts (they size the packed rows), then the
@@ -1401,18 +1285,18 @@ int job_finish(cilqr_solver* h, cilqr_job& j) {
     hipStream_t so = h->stream_out.get();
     HIP_TRY(hipEventRecord(js.exported.get(), st));
     HIP_TRY(hipStreamWaitEvent(so, js.exported.get(), 0));
-    HIP_TRY(hipMemcpyAsync(js.host_counts.get(), j.o_nc, (size_t)4 * B * 4, hipMemcpyDeviceToHost, so));   // n_cost | status | n_iter | n_iter_trajs
+    HIP_TRY(hipMemcpyAsync(js.host_counts.get(), r.n_cost, lay.counts_bytes(), hipMemcpyDeviceToHost, so));   // n_cost | status | n_iter | n_iter_trajs
     HIP_TRY(hipEventRecord(js.sync_ev.get(), so));
     if (int wrc = wait_event(js.sync_ev.get(), j.relaxed_wait)) return wrc;
     release_fin(h, j);
     const int32_t* nc = js.host_counts.as<const int32_t>();
     size_t rows = 0;
-    for (int b = 0; b < B; ++b) rows += (size_t)std::min(std::max(nc[b], 0), M + 1);
+    for (int b = 0; b < B; ++b) rows += live_cost_rows(nc[b], M);
     HIP_TRY(js.host_rows.grow(std::max(rows + rows / 2, (size_t)B * 16) * 5 * 8));
-    HIP_TRY(hipMemcpyAsync(js.host_rows.get(), j.o_hist, rows * 5 * 8, hipMemcpyDeviceToHost, so));
-    HIP_TRY(hipMemcpyAsync(out->traj, j.o_traj, j.n_traj * 8, hipMemcpyDeviceToHost, so));
-    if (out->iter_trajs) HIP_TRY(hipMemcpyAsync(out->iter_trajs, j.o_it, j.n_itr * 8, hipMemcpyDeviceToHost, so));
-    if (out->alpha_trace) HIP_TRY(hipMemcpyAsync(out->alpha_trace, j.o_at, j.n_at, hipMemcpyDeviceToHost, so));
+    HIP_TRY(hipMemcpyAsync(js.host_rows.get(), r.cost_hist, rows * 5 * 8, hipMemcpyDeviceToHost, so));
+    HIP_TRY(hipMemcpyAsync(out->traj, r.traj, lay.traj.bytes, hipMemcpyDeviceToHost, so));
+    if (out->iter_trajs) HIP_TRY(hipMemcpyAsync(out->iter_trajs, r.iter_trajs, lay.iter_trajs.bytes, hipMemcpyDeviceToHost, so));
+    if (out->alpha_trace) HIP_TRY(hipMemcpyAsync(out->alpha_trace, r.alpha_trace, lay.alpha_trace.bytes, hipMemcpyDeviceToHost, so));
     st = so;
   }
   if (int wrc = wait_stream(st, js.sync_ev.get(), j.relaxed_wait)) return wrc;
@@ -1449,59 +1333,36 @@ int job_finish(cilqr_solver* h, cilqr_job& j) {
       std::unique_lock<std::mutex> lk(h->mu);
       h->cv.wait(lk, [&] { return !j.io_busy; });
     }
-    const char* q = js.host_counts.as<const char>();
-    const int32_t* nc = reinterpret_cast<const int32_t*>(q);
-    const size_t row = 5 * 8, block = (size_t)(M + 1) * row;
-    const char* src = js.host_rows.as<const char>();
-    for (int b = 0; b < B; ++b) {   // live rows into the caller's dense array; the rest of it is zero already
-      const size_t live = (size_t)std::min(std::max(nc[b], 0), M + 1) * row;
-      std::memcpy(reinterpret_cast<char*>(out->cost_hist) + (size_t)b * block, src, live);
-      src += live;
-    }
-    std::memcpy(out->n_cost, q, (size_t)B * 4);
-    std::memcpy(out->status, q + (size_t)B * 4, (size_t)B * 4);
-    if (out->n_iter) std::memcpy(out->n_iter, q + (size_t)2 * B * 4, (size_t)B * 4);
-    if (out->iter_trajs) std::memcpy(out->n_iter_trajs, q + (size_t)3 * B * 4, (size_t)B * 4);
+    // the packed live rows into the caller's dense array (the rest of it is zero already); the alpha trace has travelled
+    const int32_t* nc = js.host_counts.as<const int32_t>();
+    scatter_cost_rows(out->cost_hist, js.host_rows.get(), 0, nc, B, M);
+    hand_out_counts(*out, lay, nc, nullptr);
   }
-  if (small_out) {   // same layout as the staging block (job_begin)
+  if (small_out) {   // the head of the staging block, as it lies there
     char* pin = js.out_pinned.as<char>();
-    const char* q = pin + (j.n_traj + j.n_hist) * 8;
-    const int32_t* nc = reinterpret_cast<const int32_t*>(q);
-    const int32_t* nit = reinterpret_cast<const int32_t*>(q + (size_t)3 * B * 4);
+    const int32_t *nc = lay.n_cost.in<const int32_t>(pin), *nit = lay.n_iter_trajs.in<const int32_t>(pin);
+    char* pin_it = lay.iter_trajs.in<char>(pin);
+    const auto used_bytes = [&](int b) { return (size_t)std::min(std::max(nit[b], 0), out->max_iter_trajs) * one_traj; };   // the iterates problem b holds
     if (out->iter_trajs) {
       // the iterates that exist and did not come with the head (the capacity is max_iter + 1 in the drop-in adapter)
       bool more = false;
       for (int b = 0; b < B; ++b) {
-        const size_t used = (size_t)std::min(std::max(nit[b], 0), out->max_iter_trajs) * one_traj;
-        const size_t have = (b == 0) ? std::min(first, used) : 0;
+        const size_t used = used_bytes(b), have = (b == 0) ? std::min(first, used) : 0;
         if (used > have) {
-          HIP_TRY(hipMemcpyAsync(pin + j.n_head + (size_t)b * per + have, reinterpret_cast<const char*>(j.o_it) + (size_t)b * per + have,
+          HIP_TRY(hipMemcpyAsync(pin_it + (size_t)b * per + have, reinterpret_cast<const char*>(r.iter_trajs) + (size_t)b * per + have,
                                  used - have, hipMemcpyDeviceToHost, st));
           more = true;
         }
       }
       if (more) { if (int wrc = wait_stream(st, js.sync_ev.get(), j.relaxed_wait)) return wrc; }
     }
-    std::memcpy(out->traj, pin, j.n_traj * 8);
-    {  // cost rows: the live ones; the rest of the caller's array is zero, as on every host path
-      const size_t row = 5 * 8, block = (size_t)(M + 1) * row;
-      std::memset(out->cost_hist, 0, j.n_hist * 8);
-      for (int b = 0; b < B; ++b) {
-        const size_t live = (size_t)std::min(std::max(nc[b], 0), M + 1) * row;
-        std::memcpy(reinterpret_cast<char*>(out->cost_hist) + (size_t)b * block, pin + j.n_traj * 8 + (size_t)b * block, live);
-      }
-    }
-    if (out->iter_trajs) {
-      for (int b = 0; b < B; ++b) {
-        const size_t used = (size_t)std::min(std::max(nit[b], 0), out->max_iter_trajs) * one_traj;
-        std::memcpy(reinterpret_cast<char*>(out->iter_trajs) + (size_t)b * per, pin + j.n_head + (size_t)b * per, used);
-      }
-    }
-    std::memcpy(out->n_cost, q, (size_t)B * 4);
-    std::memcpy(out->status, q + (size_t)B * 4, (size_t)B * 4);
-    if (out->n_iter) std::memcpy(out->n_iter, q + (size_t)2 * B * 4, (size_t)B * 4);
-    if (out->iter_trajs) std::memcpy(out->n_iter_trajs, q + (size_t)3 * B * 4, (size_t)B * 4);
-    if (out->alpha_trace) std::memcpy(out->alpha_trace, q + (size_t)4 * B * 4, j.n_at);
+    std::memcpy(out->traj, lay.traj.in<char>(pin), lay.traj.bytes);
+    // cost rows: the live ones of the dense block; the rest of the caller's array is zero, as on every host path
+    std::memset(out->cost_hist, 0, lay.cost_hist.bytes);
+    scatter_cost_rows(out->cost_hist, lay.cost_hist.in<char>(pin), lay.w.cost_hist * 8, nc, B, M);
+    if (out->iter_trajs)
+      for (int b = 0; b < B; ++b) std::memcpy(reinterpret_cast<char*>(out->iter_trajs) + (size_t)b * per, pin_it + (size_t)b * per, used_bytes(b));
+    hand_out_counts(*out, lay, nc, lay.alpha_trace.in<char>(pin));
   }
   j.tm.resolve(&j.prof);
   return CILQR_OK;
@@ -1666,7 +1527,7 @@ void worker_io_main(cilqr_solver* h) {
         if (buf < 0) rc = CILQR_ERR_DEVICE;
       }
       hipStream_t si = h->stream_in.get();
-      if (rc == CILQR_OK) rc = stage_inputs(h, &j.in, warm, &h->in_bufs[buf], si, &j.pv, &j.wv);
+      if (rc == CILQR_OK) rc = stage_inputs(h, &j.in, warm, solve_in_layout(h->cfg, j.in, warm), &h->in_bufs[buf], si, &j.pv, &j.wv);
       if (rc == CILQR_OK && hipEventRecord(h->in_bufs[buf].ready.get(), si) != hipSuccess) rc = CILQR_ERR_DEVICE;
       if (rc != CILQR_OK && buf >= 0) {   // nothing will read it
         (void)hipStreamSynchronize(si);
@@ -1682,7 +1543,7 @@ void worker_io_main(cilqr_solver* h) {
       lk.unlock();
     }
     if (j.zero_by_io && j.out.cost_hist != nullptr)
-      std::memset(j.out.cost_hist, 0, (size_t)j.in.batch * ((size_t)h->cfg.max_iter + 1) * 5 * 8);
+      std::memset(j.out.cost_hist, 0, solve_out_layout(h->cfg, j.in.batch, j.out).cost_hist.bytes);
     lk.lock();
     j.io_busy = false;
     h->cv.notify_all();
@@ -1726,8 +1587,8 @@ int cilqr_submit_warm(cilqr_handle h, const cilqr_problem_batch* in, const cilqr
   // host arrays of a large batch: the transfer thread starts on them now (worker_io_main)
   const bool plain = in->n_lane_groups <= 1 && in->batch > 0 && in->batch <= h->capacity;
   j.upload = (plain && in->memory == CILQR_MEM_HOST && check_problem(h, in) == CILQR_OK &&
-              input_payload_bytes(h, in, warm) > kSmallTransfer) ? 1 : 0;
-  j.zero_by_io = plain && out->cost_hist != nullptr && host_out_is_big(h, in->batch, out);
+              !solve_in_layout(h->cfg, *in, warm).is_small()) ? 1 : 0;
+  j.zero_by_io = plain && out->cost_hist != nullptr && solve_out_layout(h->cfg, in->batch, *out).is_big();
   j.zero_inline = !j.zero_by_io;
   j.io_busy = j.upload == 1 || j.zero_by_io;
   j.io_taken = false;

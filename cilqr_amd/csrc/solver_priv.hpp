@@ -13,6 +13,7 @@
 
 #include "../../include/cilqr.h"
 #include "hip_owned.hpp"
+#include "solve_io.hpp"
 #include "state.hpp"
 
 extern thread_local char g_last_hip_error[256];
@@ -131,13 +132,8 @@ struct cilqr_job {
   std::vector<int> bwd_iter;  // iteration index of every profiled backward launch
   cilqr_timer tm;
   cilqr_profile prof;
-  // where the kernels write the results (the caller's device buffers, or the staging of the job set)
-  double *o_traj = nullptr, *o_hist = nullptr, *o_it = nullptr;
-  int *o_nc = nullptr, *o_st = nullptr, *o_ni = nullptr, *o_nit = nullptr;
-  signed char* o_at = nullptr;
-  size_t n_traj = 0, n_hist = 0, n_itr = 0, n_at = 0;
-  size_t n_head = 0;        // bytes of the staging block in front of the iterates (traj, cost_hist, counts, alpha_trace, pad)
-  bool small_out = false;   // host outputs small enough to travel through the pinned block
+  // where the kernels write the results (the caller's device buffers, or the staging of the job set) and how they travel
+  cilqr::solve_outputs res;
   bool relaxed_wait = false;  // the host waits of this solve poll and nap instead of spinning (solver.hip: wait_event)
   // Host inputs of a submitted solve travel ahead of it: the handle's transfer thread (solver.hip: worker_io_main) copies
   // them into the job set's staging on a stream of its own as soon as the solve is SUBMITTED, i.e. while the solve before it
@@ -155,7 +151,6 @@ struct cilqr_job {
   bool io_taken = false;      // ... and has picked it up
   bool zero_by_io = false;    // large host outputs of a submitted solve: the transfer thread clears the caller's cost_hist
   bool zero_inline = false;   // large host outputs of a solve without the transfer thread: the solving thread clears cost_hist
-  bool big_out = false;       // host outputs that travel ragged: trajectory straight into the caller's array, live Cost rows packed
 };
 
 struct cilqr_solver {
@@ -286,8 +281,6 @@ int wait_event(hipEvent_t ev, bool relaxed, int spin_us = kWaitSpinUs);
 
 // The argument checks of a warm start against its problem batch (solver.hip; `in` not NULL): CILQR_OK for warm == NULL.
 int cilqr_check_warm(const cilqr_problem_batch* in, const cilqr_warm_start* warm);
-// doubles per row, rows per problem and first control column of a warm layout (n_knots = N + 1); false: no such layout
-bool cilqr_warm_geometry(int32_t layout, int32_t n_knots, int* stride, int* rows_per, int* col);
 
 // cilqr_dp_plan_batch (planner_batch.hip); times_out (HOST, [n_knots], optional): the time column every planned scene gets
 int cilqr_dp_plan_batch_impl(cilqr_solver* h, const cilqr_dp_config* cfg, const cilqr_scene_batch* scenes, const double* start3,

@@ -2,8 +2,8 @@
 // block -- every array at a 256-byte boundary, in the order asked for -- and move them in and out of it.  `staged_call`
 // is what an entry point uses: every array is handed to it in ONE statement, which says where the caller has it, how long
 // it is, which way it travels and which device pointer the kernels will take; stage() and finish() do the rest.  `slot`,
-// `block_layout`, copy_in and copy_out are what it is made of, and what the pipelines that keep their intermediates and
-// the caller's arrays in one work block (scene_pipeline.hip, carry_pipeline.hip) use directly.
+// `block_layout` (both in solve_io.hpp, which has no HIP dependency), copy_in and copy_out are what it is made of, and what the
+// pipelines that keep their intermediates and the caller's arrays in one work block (scene_pipeline.hip, carry_pipeline.hip) use.
 #pragma once
 #include <cassert>
 #include <cstring>
@@ -11,24 +11,6 @@
 #include "solver_priv.hpp"
 
 namespace cilqr {
-
-inline size_t round256(size_t n) { return (n + 255) / 256 * 256; }
-
-// one array's place in a block
-struct slot {
-  size_t off = 0, bytes = 0;
-  template <typename T>
-  T* in(void* block) const { return reinterpret_cast<T*>(static_cast<char*>(block) + off); }
-};
-
-class block_layout {
- public:
-  slot add(size_t bytes) { const slot s{end_, bytes}; end_ += round256(bytes); return s; }
-  size_t bytes() const { return end_; }   // of all slots handed out so far
-
- private:
-  size_t end_ = 0;
-};
 
 // the caller's HOST array into its slot / the slot into the caller's HOST array: nothing for an empty slot or an array
 // the caller did not give
