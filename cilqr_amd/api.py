@@ -146,6 +146,7 @@ KEY_TIME, KEY_STATION = 0, 1
 # cilqr_carry_rows / cilqr_carry_rows_batch: the state of a trajectory, and what cilqr_plan_scenes_batch_carry adds to it
 # in `source` (CILQR_CARRY_*)
 CARRY_KEPT, CARRY_NOT_ASKED, CARRY_REFUSED, CARRY_OFF_START, CARRY_HIT = 0, 1, 2, 3, 4
+PREDICT_HOLD, PREDICT_CONSTANT_VELOCITY = 0, 1   # CILQR_PREDICT_* (include/cilqr.h, "scene prediction")
 # cilqr_frenet_rows / cilqr_frenet_rows_batch: plain [K][2] x, y rows (CILQR_ROWS_POINTS; these two calls only), the doubles
 # of a centre-line row and of a result row (CILQR_FRENET_FIELDS), doubles per row of every layout they accept
 ROWS_POINTS = 4
@@ -199,6 +200,7 @@ EXPORTS = [
     "cilqr_constraint_margins", "cilqr_constraint_margins_batch",
     "cilqr_track_rows", "cilqr_track_rows_batch",
     "cilqr_window_scene", "cilqr_window_scenes_batch", "cilqr_plan_scenes_batch_warm",
+    "cilqr_predict_scene", "cilqr_predict_scenes_batch",
     "cilqr_carry_rows", "cilqr_carry_rows_batch", "cilqr_plan_scenes_batch_carry",
     "cilqr_road_barriers", "cilqr_default_tracker_config",
     "cilqr_set_tracker_config",
@@ -298,6 +300,11 @@ def lib():
                                          C.POINTER(C.c_int32)]
         L.cilqr_window_scenes_batch.argtypes = [C.c_void_p, C.POINTER(SceneBatchStruct), C.c_void_p, C.c_double, C.c_int32,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+        L.cilqr_predict_scene.argtypes = [C.POINTER(SceneStruct), C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double,
+                                          C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+        L.cilqr_predict_scenes_batch.argtypes = [C.c_void_p, C.POINTER(SceneBatchStruct), C.c_void_p, C.c_double, C.c_int32,
+                                                 C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(C.c_int32)]
         L.cilqr_check_collisions.argtypes = [C.POINTER(DpConfig), C.POINTER(SceneStruct), C.c_int32, C.c_void_p, C.c_int32,
                                              C.c_double, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.cilqr_check_collisions_batch.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(SceneBatchStruct), C.c_int32,
@@ -959,6 +966,46 @@ class BatchIlqrOptimizer:
                                               trajectories_ptr, counts_ptr, ok_ptr, C.byref(n))
         return rc, int(n.value)
 
+    def predict_scenes(self, packed: dict, t0, span: float, mode: int, max_age: float, sample_dt: float,
+                       out_samples: "int | None" = None):
+        """The scenes of a batch as cycles that start at t0[b] and know the samples up to t0[b] alone predict them, on the GPU
+        (cilqr_predict_scenes_batch), host arrays.  `packed` = scene_io.pack_scene_batch(center, scenes) -- its max_samples
+        may exceed DP_MAX_SAMPLES --, t0 [B] (or one value for all), mode = PREDICT_HOLD / PREDICT_CONSTANT_VELOCITY.
+        Returns a packed dict that shares every other array with `packed`: dynamic_trajectories [B,D,out_samples,4] (zeros
+        where the count is 0), dynamic_trajectory_counts [B,D] (out_samples, or 0: unseen at t0 or older than max_age),
+        max_samples = out_samples, plus predict_ok [B] bool and n_refused.  out_samples defaults to the smallest value
+        whose last sample lies past span + 1e-9."""
+        from . import scene_io
+        B, D = int(packed["batch"]), int(packed["max_dynamic"])
+        t0 = np.ascontiguousarray(np.broadcast_to(_f64(t0).ravel(), (B,)))
+        if out_samples is None:
+            out_samples = scene_io.predict_out_samples(sample_dt, span)
+        out_samples = int(out_samples)
+        keep = {k: np.ascontiguousarray(v) for k, v in packed.items() if isinstance(v, np.ndarray)}
+        keep["dynamic_trajectories"] = _f64(packed["dynamic_trajectories"])
+        keep["dynamic_trajectory_counts"] = np.ascontiguousarray(packed["dynamic_trajectory_counts"], dtype=np.int32)
+        sb = scene_batch_struct(packed, MEM_HOST, **{k: _ptr(keep[k]) for k in _SCENE_BATCH_ARRAYS})
+        rows = np.zeros((B, D, max(out_samples, 0), 4))
+        counts, ok = np.zeros((B, D), dtype=np.int32), np.zeros(B, dtype=np.int32)
+        rc, n = self.predict_scenes_raw(sb, _ptr(t0), span, mode, max_age, sample_dt, out_samples, _ptr(rows), _ptr(counts),
+                                        _ptr(ok))
+        self._chk(rc, "predict_scenes")
+        out = dict(packed)
+        out.update(max_samples=out_samples, dynamic_trajectories=rows, dynamic_trajectory_counts=counts,
+                   predict_ok=ok.astype(bool), n_refused=n)
+        return out
+
+    def predict_scenes_raw(self, scene_batch, t0_ptr, span, mode, max_age, sample_dt, out_samples, trajectories_ptr, counts_ptr,
+                           ok_ptr=None):
+        """Pointer-level form (t0 / trajectories / counts / ok in device or host memory as scene_batch.memory says: a
+        SceneBatchStruct with these two arrays and max_samples = out_samples feeds plan_scenes_raw and the audits where
+        they lie); returns (rc, the number of scenes with ok = 0)."""
+        n = C.c_int32(0)
+        rc = self.L.cilqr_predict_scenes_batch(self.h, C.byref(scene_batch), t0_ptr, C.c_double(span), int(mode),
+                                               C.c_double(max_age), C.c_double(sample_dt), int(out_samples),
+                                               trajectories_ptr, counts_ptr, ok_ptr, C.byref(n))
+        return rc, int(n.value)
+
     def check_collisions(self, packed: dict, rows, layout: int, cfg: "DpConfig | None" = None, buffer: float = 0.0):
         """Environment::CheckOptimizationCollision for every knot of a batch of trajectories on the GPU
         (cilqr_check_collisions_batch), host arrays.  `packed` = scene_io.pack_scene_batch(center, scenes), rows [B,K,F]
@@ -1344,6 +1391,28 @@ def window_scene(flat: dict, t0: float, span: float, out_samples: int, trajector
                                   counts.ctypes.data, C.byref(n))
     if rc != OK:
         raise CilqrError(rc, "in cilqr_window_scene")
+    return trajectories, counts, int(n.value)
+
+
+def predict_scene(flat: dict, t0: float, span: float, mode: int, max_age: float, sample_dt: float, out_samples: int,
+                  trajectories=None):
+    """The prediction rule of include/cilqr.h ("scene prediction") for one scene through the C-ABI (cilqr_predict_scene, host
+    only).  `flat` = scene_io.flatten_scene(center, scene).  Returns (trajectories [D,out_samples,4], counts [D] int32 --
+    out_samples, 0 or, for a negative source count, -1 --, n_refused); `trajectories`, if given, is written in place: the rows
+    of an obstacle with count 0 or -1 stay as they are."""
+    sc, keep = scene_struct(flat)
+    D = len(keep["dynamic_trajectory_counts"])
+    if trajectories is None:
+        trajectories = np.zeros((D, max(int(out_samples), 0), 4))
+    if not (isinstance(trajectories, np.ndarray) and trajectories.dtype == np.float64 and trajectories.flags.c_contiguous):
+        raise ValueError("trajectories must be a C-contiguous float64 array")
+    counts = np.zeros(D, dtype=np.int32)
+    n = C.c_int32(0)
+    rc = lib().cilqr_predict_scene(C.byref(sc), C.c_double(t0), C.c_double(span), int(mode), C.c_double(max_age),
+                                   C.c_double(sample_dt), int(out_samples), trajectories.ctypes.data, counts.ctypes.data,
+                                   C.byref(n))
+    if rc != OK:
+        raise CilqrError(rc, "in cilqr_predict_scene")
     return trajectories, counts, int(n.value)
 
 

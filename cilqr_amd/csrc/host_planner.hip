@@ -4,7 +4,8 @@
 // callers that are not C++ (the ctypes tests, the scene generator); cilqr_check_collisions asks DpEnvironment::CollisionMask
 // about every knot of a trajectory (Environment::CheckOptimizationCollision, environment.cpp:92-111), cilqr_clearance_rows
 // asks DpEnvironment::Clearance (Polygon2d::DistanceTo, polygon2d.cpp:43-52); cilqr_window_scene cuts the window of
-// include/cilqr/scene_window.hpp out of a scene's trajectories.  No device code in this file.
+// include/cilqr/scene_window.hpp out of a scene's trajectories, cilqr_predict_scene makes the prediction of
+// include/cilqr/scene_predict.hpp from them.  No device code in this file.
 #include <cmath>
 #include <limits>
 #include <vector>
@@ -12,6 +13,7 @@
 #include "../../include/cilqr/scene_window.hpp"
 #include "collision.hpp"
 #include "scene_batch.hpp"
+#include "scene_predict.hpp"
 
 namespace {
 
@@ -235,6 +237,32 @@ int cilqr_window_scene(const cilqr_scene* scene, double t0, double span, int32_t
     at += T;
   }
   if (n_overflow) *n_overflow = overflow;
+  return CILQR_OK;
+}
+
+int cilqr_predict_scene(const cilqr_scene* scene, double t0, double span, int32_t mode, double max_age, double sample_dt,
+                        int32_t out_samples, double* trajectories, int32_t* counts, int32_t* n_refused) {
+  if (scene == nullptr) return CILQR_ERR_NULL;
+  if (scene->n_dynamic < 0) return CILQR_ERR_ARG;
+  if (scene->n_dynamic > 0 && (scene->dynamic_trajectories == nullptr || scene->dynamic_trajectory_counts == nullptr ||
+                               trajectories == nullptr || counts == nullptr))
+    return CILQR_ERR_NULL;
+  if (!std::isfinite(t0)) return CILQR_ERR_ARG;
+  if (int rc = cilqr::check_prediction(span, mode, max_age, sample_dt, out_samples)) return rc;
+  size_t at = 0;
+  int refused = 0;
+  for (int o = 0; o < scene->n_dynamic; ++o) {
+    const int T = scene->dynamic_trajectory_counts[o];
+    if (T < 0) {   // the rule's refusal: this obstacle alone, and no samples of the packed array are its
+      counts[o] = -1;
+      ++refused;
+      continue;
+    }
+    counts[o] = cilqr::scene_predict::predict_trajectory(scene->dynamic_trajectories + at * 4, T, t0, mode, max_age, sample_dt,
+                                                         out_samples, trajectories + (size_t)o * out_samples * 4);
+    at += T;
+  }
+  if (n_refused) *n_refused = refused;
   return CILQR_OK;
 }
 

@@ -7,10 +7,9 @@
 // source counts and t0 they read from the same lines.  A window is a few dozen samples out of thousands: what decides the
 // kernel is how the two borders are found, not the copy.
 //   search  the rule's halving is a chain of log2 T dependent loads (17 for 10^5 samples), each a trip to HBM.  Here the
-//           wave searches together: per round its 64 lanes probe 64 evenly spaced samples of the remaining interval -- the
-//           last sample of each 1/64th --, one __ballot finds the first lane whose predicate holds and the interval becomes
-//           that lane's piece: three rounds for 10^5 samples, two for the 1501 of a 15 s recording.  On non-decreasing
-//           times both predicates are monotone, and the first index that holds is what the halving returns as well.
+//           wave searches together (wave_search.hpp: sw_wave_first): three rounds for 10^5 samples, two for the 1501 of a
+//           15 s recording.  On non-decreasing times both predicates are monotone, and the first index that holds is what
+//           the halving returns as well.
 //   copy    one sample (32 bytes) per lane and step: a wave moves 2 KiB of contiguous source.  16-byte accesses where both
 //           base pointers are 16-byte aligned (a slot's offset is a multiple of 32 bytes), 8-byte accesses otherwise.
 // Every index that is probed or copied lies in [0, T) with T <= max_samples checked first, on any input.  No atomics here;
@@ -18,37 +17,13 @@
 // per wave that saw one).
 #include "dev_model.hpp"
 #include "scene_window.hpp"
+#include "wave_search.hpp"
 
 namespace cilqr {
 
-constexpr int kSwWave = 64;
 constexpr int kSwWaves = 4;   // slots of one scene per workgroup
 constexpr int kSwLanes = kSwWave * kSwWaves;
 constexpr double kSwMargin = 1e-9;   // scene_window.hpp: kMargin
-
-// the first k of [0, T) with pred(k), T if there is none, for a predicate that is monotone in k; all 64 lanes call it with
-// the same T (the ballots are the wave's)
-template <class Pred>
-CILQR_DEV int sw_wave_first(int T, int lane, Pred pred) {
-  int a = 0, b = T;   // the answer lies in [a, b]; nothing in [0, a) holds
-  while (b - a > kSwWave) {
-    const int step = ((b - a - 1) >> 6) + 1;   // ceil((b - a) / 64): lane l probes the last sample of piece l
-    const long long p = (long long)a + (long long)(lane + 1) * step - 1;
-    const bool valid = p < b;
-    const bool hit = valid && pred((int)p);
-    const unsigned long long hits = __ballot(hit);
-    if (hits != 0ull) {
-      const int j = __ffsll(hits) - 1;   // the probes of the lanes below j are valid and do not hold
-      b = a + (j + 1) * step - 1;
-      a = a + j * step;
-    } else {
-      a = a + __popcll(__ballot(valid)) * step;   // past the last probe; <= b
-    }
-  }
-  const int p = a + lane;
-  const unsigned long long hits = __ballot(p < b && pred(p));
-  return hits != 0ull ? a + (__ffsll(hits) - 1) : b;
-}
 
 __global__ __launch_bounds__(kSwLanes) void k_scene_window(SceneWindowParams P, int groups, const double* __restrict__ src,
                                                            const int* __restrict__ src_counts, const double* __restrict__ t0,
@@ -134,8 +109,12 @@ void launch_scene_window(const SceneWindowParams& P, const double* src, const in
     const dim3 grid((unsigned)((long long)P.batch * groups));   // the host has checked that this fits
     hipLaunchKernelGGL(k_scene_window, grid, dim3(kSwLanes), 0, st, P, groups, src, src_counts, t0, out, out_counts);
   }
-  const dim3 grid_ok((unsigned)(((long long)P.batch + kSwLanes - 1) / kSwLanes));
-  hipLaunchKernelGGL(k_scene_window_ok, grid_ok, dim3(kSwLanes), 0, st, P.batch, P.max_dynamic, out_counts, ok, n_failed);
+  launch_scene_window_ok(P.batch, P.max_dynamic, out_counts, ok, n_failed, st);
+}
+
+void launch_scene_window_ok(int batch, int max_dynamic, const int* out_counts, int* ok, int* n_failed, hipStream_t st) {
+  const dim3 grid_ok((unsigned)(((long long)batch + kSwLanes - 1) / kSwLanes));
+  hipLaunchKernelGGL(k_scene_window_ok, grid_ok, dim3(kSwLanes), 0, st, batch, max_dynamic, out_counts, ok, n_failed);
 }
 
 }  // namespace cilqr

@@ -18,5 +18,7 @@ struct SceneWindowParams {
 // (NULL to skip); *n_failed += the scenes with a window count < 0.  Aligned as doubles, no more is assumed.
 void launch_scene_window(const SceneWindowParams& P, const double* src, const int* src_counts, const double* t0, double* out,
                          int* out_counts, int* ok, int* n_failed, hipStream_t st);
+// its second kernel alone (k_scene_window_ok), for the other calls that report counts this way (kernels_scene_predict.hip)
+void launch_scene_window_ok(int batch, int max_dynamic, const int* out_counts, int* ok, int* n_failed, hipStream_t st);
 
 }  // namespace cilqr

@@ -1,7 +1,7 @@
 """Closed-loop episodes over a batch of recorded scenes: plan, drive a little, plan again.
 
-This module is glue over public calls of BatchIlqrOptimizer -- window_scenes, plan_scenes and track -- and adds no rule of
-its own: what a cycle computes is what those three calls compute, made in this order.  Host arrays throughout; a caller who
+This module is glue over public calls of BatchIlqrOptimizer -- window_scenes (or predict_scenes), plan_scenes and track -- and
+adds no rule of its own: what a cycle computes is what those three calls compute, made in this order.  Host arrays throughout; a caller who
 keeps the batch on the device chains window_scenes_raw, plan_scenes_raw (warm=...) and track_raw the same way, and then
 nothing but t0 and the start states cross to the device per cycle ("Planning cycle after cycle").
 """
@@ -14,7 +14,8 @@ from . import api
 
 def run_episode(opt: "api.BatchIlqrOptimizer", packed: dict, start4, n_cycles: int, n_drive: int = 6,
                 out_samples: "int | None" = None, dp_cfg: "api.DpConfig | None" = None,
-                corridor_cfg: "api.CorridorConfig | None" = None, carry: "dict | None" = None) -> dict:
+                corridor_cfg: "api.CorridorConfig | None" = None, carry: "dict | None" = None,
+                prediction: "dict | None" = None) -> dict:
     """n_cycles planning cycles on the scenes of `packed` (scene_io.pack_scene_batch; recordings of any length, absolute
     times), all scenes starting at scene time 0 in start4 [B,4] = x y theta v.  Per cycle:
 
@@ -34,6 +35,12 @@ def run_episode(opt: "api.BatchIlqrOptimizer", packed: dict, start4, n_cycles: i
     refresh_every-th cycle (0 or absent: never).  Each such cycle's dict gains source [B] and n_kept; the first cycle has
     source = CARRY_NOT_ASKED for all.  carry = None: the loop as above.
 
+    prediction = dict(mode, max_age, sample_dt=None, out_samples=None): the scene of a cycle is not the recording's window but
+    opt.predict_scenes(packed, t0, dp_cfg.tf, mode, max_age, sample_dt, out_samples) -- what the samples observed by t0 alone
+    say (include/cilqr.h, "scene prediction"); sample_dt defaults to dp_cfg.delta_t and out_samples to the smallest value the
+    call accepts for dp_cfg.tf.  The run_episode argument out_samples is the window's and is not read then.  A refused scene
+    is handled as a window overflow is (window_ok = predict_ok).  It composes with carry=.  prediction = None: the window.
+
     A scene whose tracker failed (ok = 0) or whose window overflowed keeps its start and its t0, and its `alive` flag is 0
     for the rest of the episode.  It is still carried through the calls -- after an overflow with the counts of the
     obstacles that did not fit set to 0, because HOST arrays with a negative count refuse the whole batch -- and its
@@ -51,8 +58,14 @@ def run_episode(opt: "api.BatchIlqrOptimizer", packed: dict, start4, n_cycles: i
     prev, cycles = None, []
     driven_time = np.zeros(B)
     for cycle in range(int(n_cycles)):
-        win = opt.window_scenes(packed, t0, float(dp_cfg.tf), out_samples)
-        window_ok = win["window_ok"]
+        if prediction is None:
+            win = opt.window_scenes(packed, t0, float(dp_cfg.tf), out_samples)
+            window_ok = win["window_ok"]
+        else:
+            sample_dt = prediction.get("sample_dt")
+            win = opt.predict_scenes(packed, t0, float(dp_cfg.tf), prediction["mode"], prediction["max_age"],
+                                     float(dp_cfg.delta_t) if sample_dt is None else sample_dt, prediction.get("out_samples"))
+            window_ok = win["predict_ok"]
         if not window_ok.all():
             win = dict(win, dynamic_trajectory_counts=np.maximum(win["dynamic_trajectory_counts"], 0))
         warm = None

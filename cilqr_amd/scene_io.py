@@ -591,6 +591,72 @@ def shift_scene(scene: Scene, t0: float) -> Scene:
                  dynamic=[DynamicObstacle(polygon=d.polygon, trajectory=shifted(d.trajectory)) for d in scene.dynamic])
 
 
+PREDICT_MARGIN = 1e-9      # include/cilqr.h, "scene prediction"
+PREDICT_MIN_STEP = 1e-10
+PREDICT_HOLD, PREDICT_CONSTANT_VELOCITY = 0, 1
+
+
+def predict_covers(out_samples: int, sample_dt: float, span: float) -> bool:
+    """the span condition of the prediction calls: the last of out_samples samples lies past every query time of [0, span]"""
+    return bool(np.float64(out_samples - 1) * np.float64(sample_dt) >= np.float64(span) + np.float64(PREDICT_MARGIN))
+
+
+def predict_out_samples(sample_dt: float, span: float) -> int:
+    """the smallest out_samples >= 2 that satisfies the span condition"""
+    n = max(2, int(span / sample_dt))
+    while not predict_covers(n, sample_dt, span):
+        n += 1
+    while n > 2 and predict_covers(n - 1, sample_dt, span):
+        n -= 1
+    return n
+
+
+def predict_trajectory(traj, t0: float, mode: int, max_age: float, sample_dt: float, out_samples: int) -> np.ndarray:
+    """The prediction rule of include/cilqr.h ("scene prediction") in NumPy: from the samples of traj [T,4] = time x y theta
+    observed by t0 alone, out_samples samples on the clock 0, sample_dt, ... -- the latest observation held
+    (PREDICT_HOLD) or moved on with the velocity of the last two (PREDICT_CONSTANT_VELOCITY), its heading kept as bits.
+    [out_samples,4], or [0,4] for an obstacle that is unseen at t0 or older than max_age.  Every operation is rounded once."""
+    traj = np.asarray(traj, dtype=np.float64).reshape(-1, 4)
+    T = len(traj)
+    none = np.zeros((0, 4))
+    if T < 1:
+        return none
+    f = np.float64
+    with np.errstate(all="ignore"):
+        s = traj[:, 0] - f(t0)
+        J = _first_true(T, lambda k: bool(PREDICT_MARGIN < s[k]))
+        if J == 0:
+            return none
+        j = J - 1
+        e = -s[j]
+        if e > max_age:
+            return none
+        vx = vy = f(0.0)
+        if mode == PREDICT_CONSTANT_VELOCITY and j >= 1:
+            h = traj[j, 0] - traj[j - 1, 0]
+            if h > PREDICT_MIN_STEP:
+                vx = (traj[j, 1] - traj[j - 1, 1]) / h
+                vy = (traj[j, 2] - traj[j - 1, 2]) / h
+        x0 = traj[j, 1] + vx * e
+        y0 = traj[j, 2] + vy * e
+        tm = np.arange(int(out_samples), dtype=np.float64) * f(sample_dt)
+        out = np.empty((int(out_samples), 4))
+        out[:, 0] = tm
+        out[:, 1] = x0 + vx * tm
+        out[:, 2] = y0 + vy * tm
+        out[:, 3] = traj[j, 3]
+    return out
+
+
+def predict_scene(scene: Scene, t0: float, mode: int, max_age: float, sample_dt: float, out_samples: int) -> Scene:
+    """`scene` as a planning cycle that starts at scene time t0 and knows the samples up to t0 alone predicts it: every
+    dynamic trajectory replaced by its prediction (no sample: the obstacle is not there for the scene calls)."""
+    return Scene(start=scene.start, coarse=scene.coarse, static=scene.static,
+                 dynamic=[DynamicObstacle(polygon=d.polygon,
+                                          trajectory=predict_trajectory(d.trajectory, t0, mode, max_age, sample_dt, out_samples))
+                          for d in scene.dynamic])
+
+
 # ---------------------------------------------------------------------------------------------
 # the reference's own scene artefact: reference.pickle
 # ---------------------------------------------------------------------------------------------

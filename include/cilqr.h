@@ -1089,7 +1089,65 @@ int cilqr_window_scenes_batch(cilqr_handle h, const cilqr_scene_batch* scenes, c
                               int32_t* counts /* [B][max_dynamic] */, int32_t* ok /* [B], optional */,
                               int32_t* n_overflow /* HOST, optional */);
 
-/* ---- carry: the plan of the previous cycle as the coarse trajectory of the next (additive, ABI 7) ----
+/* ---- scene prediction: a scene at t0 from what was observed by t0 (additive, ABI 7) ----
+ * The window hands a cycle that starts at t0 the recording's future.  A caller with perception has the samples up to t0 and
+ * nothing else; the prediction rule makes, from those alone, a trajectory on the clock 0 ... span in the layout the scene
+ * calls read.  For ONE dynamic obstacle with T samples time x y theta (times taken as non-decreasing), a finite t0, a mode,
+ * max_age >= 0, sample_dt > 0 and out_samples >= 2; every operation is rounded once, no product and sum are fused,
+ * s[k] = time[k] - t0:
+ *   T < 1:  count 0.  Otherwise
+ *   J = the first k with 1e-9 < s[k], T if there is none (the window rule's halving over this predicate: defined for any input)
+ *   J == 0: nothing has been observed yet.  count 0: the obstacle is unseen, and the scene calls treat it as never there.
+ *   j = J - 1 is the latest observation, e = -s[j] its age (>= -1e-9).  e > max_age: count 0 -- the obstacle has left, or
+ *       its recording ended before t0.
+ *   CILQR_PREDICT_HOLD:               vx = vy = 0
+ *   CILQR_PREDICT_CONSTANT_VELOCITY:  j >= 1 and h = time[j] - time[j-1] > 1e-10:  vx = (x[j] - x[j-1]) / h, vy likewise;
+ *                                     otherwise vx = vy = 0 (a first sighting stands still)
+ *   x0 = x[j] + vx * e,  y0 = y[j] + vy * e:  the position at t0
+ *   output sample m = 0 ... out_samples - 1:  tm = (double)m * sample_dt;  (tm, x0 + vx * tm, y0 + vy * tm, theta[j] as bits)
+ *       -- the heading is the observed one, never derived from the velocity;  count = out_samples.
+ *   A source count that is negative (or, batched, above the source's max_samples) gives count -1, as in the window rule.
+ *   Rows of a slot whose count is 0 or -1 are left untouched.  Non-finite samples are no error: the arithmetic decides.
+ * The calls also take span and refuse (CILQR_ERR_ARG) unless (double)(out_samples - 1) * sample_dt >= span + 1e-9: the audit
+ * calls an obstacle absent when time[T-1] < t, with no epsilon, and the Query...Points rule with its 1e-10.  With the last
+ * sample at or past span + 1e-9 the window rule's argument (1e-9 against 1e-10) carries over unchanged: a predicted obstacle
+ * is present at every t in [0, span].  (dt = 0.1 and a 5 s horizon: 51 samples do not suffice, 52 do.)
+ *
+ * cilqr_predict_scene: one scene on the host, no handle (C++ callers use include/cilqr/scene_predict.hpp directly).
+ *   trajectories [n_dynamic][out_samples][4], counts [n_dynamic]
+ *   *n_refused (optional): the obstacles with count -1 (a negative source count: the obstacle is refused, its neighbours
+ *                          are predicted, and it takes no samples of the packed array)
+ * CILQR_ERR_NULL; CILQR_ERR_ARG for a non-finite t0, a span that is non-finite or negative, n_dynamic < 0, an unknown mode,
+ * a max_age that is negative or not finite, a sample_dt that is not positive or not finite, out_samples < 2 and the span
+ * condition. */
+#define CILQR_PREDICT_HOLD 0
+#define CILQR_PREDICT_CONSTANT_VELOCITY 1
+int cilqr_predict_scene(const cilqr_scene* scene, double t0, double span, int32_t mode, double max_age, double sample_dt,
+                        int32_t out_samples, double* trajectories /* [n_dynamic][out_samples][4] */,
+                        int32_t* counts /* [n_dynamic] */, int32_t* n_refused);
+/* ---- the same for B scenes per call, each at its own t0, on the GPU (kernels_scene_predict.hip) ----
+ * A cilqr_scene_batch with dynamic_trajectories = `trajectories`, dynamic_trajectory_counts = `counts`, max_samples =
+ * out_samples and every other member as in `scenes` is the predicted batch; nothing but t0 crosses to the device per cycle.
+ * scenes->max_samples may be any positive value (CILQR_ERR_CAPACITY for out_samples beyond CILQR_DP_MAX_SAMPLES).
+ *   t0           [B]                                     (memory as scenes->memory, like the three arrays below)
+ *   trajectories [B][max_dynamic][out_samples][4]        rows of a slot with count 0 or -1 are left untouched
+ *   counts       [B][max_dynamic]                        out_samples, 0 or -1
+ *   ok           [B] 1 / 0, optional (NULL to skip): 0 where one of the scene's counts is -1
+ *   *n_refused   (HOST, optional): the scenes with ok = 0
+ * One wavefront per (scene, slot); J comes from the wave's joint search (64 probes and one ballot per round), which returns
+ * what the halving returns on non-decreasing times.  On times that decrease the wave's J may differ from the halving's and
+ * the bits with it; every index read still lies in [0, T).  Otherwise every element is the host call's bit for bit; a
+ * scene's prediction does not depend on the batch around it; no alignment beyond a double's is assumed.  Stream, work space
+ * and checks as for cilqr_window_scenes_batch, plus the checks on mode, max_age, sample_dt, out_samples and span above:
+ * HOST arrays with a non-finite t0[b] or a bad source count are refused with CILQR_ERR_ARG before anything is launched;
+ * with DEVICE arrays they give every slot of that scene the count -1 and ok 0, the other scenes are unaffected. */
+int cilqr_predict_scenes_batch(cilqr_handle h, const cilqr_scene_batch* scenes, const double* t0 /* [B] */, double span,
+                               int32_t mode, double max_age, double sample_dt, int32_t out_samples,
+                               double* trajectories /* [B][max_dynamic][out_samples][4] */,
+                               int32_t* counts /* [B][max_dynamic] */, int32_t* ok /* [B], optional */,
+                               int32_t* n_refused /* HOST, optional */);
+
+/* ---- carry:the plan of the previous cycle as the coarse trajectory of the next (additive, ABI 7) ----
  * A later planning cycle need not search the lattice again: the plan of cycle n, read from the time the vehicle has reached,
  * is a coarse trajectory for cycle n + 1 as long as it still clears the obstacles on the new clock.  The carry rule makes that
  * coarse trajectory -- DiscretizedTrajectory::EvaluateTime at the knot times of the new cycle -- in the four forms
