@@ -12,7 +12,7 @@ namespace cilqr {
 
 struct CarryParams {
   int batch, n_rows;      // B, rows per trajectory (2 ... CILQR_DP_MAX_KNOTS)
-  int fields;             // 9, 10 or 11: the layout (trajectory_queries.hpp: columns_of)
+  int fields;             // 9, 10 or 11: the layout (row_layouts.hpp)
   int n_knots, n_live;    // rows per trajectory in the outputs; the first n_live are produced, the others are zero
   double max_advance, delta_t;
 };

@@ -12,7 +12,7 @@ struct ClearanceParams {
   double radius, r2x, f2x, threshold;
   int n_knots;
   int max_static, max_dynamic, max_vertices, max_samples;   // of the cilqr_scene_batch
-  RowLayout rows;
+  PoseColumns rows;
 };
 
 // One workgroup per scene of `dv`, the batch with its arrays on the device.  clearance [B][K][4] and nearest [B][K][4] may

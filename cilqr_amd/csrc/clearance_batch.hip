@@ -29,7 +29,7 @@ extern "C" int cilqr_clearance_rows_batch(cilqr_handle h, const cilqr_dp_config*
   P.threshold = threshold;
   P.n_knots = n_knots;
   scene_limits_into(&P, sb);
-  P.rows = row_layout(layout);
+  P.rows = pose_columns(layout);
 
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = h->stream;

@@ -1,32 +1,19 @@
 // Private to cilqr_amd/csrc: what the audits of one scene (host_planner.hip), the batched ones (collision_batch.hip,
-// clearance_batch.hip) and kernels_collision.hip share -- where a row layout keeps the pose, the checks on the scalar
-// arguments, the parameters of a launch and the launch function.  Every pointer of the launch is device memory; nothing
-// here synchronises.
+// clearance_batch.hip) and kernels_collision.hip share -- the checks on the scalar arguments, the parameters of a launch and
+// the launch function.  Every pointer of the launch is device memory; nothing here synchronises.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "../../include/cilqr.h"
+#include "../../include/cilqr/row_layouts.hpp"
 
 namespace cilqr {
 
-// doubles per row and the columns of time, x, y, theta (CILQR_ROWS_*); fields = 0: no such layout
-struct RowLayout {
-  int fields, time, x, y, theta;
-};
-inline RowLayout row_layout(int layout) {
-  switch (layout) {
-    case CILQR_ROWS_TRAJ: return RowLayout{CILQR_TRAJ_FIELDS, 0, 1, 2, 3};
-    case CILQR_ROWS_PLAN: return RowLayout{CILQR_PLAN_FIELDS, 0, 2, 3, 4};
-    case CILQR_ROWS_COARSE: return RowLayout{CILQR_COARSE_FIELDS, 0, 2, 3, 4};
-  }
-  return RowLayout{0, 0, 0, 0, 0};
-}
-
 // layout, knot count and buffer of either audit: CILQR_ERR_ARG / CILQR_ERR_CAPACITY / CILQR_OK
 inline int check_audit_arguments(int layout, int n_knots, double collision_buffer) {
-  if (row_layout(layout).fields == 0 || n_knots < 1) return CILQR_ERR_ARG;
+  if (pose_columns(layout).fields == 0 || n_knots < 1) return CILQR_ERR_ARG;
   if (!(collision_buffer >= 0.0) || !std::isfinite(collision_buffer)) return CILQR_ERR_ARG;
   if (n_knots > CILQR_DP_MAX_KNOTS) return CILQR_ERR_CAPACITY;
   return CILQR_OK;
@@ -38,7 +25,7 @@ struct CollisionParams {
   double h, r2x, f2x;
   int n_knots, n_barrier;
   int max_static, max_dynamic, max_vertices, max_samples;   // of the cilqr_scene_batch
-  RowLayout rows;
+  PoseColumns rows;        // what the audits read of a row (row_layouts.hpp)
   const double* barrier;   // [n_barrier][2], read through L2
 };
 

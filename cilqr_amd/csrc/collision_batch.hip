@@ -29,7 +29,7 @@ extern "C" int cilqr_check_collisions_batch(cilqr_handle h, const cilqr_dp_confi
   P.r2x = env.rear_disc_x(); P.f2x = env.front_disc_x();
   P.n_knots = n_knots; P.n_barrier = (int)barrier.size();
   scene_limits_into(&P, sb);
-  P.rows = row_layout(layout);
+  P.rows = pose_columns(layout);
 
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = h->stream;

@@ -15,6 +15,7 @@
 #include <float.h>
 #include <math.h>
 
+#include "../../include/cilqr/row_layouts.hpp"
 #include "state.hpp"
 
 namespace cilqr {
@@ -23,7 +24,6 @@ namespace cilqr {
 
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kTwoPi = 2.0 * kPi;
-constexpr double kMathEps = 1e-10;  // algorithm/math/vec2d.h:33
 
 // ---- how the six products of a coefficient of `X.transpose() * Y` are added ----
 // Every such product of the path -- A^T Vx, B^T Vx, A^T Vxx, B^T Vxx (Backward, cc:348-353) and B^T P, A^T P (iqr,
@@ -79,6 +79,56 @@ CILQR_DEV double normalize_angle(double angle) {
   }
   if (r < 0.0) r += kTwoPi;
   return r - kPi;
+}
+
+// ---- the steps every query on rows shares (include/cilqr.h, "resample"; the host statement is trajectory_queries.hpp)
+// math::slerp (math_utils.h:208-225)
+CILQR_DEV double slerp(double a0, double t0, double a1, double t1, double t) {
+  if (fabs(t1 - t0) <= kMathEps) return normalize_angle(a0);
+  const double a0_n = normalize_angle(a0), a1_n = normalize_angle(a1);
+  double d = a1_n - a0_n;
+  if (d > kPi) d = d - kTwoPi;
+  else if (d < -kPi) d = d + kTwoPi;
+  const double r = (t - t0) / (t1 - t0);
+  const double a = a0_n + d * r;
+  return normalize_angle(a);
+}
+
+// bracket: n - 1 for q >= key(n - 1), 0 for q < key(0), else std::lower_bound's halving written out -- the first row whose
+// key is not below q.  The caller applies its own `i == 0 -> 1` and upper clamp.  key: int -> double, n >= 2
+template <class Key>
+CILQR_DEV int bracket(int n, double q, Key key) {
+  if (q >= key(n - 1)) return n - 1;
+  if (q < key(0)) return 0;
+  int first = 0, len = n;
+  while (len > 0) {
+    const int half = len >> 1;
+    if (key(first + half) < q) {
+      first += half + 1;
+      len -= half + 1;
+    } else {
+      len = half;
+    }
+  }
+  return first;
+}
+
+// n doubles from global `g` to LDS `s` by the Lanes lanes of a workgroup, 16 bytes per lane and load where `g` allows:
+// the caller's arrays are only known to be aligned as doubles, so a piece that starts on an odd double moves its first
+// (and, as it comes, last) double alone
+template <int Lanes>
+CILQR_DEV void stage_in(const double* __restrict__ g, double* s, int n) {
+  const int tid = threadIdx.x;
+  const int head = min((int)((reinterpret_cast<uintptr_t>(g) >> 3) & 1), n);
+  if (head && tid == 0) s[0] = g[0];
+  const int pairs = (n - head) >> 1;
+  for (int j = tid; j < pairs; j += Lanes) {
+    const int i = head + 2 * j;
+    const double2 v = *reinterpret_cast<const double2*>(g + i);
+    s[i] = v.x;
+    s[i + 1] = v.y;
+  }
+  if (((n - head) & 1) && tid == Lanes - 1) s[n - 1] = g[n - 1];
 }
 
 // ---- lean fp64 math for the barrier terms ----

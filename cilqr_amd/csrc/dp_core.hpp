@@ -19,7 +19,6 @@ constexpr int kDpLayers = 5, kDpStations = 7, kDpLaterals = 10;   // dp_planner.
 constexpr int kDpCells = kDpStations * kDpLaterals;                // cells of a layer, si-major / li-minor
 constexpr int kDpMaxV = 8;                                         // CILQR_DP_MAX_VERTICES
 constexpr int kDpRec = 4 + 2 * kDpMaxV;                            // a static polygon in LDS: min_x max_x min_y max_y, vertices
-constexpr double kDpGeomEps = 1e-10;                               // math::kMathEpsilon, vec2d.h:33
 constexpr double kDpEps = 1e-3;                                    // dp_planner.cpp:25
 
 // everything a call shares between its scenes: the lattice as DpPlanner's constructor lays it out, the vehicle's discs
@@ -55,27 +54,15 @@ CILQR_DEV DpRef dp_center_point(const DpParams& P, int i) {
   return DpRef{c[0], c[1], c[2], c[3], c[4], c[5], c[6]};
 }
 
-CILQR_DEV double dp_slerp(double a0, double t0, double a1, double t1, double t) {   // math_utils.h:208-225
-  if (fabs(t1 - t0) <= kDpGeomEps) return normalize_angle(a0);
-  const double a0_n = normalize_angle(a0);
-  const double a1_n = normalize_angle(a1);
-  double d = a1_n - a0_n;
-  if (d > kPi) d = d - 2 * kPi;
-  else if (d < -kPi) d = d + 2 * kPi;
-  const double r = (t - t0) / (t1 - t0);
-  const double a = a0_n + d * r;
-  return normalize_angle(a);
-}
-
 CILQR_DEV DpRef dp_interpolate(const DpRef& p0, const DpRef& p1, double s) {   // discretized_trajectory.cpp:66-89
   const double s0 = p0.s, s1 = p1.s;
-  if (fabs(s1 - s0) < kDpGeomEps) return p0;
+  if (fabs(s1 - s0) < kMathEps) return p0;
   DpRef pt;
   const double weight = (s - s0) / (s1 - s0);
   pt.s = s;
   pt.x = (1 - weight) * p0.x + weight * p1.x;
   pt.y = (1 - weight) * p0.y + weight * p1.y;
-  pt.theta = dp_slerp(p0.theta, p0.s, p1.theta, p1.s, s);
+  pt.theta = slerp(p0.theta, p0.s, p1.theta, p1.s, s);
   pt.kappa = (1 - weight) * p0.kappa + weight * p1.kappa;
   pt.left_bound = (1 - weight) * p0.left_bound + weight * p1.left_bound;
   pt.right_bound = (1 - weight) * p0.right_bound + weight * p1.right_bound;
@@ -112,7 +99,7 @@ CILQR_DEV void dp_bounds_at(const DpParams& P, double station, double* left_boun
   const double* p0 = P.center + (size_t)(it - 1) * 7;
   const double* p1 = p0 + 7;
   const double s0 = p0[0], s1 = p1[0];
-  if (fabs(s1 - s0) < kDpGeomEps) {
+  if (fabs(s1 - s0) < kMathEps) {
     *left_bound = p0[5];
     *right_bound = p0[6];
     return;
@@ -144,7 +131,7 @@ CILQR_DEV bool dp_square_has_point(const DpSquare& b, double px, double py) {   
   const double x0 = px - b.cx, y0 = py - b.cy;
   const double dx = fabs(x0 * 1.0 + y0 * 0.0);
   const double dy = fabs(-x0 * 0.0 + y0 * 1.0);
-  return dx <= b.h + kDpGeomEps && dy <= b.h + kDpGeomEps;
+  return dx <= b.h + kMathEps && dy <= b.h + kMathEps;
 }
 // a placed polygon: box[4] = min_x max_x min_y max_y, pts[n][2]
 CILQR_DEV bool dp_poly_has_point(const double* box, const double* pts, int n, double px, double py) {

@@ -151,10 +151,12 @@ int cilqr_dp_plan(const cilqr_dp_config* cfg, const cilqr_scene* scene, const do
   std::vector<cilqr::CoarsePoint> out;
   const bool ok = dp.Plan(start3[0], start3[1], start3[2], &out);
   if ((int32_t)out.size() != n_knots) return CILQR_ERR_KNOTS;
+  constexpr cilqr::RowColumns C = cilqr::row_columns(CILQR_ROWS_COARSE);
   for (int i = 0; i < n_knots; ++i) {
-    double* r = coarse + (size_t)i * CILQR_COARSE_FIELDS;
+    double* r = coarse + (size_t)i * C.fields;
     const cilqr::CoarsePoint& p = out[i];
-    r[0] = p.time; r[1] = p.s; r[2] = p.x; r[3] = p.y; r[4] = p.theta; r[5] = p.kappa; r[6] = p.velocity; r[7] = p.a; r[8] = p.delta;
+    r[C.time] = p.time; r[C.station] = p.s; r[C.x] = p.x; r[C.y] = p.y; r[C.theta] = p.theta; r[C.kappa] = p.kappa;
+    r[C.v] = p.velocity; r[C.a] = p.a; r[C.delta] = p.delta;
   }
   return ok ? CILQR_OK : CILQR_ERR_NO_PATH;
 }
@@ -168,7 +170,7 @@ int cilqr_check_collisions(const cilqr_dp_config* cfg, const cilqr_scene* scene,
   if (int rc = check_scene_counts(*scene)) return rc;
 
   const AuditScene audit(*cfg, *scene);
-  const cilqr::RowLayout L = cilqr::row_layout(layout);
+  const cilqr::PoseColumns L = cilqr::pose_columns(layout);
   int first = -1, count = 0;
   for (int k = 0; k < n_knots; ++k) {
     const double* r = rows + (size_t)k * L.fields;
@@ -194,7 +196,7 @@ int cilqr_clearance_rows(const cilqr_dp_config* cfg, const cilqr_scene* scene, i
   if (int rc = check_scene_counts(*scene)) return rc;
 
   const AuditScene audit(*cfg, *scene);
-  const cilqr::RowLayout L = cilqr::row_layout(layout);
+  const cilqr::PoseColumns L = cilqr::pose_columns(layout);
   double lowest = std::numeric_limits<double>::infinity();
   int at = -1;
   for (int k = 0; k < n_knots; ++k) {

@@ -15,6 +15,7 @@
 // The image's row stride is 9 doubles: odd, so the lanes of a ds_write_b64 group spread over all banks.
 #include <algorithm>
 
+#include "../../include/cilqr/trajectory_queries.hpp"
 #include "carry.hpp"
 #include "dev_model.hpp"
 
@@ -24,33 +25,21 @@ constexpr int kCyLanes = 256;
 constexpr int kCyMaxRun = 16;                 // trajectories per workgroup, at most
 constexpr size_t kCyLdsBudget = 48 * 1024;    // ... and what their rows and images may take together
 
-// math::slerp (math_utils.h:208-225)
-CILQR_DEV double cy_slerp(double a0, double t0, double a1, double t1, double t) {
-  if (fabs(t1 - t0) <= kMathEps) return normalize_angle(a0);
-  const double a0_n = normalize_angle(a0), a1_n = normalize_angle(a1);
-  double d = a1_n - a0_n;
-  if (d > kPi) d = d - kTwoPi;
-  else if (d < -kPi) d = d + kTwoPi;
-  const double r = (t - t0) / (t1 - t0);
-  const double a = a0_n + d * r;
-  return normalize_angle(a);
-}
-
 // doubles of LDS one trajectory takes: its rows, its coarse9 image, its chord lengths
 inline size_t carry_lds_doubles(const CarryParams& P) {
   return (size_t)P.n_rows * P.fields + (size_t)P.n_live * (CILQR_COARSE_FIELDS + 1);
 }
 
-// F: doubles per row (9 coarse, 10 traj, 11 plan); time is column 0 in all three.  run: trajectories per workgroup.
+// F: doubles per row (9 coarse, 10 traj, 11 plan).  run: trajectories per workgroup.
 template <int F>
 __global__ __launch_bounds__(kCyLanes) void k_carry(CarryParams P, int run, const double* __restrict__ rows,
                                                     const double* __restrict__ advance, double* __restrict__ coarse9,
                                                     double* __restrict__ coarse6, double* __restrict__ knots3,
                                                     double* __restrict__ station, int* __restrict__ state,
                                                     int* __restrict__ n_kept) {
-  // x y theta kappa velocity a delta of a row, in the order of a coarse row's columns 2 ... 8
-  constexpr int kFrom[7] = {F == 10 ? 1 : 2, F == 10 ? 2 : 3, F == 10 ? 3 : 4, F == 10 ? 7 : 5,
-                            F == 10 ? 4 : 6, F == 10 ? 5 : 7, F == 10 ? 6 : 8};
+  constexpr RowColumns C = columns_of_fields(F);
+  constexpr int TC = C.time;
+  constexpr trajectory_queries::CarryColumns kFrom = trajectory_queries::carry_columns(C);
   extern __shared__ double s_mem[];
   __shared__ int s_state[kCyMaxRun];
   const int R = P.n_rows, K = P.n_knots, L = P.n_live;
@@ -62,20 +51,7 @@ __global__ __launch_bounds__(kCyLanes) void k_carry(CarryParams P, int run, cons
   const int np = (int)min((size_t)run, (size_t)P.batch - b0);
 
   // ---- 1. the rows of the run, and what the advances say
-  {
-    const double* __restrict__ g = rows + b0 * R * F;
-    const int n = np * R * F;
-    const int head = (int)((reinterpret_cast<uintptr_t>(g) >> 3) & 1);
-    if (head && tid == 0) s_rows[0] = g[0];
-    const int pairs = (n - head) >> 1;
-    for (int j = tid; j < pairs; j += kCyLanes) {
-      const int i = head + 2 * j;
-      const double2 v = *reinterpret_cast<const double2*>(g + i);
-      s_rows[i] = v.x;
-      s_rows[i + 1] = v.y;
-    }
-    if (((n - head) & 1) && tid == kCyLanes - 1) s_rows[n - 1] = g[n - 1];
-  }
+  stage_in<kCyLanes>(rows + b0 * R * F, s_rows, np * R * F);
   __syncthreads();
   if (tid < np) {
     const double adv = advance[b0 + tid];
@@ -83,7 +59,7 @@ __global__ __launch_bounds__(kCyLanes) void k_carry(CarryParams P, int run, cons
     int st = 0;
     if (adv < 0.0) st = 1;
     else if (!(adv <= P.max_advance)) st = 2;   // a NaN, or above the limit
-    else if (!(T[(R - 1) * F] - T[0] > 0.0)) st = 2;
+    else if (!(T[(R - 1) * F + TC] - T[TC] > 0.0)) st = 2;
     s_state[tid] = st;
   }
   __syncthreads();
@@ -95,43 +71,25 @@ __global__ __launch_bounds__(kCyLanes) void k_carry(CarryParams P, int run, cons
     bool bad = false;
     if (e < np * L && s_state[p] == 0) {
       const double* T = s_rows + p * R * F;
-      const double q = (T[0] + advance[b0 + p]) + k * P.delta_t;
-      // ---- bracket (trajectory_queries.hpp)
-      int i;
-      if (q >= T[(R - 1) * F]) {
-        i = R - 1;
-      } else if (q < T[0]) {
-        i = 0;
-      } else {
-        int lo = 0, len = R;
-        while (len > 0) {
-          const int half = len >> 1;
-          if (T[(lo + half) * F] < q) {
-            lo += half + 1;
-            len -= half + 1;
-          } else {
-            len = half;
-          }
-        }
-        i = lo;
-      }
+      const double q = (T[TC] + advance[b0 + p]) + k * P.delta_t;
+      int i = bracket(R, q, [&](int r) { return T[r * F + TC]; });
       if (i == 0) i = 1;
       if (i > R - 1) i = R - 1;
       const double* p0 = T + (i - 1) * F;
       const double* p1 = p0 + F;
       double* o = s_out + (size_t)e * CILQR_COARSE_FIELDS;
-      const double k0 = p0[0], k1 = p1[0];
+      const double k0 = p0[TC], k1 = p1[TC];
       double v[7];
       if (fabs(k1 - k0) < kMathEps) {
 #pragma unroll
-        for (int c = 0; c < 7; ++c) v[c] = p0[kFrom[c]];   // the degenerate pair: p0 as it is
+        for (int c = 0; c < 7; ++c) v[c] = p0[kFrom.col[c]];   // the degenerate pair: p0 as it is
       } else {
         const double w = (q - k0) / (k1 - k0);
         const double w1 = 1 - w;
 #pragma unroll
         for (int c = 0; c < 7; ++c) {
-          const double a = p0[kFrom[c]], z = p1[kFrom[c]];
-          v[c] = c == 2 ? cy_slerp(a, k0, z, k1, q) : w1 * a + w * z;
+          const double a = p0[kFrom.col[c]], z = p1[kFrom.col[c]];
+          v[c] = c == 2 ? slerp(a, k0, z, k1, q) : w1 * a + w * z;
         }
       }
       o[0] = P.delta_t * k;

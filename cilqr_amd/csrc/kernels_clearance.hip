@@ -73,7 +73,7 @@ CILQR_DEV void cl_edge(const double* pts, int n, int i, double* ux, double* uy, 
   const int j = i >= n - 1 ? 0 : i + 1;
   const double dx = pts[2 * j] - pts[2 * i], dy = pts[2 * j + 1] - pts[2 * i + 1];
   const double len = cl_hypot(dx, dy);
-  const bool point = len <= kDpGeomEps;
+  const bool point = len <= kMathEps;
   *ux = point ? 0.0 : dx / len;
   *uy = point ? 0.0 : dy / len;
   *length = len;
@@ -82,7 +82,7 @@ CILQR_DEV void cl_edge(const double* pts, int n, int i, double* ux, double* uy, 
 // LineSegment2d::DistanceTo (line_segment2d.cpp:61-75)
 CILQR_DEV double cl_edge_distance(double sx, double sy, double ux, double uy, double len, double ex, double ey, double px, double py) {
   const double x0 = px - sx, y0 = py - sy;
-  if (len <= kDpGeomEps) return cl_hypot(x0, y0);
+  if (len <= kMathEps) return cl_hypot(x0, y0);
   const double proj = x0 * ux + y0 * uy;
   if (proj <= 0.0) return cl_hypot(x0, y0);
   if (proj >= len) return cl_hypot(px - ex, py - ey);

@@ -39,7 +39,7 @@ CILQR_DEV double fr_hypot(double x, double y) {
 template <int F, int R>
 __global__ __launch_bounds__(kFrLanes) void k_frenet(FrenetParams P, size_t n_groups, const double* __restrict__ rows,
                                                      double* __restrict__ frenet) {
-  constexpr int XC = (F == 10) ? 1 : (F == 2) ? 0 : 2;
+  constexpr RowColumns C = columns_of_fields(F);
   static_assert(F <= CILQR_PLAN_FIELDS, "a run's rows must fit the tile");
   __shared__ double2 s_xy[kFrTile];
   __shared__ double s_tile[kFrTileDoubles];
@@ -63,8 +63,8 @@ __global__ __launch_bounds__(kFrLanes) void k_frenet(FrenetParams P, size_t n_gr
         for (int i = tid; i < n * F; i += kFrLanes) s_tile[i] = src[i];
       }
       __syncthreads();
-      px[r] = tid < n ? s_tile[tid * F + XC] : 0.0;
-      py[r] = tid < n ? s_tile[tid * F + XC + 1] : 0.0;
+      px[r] = tid < n ? s_tile[tid * F + C.x] : 0.0;
+      py[r] = tid < n ? s_tile[tid * F + C.y] : 0.0;
       nearest[r] = DBL_MAX;
       at[r] = 0;
       __syncthreads();

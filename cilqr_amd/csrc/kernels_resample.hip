@@ -25,41 +25,16 @@ constexpr int kRsRowDoubles = 3072;   // >= CILQR_DP_MAX_KNOTS * CILQR_PLAN_FIEL
 constexpr int kRsItems = 2048;        // items a workgroup aims for (8 tiles): what its staged rows are shared among
 static_assert(kRsRowDoubles >= CILQR_DP_MAX_KNOTS * CILQR_PLAN_FIELDS, "one problem must fit the row image");
 
-// math::slerp (math_utils.h:208-225)
-CILQR_DEV double rs_slerp(double a0, double t0, double a1, double t1, double t) {
-  if (fabs(t1 - t0) <= kMathEps) return normalize_angle(a0);
-  const double a0_n = normalize_angle(a0), a1_n = normalize_angle(a1);
-  double d = a1_n - a0_n;
-  if (d > kPi) d = d - kTwoPi;
-  else if (d < -kPi) d = d + kTwoPi;
-  const double r = (t - t0) / (t1 - t0);
-  const double a = a0_n + d * r;
-  return normalize_angle(a);
-}
-
-// n doubles from global `g` to LDS `s`, 16 bytes per lane and load where `g` allows
-CILQR_DEV void rs_stage_in(const double* __restrict__ g, double* s, int n) {
-  const int tid = threadIdx.x;
-  const int head = min((int)((reinterpret_cast<uintptr_t>(g) >> 3) & 1), n);
-  if (head && tid == 0) s[0] = g[0];
-  const int pairs = (n - head) >> 1;
-  for (int j = tid; j < pairs; j += kRsLanes) {
-    const int i = head + 2 * j;
-    const double2 v = *reinterpret_cast<const double2*>(g + i);
-    s[i] = v.x;
-    s[i + 1] = v.y;
-  }
-  if (((n - head) & 1) && tid == kRsLanes - 1) s[n - 1] = g[n - 1];
-}
-
-// F: doubles per row (9 coarse, 10 traj, 11 plan); theta at 3 (traj) or 4; the two controls last, where there are any
+// F: doubles per row (9 coarse, 10 traj, 11 plan); the two controls are the last columns, where there are any
 template <int F>
 __global__ __launch_bounds__(kRsLanes) void k_resample(ResampleParams P, int probs_per_wg, unsigned chunk,
                                                        const double* __restrict__ rows, const double* __restrict__ queries,
                                                        double* __restrict__ out) {
+  constexpr RowColumns C = columns_of_fields(F);
   constexpr int FS = F | 1;
-  constexpr int TH = (F == 10) ? 3 : 4;
-  constexpr int CTRL = (F == 9) ? F : F - 2;   // first control column; F: none
+  constexpr int TH = C.theta;
+  constexpr int CTRL = C.jerk < 0 ? F : C.jerk;   // first control column; F: none
+  static_assert(C.time < 2 && C.station < 2 && CTRL >= F - 2, "a key is one of the first two columns, the controls the last two");
   __shared__ double s_rows[kRsRowDoubles];
   __shared__ double s_out[kRsLanes * FS];
   const int tid = threadIdx.x;
@@ -73,7 +48,7 @@ __global__ __launch_bounds__(kRsLanes) void k_resample(ResampleParams P, int pro
   const unsigned c1 = (n_items - c0 < chunk) ? n_items : c0 + chunk;
   if (c0 >= c1) return;   // the last run of a batch can be shorter than the grid's second dimension covers
 
-  rs_stage_in(rows + (size_t)b0 * K * F, s_rows, np * K * F);
+  stage_in<kRsLanes>(rows + (size_t)b0 * K * F, s_rows, np * K * F);
   __syncthreads();
 
   for (unsigned t0 = c0; t0 < c1; t0 += kRsLanes) {
@@ -83,25 +58,7 @@ __global__ __launch_bounds__(kRsLanes) void k_resample(ResampleParams P, int pro
       const unsigned p = e / M, m = e - p * M;
       const double q = P.per_problem ? queries[(size_t)(b0 + p) * M + m] : queries[m];
       const double* R = s_rows + (int)p * K * F;
-      // ---- bracket
-      int i;
-      if (q >= R[(K - 1) * F + kc]) {
-        i = K - 1;
-      } else if (q < R[kc]) {
-        i = 0;
-      } else {
-        int first = 0, len = K;
-        while (len > 0) {
-          const int half = len >> 1;
-          if (R[(first + half) * F + kc] < q) {
-            first += half + 1;
-            len -= half + 1;
-          } else {
-            len = half;
-          }
-        }
-        i = first;
-      }
+      int i = bracket(K, q, [&](int r) { return R[r * F + kc]; });
       if (i == 0) i = 1;
       if (i > K - 1) i = K - 1;
       const double* p0 = R + (i - 1) * F;
@@ -118,7 +75,7 @@ __global__ __launch_bounds__(kRsLanes) void k_resample(ResampleParams P, int pro
         for (int c = 0; c < F; ++c) {
           const double a = p0[c];
           double v;
-          if (c == TH) v = rs_slerp(a, k0, p1[c], k1, q);
+          if (c == TH) v = slerp(a, k0, p1[c], k1, q);
           else if (c >= CTRL) v = a;
           else {
             v = w1 * a + w * p1[c];

@@ -269,9 +269,10 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_rows(int K, const double* _
   const int tid = threadIdx.x;
   const double* in = traj + (size_t)blockIdx.x * K * CILQR_TRAJ_FIELDS;
   double* out = plan + (size_t)blockIdx.x * K * CILQR_PLAN_FIELDS;
+  constexpr RowColumns kTraj = row_columns(CILQR_ROWS_TRAJ), kPlan = row_columns(CILQR_ROWS_PLAN);
   for (int k = tid; k < K; k += kPlanBlock)
-    s_len[k] = k > 0 ? hypot_ref(in[k * CILQR_TRAJ_FIELDS + 1] - in[(k - 1) * CILQR_TRAJ_FIELDS + 1],
-                                 in[k * CILQR_TRAJ_FIELDS + 2] - in[(k - 1) * CILQR_TRAJ_FIELDS + 2])
+    s_len[k] = k > 0 ? hypot_ref(in[k * CILQR_TRAJ_FIELDS + kTraj.x] - in[(k - 1) * CILQR_TRAJ_FIELDS + kTraj.x],
+                                 in[k * CILQR_TRAJ_FIELDS + kTraj.y] - in[(k - 1) * CILQR_TRAJ_FIELDS + kTraj.y])
                      : 0.0;
   __syncthreads();
   if (tid == 0) {
@@ -282,11 +283,11 @@ __global__ __launch_bounds__(kPlanBlock) void k_plan_rows(int K, const double* _
     }
   }
   __syncthreads();
-  // plan: time s x y theta kappa velocity a delta jerk delta_rate <- traj: time x y theta v a delta kappa jerk delta_rate
-  const int from[CILQR_PLAN_FIELDS] = {0, -1, 1, 2, 3, 7, 4, 5, 6, 8, 9};
+  // every column of a plan row from the CILQR_ROWS_TRAJ column of the same name; the station is the running chord length
+  constexpr ColumnMap from = column_map(kPlan, kTraj);
   for (int i = tid; i < K * CILQR_PLAN_FIELDS; i += kPlanBlock) {
     const int k = i / CILQR_PLAN_FIELDS, c = i - k * CILQR_PLAN_FIELDS;
-    out[i] = c == 1 ? s_len[k] : in[k * CILQR_TRAJ_FIELDS + from[c]];
+    out[i] = c == kPlan.station ? s_len[k] : in[k * CILQR_TRAJ_FIELDS + from.col[c]];
   }
 }
 

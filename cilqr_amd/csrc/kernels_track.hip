@@ -31,8 +31,8 @@ template <int F>
 __global__ __launch_bounds__(kTgLanes) void k_track_gather(TrackParams P, const double* __restrict__ rows,
                                                            const double* __restrict__ start6, FollowTable tab) {
   constexpr int S = kTgKnots * F + 1;            // odd for every F here (81, 89, 73)
-  constexpr bool kChord = F == 10;               // CILQR_ROWS_TRAJ has no station column
-  constexpr int XC = kChord ? 1 : 2, TH = kChord ? 3 : 4, VC = kChord ? 4 : 6, AC = kChord ? 5 : 7, DC = kChord ? 6 : 8;
+  constexpr RowColumns C = columns_of_fields(F);
+  constexpr bool kChord = C.station < 0;         // CILQR_ROWS_TRAJ has no station column
   __shared__ double tile[kTgProblems * S];
   const int tid = threadIdx.x;
   const int K = P.n_knots;
@@ -51,22 +51,22 @@ __global__ __launch_bounds__(kTgLanes) void k_track_gather(TrackParams P, const 
       for (int kk = 0; kk < kt; ++kk) {
         const double* r = tile + tid * S + kk * F;
         const int k = k0 + kk;
-        const double x = r[XC], y = r[XC + 1];
+        const double x = r[C.x], y = r[C.y];
         double station;
-        if (kChord) {
+        if constexpr (kChord) {
           if (k > 0) acc = acc + hypot_ref(x - px, y - py);
           station = acc;
           px = x;
           py = y;
         } else {
-          station = r[1];
+          station = r[C.station];
         }
         const size_t at = (size_t)k * tab.stride + col;
         tab.xy[at] = make_double2(x, y);
-        tab.thv[at] = make_double2(r[TH], r[VC]);
-        tab.ts[at] = make_double2(r[0], station);
+        tab.thv[at] = make_double2(r[C.theta], r[C.v]);
+        tab.ts[at] = make_double2(r[C.time], station);
         if (k == 0) {
-          double s6[6] = {x, y, r[TH], r[VC], r[AC], r[DC]};
+          double s6[6] = {x, y, r[C.theta], r[C.v], r[C.a], r[C.delta]};
           if (start6 != nullptr) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) s6[c] = start6[col * 6 + c];
@@ -112,19 +112,7 @@ struct TableFollow {
   CILQR_DEV double time(int i) const { return t.ts[(size_t)i * t.stride + col].x; }
   // the bracket of include/cilqr.h ("resample") on the time column, before its `i == 0 -> 1`
   CILQR_DEV int locate(double q) const {
-    if (q >= time(K - 1)) return K - 1;
-    if (q < time(0)) return 0;
-    int first = 0, len = K;
-    while (len > 0) {
-      const int half = len >> 1;
-      if (time(first + half) < q) {
-        first += half + 1;
-        len -= half + 1;
-      } else {
-        len = half;
-      }
-    }
-    return min(first, K - 1);   // (not reached beyond K - 1: q < time[K-1] here)
+    return min(bracket(K, q, [&](int i) { return time(i); }), K - 1);   // (not reached beyond K - 1: q < time[K-1] here)
   }
 };
 

@@ -1,5 +1,5 @@
-// Private to cilqr_amd/csrc: what margins_batch.hip (the entry points) and kernels_margins.hip share -- where a row layout
-// keeps what the rule reads, the parameters of a launch, the launch functions -- and the device statement of the plane
+// Private to cilqr_amd/csrc: what margins_batch.hip (the entry points) and kernels_margins.hip share -- the parameters of
+// a launch, the launch functions -- and the device statement of the plane
 // arithmetic the margins are taken from: ShrinkConstraints + NormalizeHalfPlane as k_load_corridor / k_load_lanes
 // (kernels_load.hip) evaluate them, written a second time here so that the load kernels stay as they are;
 // tests/test_gpu_margins.py pins the two copies to each other through cilqr_stage_read.
@@ -15,25 +15,11 @@ namespace cilqr {
 constexpr int kMgLanes = 256;       // lanes of a workgroup
 constexpr int kMgKnotTile = 128;    // knots of a problem in LDS at a time
 
-// doubles per row and the columns of the pose, the state and the controls (CILQR_ROWS_*); fields = 0: no such layout,
-// jerk = -1: the layout has no controls
-struct MarginRows {
-  int fields, x, y, theta, v, a, delta, jerk, rate;
-};
-inline MarginRows margin_rows(int layout) {
-  switch (layout) {
-    case CILQR_ROWS_TRAJ: return MarginRows{CILQR_TRAJ_FIELDS, 1, 2, 3, 4, 5, 6, 8, 9};
-    case CILQR_ROWS_PLAN: return MarginRows{CILQR_PLAN_FIELDS, 2, 3, 4, 6, 7, 8, 9, 10};
-    case CILQR_ROWS_COARSE: return MarginRows{CILQR_COARSE_FIELDS, 2, 3, 4, 6, 7, 8, -1, -1};
-  }
-  return MarginRows{0, 0, 0, 0, 0, 0, 0, -1, -1};
-}
-
 struct MarginParams {
   Params p;              // the handle's: bounds, disc_off, shrink_corridor, shrink_lane
   int exact_ties;        // CILQR_OPT_EXACT_LANE_TIES as in force
   int n_knots, cmax;     // of the call's problem batch
-  MarginRows rows;
+  StateColumns rows;     // what the rule reads of a row (row_layouts.hpp)
   double tol[CILQR_MARGIN_FIELDS];
 };
 

@@ -27,7 +27,7 @@ int check_margin_call(const cilqr_problem_batch* in, int32_t layout, const doubl
                       std::vector<LaneGroup>* groups) {
   if (in == nullptr || rows == nullptr || min_margin == nullptr || min_knot == nullptr || violated == nullptr)
     return CILQR_ERR_NULL;
-  if (in->batch < 1 || in->n_knots < 1 || margin_rows(layout).fields == 0) return CILQR_ERR_ARG;
+  if (in->batch < 1 || in->n_knots < 1 || state_columns(layout).fields == 0) return CILQR_ERR_ARG;
   if (in->memory != CILQR_MEM_HOST && in->memory != CILQR_MEM_DEVICE) return CILQR_ERR_ARG;
   if (tol != nullptr)
     for (int f = 0; f < CILQR_MARGIN_FIELDS; ++f)
@@ -106,7 +106,7 @@ extern "C" int cilqr_constraint_margins_batch(cilqr_handle h, const cilqr_proble
   P.exact_ties = h->ds.exact_ties;
   P.n_knots = in->n_knots;
   P.cmax = in->cmax;
-  P.rows = margin_rows(layout);
+  P.rows = state_columns(layout);
   for (int f = 0; f < CILQR_MARGIN_FIELDS; ++f) P.tol[f] = tol ? tol[f] : 0.0;
 
   HIP_TRY(hipSetDevice(h->device));

@@ -9,7 +9,7 @@ namespace cilqr {
 
 struct ResampleParams {
   int batch, n_knots, n_queries;   // B, K (2 ... CILQR_DP_MAX_KNOTS), M
-  int fields;                      // 9, 10 or 11: the layout (trajectory_queries.hpp: columns_of)
+  int fields;                      // 9, 10 or 11: the layout (row_layouts.hpp)
   int key_col;                     // 0 or 1
   int per_problem;                 // queries [B][M] instead of [M]
 };

@@ -6,15 +6,21 @@
 #include <cstring>
 
 #include "../../include/cilqr.h"
+#include "../../include/cilqr/row_layouts.hpp"
+
+static_assert(cilqr::row_columns(CILQR_ROWS_TRAJ).fields == CILQR_TRAJ_FIELDS && cilqr::row_columns(CILQR_ROWS_PLAN).fields == CILQR_PLAN_FIELDS &&
+                  cilqr::row_columns(CILQR_ROWS_COARSE).fields == CILQR_COARSE_FIELDS && cilqr::row_columns(CILQR_ROWS_CONTROLS).fields == CILQR_NU &&
+                  cilqr::row_columns(CILQR_ROWS_POINTS).fields == 2 && cilqr::kMaxRowFields == CILQR_PLAN_FIELDS,
+              "row_layouts.hpp states the layouts of cilqr.h");
 
 // doubles per row, rows per problem and first control column of a warm layout (n_knots = N + 1); false: no such layout
 inline bool cilqr_warm_geometry(int32_t layout, int32_t n_knots, int* stride, int* rows_per, int* col) {
-  switch (layout) {
-    case CILQR_ROWS_TRAJ: *stride = CILQR_TRAJ_FIELDS; *rows_per = n_knots; *col = 8; return true;
-    case CILQR_ROWS_PLAN: *stride = CILQR_PLAN_FIELDS; *rows_per = n_knots; *col = 9; return true;
-    case CILQR_ROWS_CONTROLS: *stride = CILQR_NU; *rows_per = n_knots - 1; *col = 0; return true;
-    default: return false;   // CILQR_ROWS_COARSE carries no controls
-  }
+  const cilqr::RowColumns c = cilqr::row_columns(layout);
+  if (c.jerk < 0) return false;   // CILQR_ROWS_COARSE and CILQR_ROWS_POINTS carry no controls
+  *stride = c.fields;
+  *rows_per = layout == CILQR_ROWS_CONTROLS ? n_knots - 1 : n_knots;   // a control per step; a trajectory row per knot
+  *col = c.jerk;
+  return true;
 }
 
 namespace cilqr {

@@ -513,7 +513,6 @@ void apply_tracker_config(cilqr_solver* h, const cilqr_tracker_config* c) {   //
 // K - 1 knots?  Where it does not the reference gives up ("tacker failed", cc:205-208).  At most CILQR_TRACKER_MAX_SIM_STEPS + 2
 // rounds: the caller has bounded end_time / sim_dt.
 bool tracker_clock_passes_every_knot(int K, double knot_dt, double sim_dt) {
-  constexpr double kMathEps = 1e-10;   // algorithm/math/vec2d.h:33 (dev_model.hpp)
   const double start_time = knot_dt * 0, end_time = knot_dt * (K - 1);
   int i = 1;
   for (double t = start_time; t < end_time + kMathEps; t += sim_dt)

@@ -103,16 +103,6 @@ CILQR_DEV void solve_lqr(const M3& A, const double* B, const M3& Q, double R, do
   for (int j = 0; j < 3; ++j) K[j] = inv * (BTPA[j] + 0.0);
 }
 
-CILQR_DEV double slerp(double a0, double t0, double a1, double t1, double t) {   // math_utils.h:208-225
-  if (fabs(t1 - t0) <= kMathEps) return normalize_angle(a0);
-  const double a0_n = normalize_angle(a0), a1_n = normalize_angle(a1);
-  double d = a1_n - a0_n;
-  if (d > kPi) d = d - 2 * kPi;
-  else if (d < -kPi) d = d + 2 * kPi;
-  const double r = (t - t0) / (t1 - t0);
-  return normalize_angle(a0_n + d * r);
-}
-
 struct FollowPt {
   double s, x, y, theta, v;
 };

@@ -554,6 +554,7 @@ int cilqr_dp_plan(const cilqr_dp_config* cfg, const cilqr_scene* scene, const do
 #define CILQR_ROWS_TRAJ 0     /* [K][CILQR_TRAJ_FIELDS]    time 0, x 1, y 2, theta 3 */
 #define CILQR_ROWS_PLAN 1     /* [K][CILQR_PLAN_FIELDS]    time 0, x 2, y 3, theta 4 */
 #define CILQR_ROWS_COARSE 2   /* [K][CILQR_COARSE_FIELDS]  time 0, x 2, y 3, theta 4 */
+/* (every column of every CILQR_ROWS_* layout is stated once for the code: include/cilqr/row_layouts.hpp) */
 #define CILQR_HIT_REAR_STATIC 1     /* mask bits: the rear disc against a static polygon, */
 #define CILQR_HIT_REAR_BARRIER 2    /*            a road barrier point,                   */
 #define CILQR_HIT_REAR_DYNAMIC 4    /*            a dynamic polygon;                      */
@@ -860,7 +861,8 @@ int cilqr_clearance_rows_batch(cilqr_handle h, const cilqr_dp_config* cfg, const
  *                  steering rate are +inf at the last knot, and at every knot of a layout without control columns.
  *   NaN            a NaN margin is replaced by -inf before any comparison: a NaN pose never passes as feasible.
  *   columns read   CILQR_ROWS_TRAJ x 1 y 2 theta 3 v 4 a 5 delta 6 jerk 8 rate 9;  CILQR_ROWS_PLAN x 2 y 3 theta 4 v 6 a 7
- *                  delta 8 jerk 9 rate 10;  CILQR_ROWS_COARSE x 2 y 3 theta 4 v 6 a 7 delta 8, no controls.
+ *                  delta 8 jerk 9 rate 10;  CILQR_ROWS_COARSE x 2 y 3 theta 4 v 6 a 7 delta 8, no controls.  (The code takes
+ *                  these numbers from include/cilqr/row_layouts.hpp: state_columns.)
  *   which          (optional) [K][CILQR_MARGIN_WHICH_FIELDS]: the deciders -- corridor disc, corridor plane, left disc, left
  *                  segment, right disc, right segment (segments counted within the side's table of the problem's lane
  *                  group); -1 where the column is +inf.
@@ -1165,7 +1167,8 @@ int cilqr_predict_scenes_batch(cilqr_handle h, const cilqr_scene_batch* scenes, 
  *                                     summed in knot order (the hypot of the `plan` rows of cilqr_plan_scenes_batch);
  *                                     coarse6, knots3 and station are the projections cilqr_dp_plan_batch writes.
  *   columns read   CILQR_ROWS_TRAJ x 1 y 2 theta 3 v 4 a 5 delta 6 kappa 7;  CILQR_ROWS_PLAN and _COARSE x 2 y 3 theta 4
- *                  kappa 5 v 6 a 7 delta 8.
+ *                  kappa 5 v 6 a 7 delta 8.  (The code takes these numbers from include/cilqr/row_layouts.hpp through
+ *                  trajectory_queries.hpp: carry_columns.)
  * cilqr_carry_rows: one trajectory on the host, no handle (C++ callers use include/cilqr/trajectory_queries.hpp: carry_rows).
  *   coarse9 [n_knots][CILQR_COARSE_FIELDS], coarse6 [n_knots][6], knots3 [n_knots][3], station [n_knots]: each optional
  * CILQR_ERR_NULL (rows, state); CILQR_ERR_ARG for an unknown layout, n_rows < 2, n_knots < 1, a delta_t that is not positive,

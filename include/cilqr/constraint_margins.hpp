@@ -13,6 +13,8 @@
 #include <limits>
 #include <vector>
 
+#include "row_layouts.hpp"
+
 namespace cilqr {
 namespace constraint_margins {
 
@@ -23,19 +25,9 @@ constexpr int kMaxDiscs = 16;
 constexpr double kMathEpsilon = 1e-10;   // algorithm/math/vec2d.h:33
 constexpr double kInf = std::numeric_limits<double>::infinity();
 
-// where a row layout (CILQR_ROWS_TRAJ 0 / _PLAN 1 / _COARSE 2) keeps what the rule reads; fields = 0: no such layout,
-// jerk = -1: the layout has no control columns
-struct Columns {
-  int fields, x, y, theta, v, a, delta, jerk, rate;
-};
-inline Columns columns_of(int layout) {
-  switch (layout) {
-    case 0: return Columns{10, 1, 2, 3, 4, 5, 6, 8, 9};
-    case 1: return Columns{11, 2, 3, 4, 6, 7, 8, 9, 10};
-    case 2: return Columns{9, 2, 3, 4, 6, 7, 8, -1, -1};
-  }
-  return Columns{0, 0, 0, 0, 0, 0, 0, -1, -1};
-}
+// what the rule reads of a row (row_layouts.hpp); fields = 0: no such layout, jerk = -1: the layout has no control columns
+using Columns = StateColumns;
+constexpr Columns columns_of(int layout) { return state_columns(layout); }
 
 // hypot as the reference's C library evaluates it for lengths in metres (glibc's e_hypot.c without FMA): the square root
 // of the sum of squares, corrected by one Newton step.  Written out so that the value does not depend on the C library

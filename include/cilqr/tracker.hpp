@@ -134,18 +134,9 @@ inline void solve_lqr(const double* A, const double* B, const double* Q, double 
   for (int j = 0; j < 3; ++j) K[j] = inv * (BTPA[j] + 0.0);
 }
 
-// the columns of a layout the rule reads; x_col < 0: no such layout
-struct FollowColumns {
-  int fields, time, station, x, theta, v, a, delta;   // y follows x; station < 0: chord length
-};
-inline FollowColumns follow_columns(int layout) {
-  switch (layout) {
-    case 0: return FollowColumns{10, 0, -1, 1, 3, 4, 5, 6};
-    case 1: return FollowColumns{11, 0, 1, 2, 4, 6, 7, 8};
-    case 2: return FollowColumns{9, 0, 1, 2, 4, 6, 7, 8};
-  }
-  return FollowColumns{0, 0, -1, -1, 0, 0, 0, 0};
-}
+// the columns of a trajectory layout (row_layouts.hpp); fields = 0: no such layout.  station < 0: chord length
+using FollowColumns = RowColumns;
+constexpr FollowColumns follow_columns(int layout) { return trajectory_columns(layout); }
 
 // One trajectory: rows [n_knots][fields] of `layout`, start6 (or nullptr: row 0) -> driven [n_drive][10].  The arguments are
 // taken as checked (cilqr_track_rows).  true: n_drive rows were recorded; false: the failure of the rule, `driven` all zero.
@@ -160,7 +151,7 @@ inline bool track_rows(const Config& cfg, const Vehicle& veh, int layout, const 
   double *ft = tab.data(), *fs = ft + K, *fx = fs + K, *fy = fx + K, *fth = fy + K, *fv = fth + K;
   for (int k = 0; k < K; ++k) {
     const double* r = rows + (size_t)k * F;
-    ft[k] = r[c.time]; fx[k] = r[c.x]; fy[k] = r[c.x + 1]; fth[k] = r[c.theta]; fv[k] = r[c.v];
+    ft[k] = r[c.time]; fx[k] = r[c.x]; fy[k] = r[c.y]; fth[k] = r[c.theta]; fv[k] = r[c.v];
     if (c.station >= 0) fs[k] = r[c.station];
   }
   if (c.station < 0) {
@@ -185,7 +176,7 @@ inline bool track_rows(const Config& cfg, const Vehicle& veh, int layout, const 
   if (start6 != nullptr) {
     cx = start6[0]; cy = start6[1]; cth = start6[2]; cv = start6[3]; ca = start6[4]; cdl = start6[5];
   } else {
-    cx = rows[c.x]; cy = rows[c.x + 1]; cth = rows[c.theta]; cv = rows[c.v]; ca = rows[c.a]; cdl = rows[c.delta];
+    cx = rows[c.x]; cy = rows[c.y]; cth = rows[c.theta]; cv = rows[c.v]; ca = rows[c.a]; cdl = rows[c.delta];
   }
   const double L = veh.wheel_base;
   auto record = [&](int i, double time) {

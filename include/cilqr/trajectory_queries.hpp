@@ -13,24 +13,17 @@
 #include <cstdint>
 #include <cstring>
 
+#include "row_layouts.hpp"
+
 namespace cilqr {
 namespace trajectory_queries {
 
 constexpr double kPi = 3.14159265358979323846;   // M_PI
 constexpr double kMathEpsilon = 1e-10;            // algorithm/math/vec2d.h:33
 
-// where a row layout (CILQR_ROWS_TRAJ 0 / _PLAN 1 / _COARSE 2) keeps what the rule names; fields = 0: no such layout
-struct Columns {
-  int fields, time, station, theta, control;   // station / control = -1: the layout has none; the controls are two columns
-};
-inline Columns columns_of(int layout) {
-  switch (layout) {
-    case 0: return Columns{10, 0, -1, 3, 8};
-    case 1: return Columns{11, 0, 1, 4, 9};
-    case 2: return Columns{9, 0, 1, 4, -1};
-  }
-  return Columns{0, 0, -1, 0, -1};
-}
+// the columns of a trajectory layout (CILQR_ROWS_TRAJ 0 / _PLAN 1 / _COARSE 2, row_layouts.hpp); fields = 0: no such layout
+using Columns = RowColumns;
+constexpr Columns columns_of(int layout) { return trajectory_columns(layout); }
 // the key column of (layout, key) with key = CILQR_KEY_TIME 0 / CILQR_KEY_STATION 1; -1: no such pair
 inline int key_column(int layout, int key) {
   const Columns c = columns_of(layout);
@@ -96,7 +89,7 @@ inline void interpolate(const Columns& c, int key_col, const double* p0, const d
       out[f] = q;
     } else if (f == c.theta) {
       out[f] = slerp(p0[f], k0, p1[f], k1, q);
-    } else if (c.control >= 0 && (f == c.control || f == c.control + 1)) {
+    } else if (f == c.jerk || f == c.rate) {
       std::memcpy(out + f, p0 + f, sizeof(double));   // a control holds over its step
     } else {
       out[f] = (1 - w) * p0[f] + w * p1[f];
@@ -119,18 +112,18 @@ inline void resample_rows(int layout, const double* rows, int n_knots, int key, 
 // ---- carry: a trajectory of the previous cycle as the coarse trajectory of the next: the host statement of cilqr_carry_rows
 // and cilqr_carry_rows_batch.  The rule is stated in include/cilqr.h ("carry").
 constexpr int kCoarseFields = 9;   // time s x y theta kappa velocity a delta
-// where a layout keeps x y theta kappa velocity a delta, in that order (the columns 2 ... 8 of a coarse row)
-inline const int* carry_columns(int layout) {
-  static const int traj[7] = {1, 2, 3, 7, 4, 5, 6}, plan[7] = {2, 3, 4, 5, 6, 7, 8};
-  return layout == 0 ? traj : plan;
-}
+// what a coarse row takes from a row, in the order of its columns 2 ... 8
+struct CarryColumns {
+  int col[7];
+};
+constexpr CarryColumns carry_columns(const RowColumns& c) { return CarryColumns{{c.x, c.y, c.theta, c.kappa, c.v, c.a, c.delta}}; }
 
 // rows [n_rows][fields] -> coarse9 [n_knots][9], coarse6 [n_knots][6], knots3 [n_knots][3], station [n_knots] (each may be
 // null); returns the state (0 kept, 1 not asked, 2 refused).  The arguments are taken as checked (cilqr_carry_rows).
 inline int carry_rows(int layout, const double* rows, int n_rows, double advance, double max_advance, int n_knots,
                       double delta_t, double* coarse9, double* coarse6, double* knots3, double* station) {
   const Columns c = columns_of(layout);
-  const int* from = carry_columns(layout);
+  const CarryColumns from = carry_columns(c);
   int state = 0;
   if (advance < 0.0) state = 1;
   else if (!(advance <= max_advance)) state = 2;                                          // a NaN, or above the limit
@@ -146,7 +139,7 @@ inline int carry_rows(int layout, const double* rows, int n_rows, double advance
       interpolate(c, c.time, rows + (size_t)(i - 1) * c.fields, rows + (size_t)i * c.fields, q, r);
       double* o = nine + (size_t)k * kCoarseFields;
       o[0] = delta_t * k;
-      for (int e = 0; e < 7; ++e) std::memcpy(o + 2 + e, r + from[e], sizeof(double));
+      for (int e = 0; e < 7; ++e) std::memcpy(o + 2 + e, r + from.col[e], sizeof(double));
       if (k > 0) s = s + std::hypot(o[2] - o[2 - kCoarseFields], o[3] - o[3 - kCoarseFields]);
       o[1] = s;
       finite = finite && std::isfinite(o[2]) && std::isfinite(o[3]) && std::isfinite(o[4]) && std::isfinite(o[6]) &&
@@ -173,15 +166,13 @@ inline int carry_rows(int layout, const double* rows, int n_rows, double advance
 constexpr int kCenterFields = 7;
 constexpr int kFrenetFields = 8;   // station, lateral, then x y theta kappa left_bound right_bound of the projected point
 
-// where a layout keeps x (y follows it) and how many doubles a row has; layout 4 is CILQR_ROWS_POINTS.  false: no such layout
+// where a layout keeps x (y follows it) and how many doubles a row has; CILQR_ROWS_POINTS too.  false: no such layout
 inline bool point_columns(int layout, int* fields, int* x_col) {
-  switch (layout) {
-    case 0: *fields = 10; *x_col = 1; return true;
-    case 1: *fields = 11; *x_col = 2; return true;
-    case 2: *fields = 9; *x_col = 2; return true;
-    case 4: *fields = 2; *x_col = 0; return true;
-  }
-  return false;
+  const RowColumns c = row_columns(layout);
+  if (c.x < 0) return false;   // CILQR_ROWS_CONTROLS and every unknown layout
+  *fields = c.fields;
+  *x_col = c.x;
+  return true;
 }
 
 // sin and cos of one angle as the reference's build evaluates them: g++ -O2 turns its std::sin / std::cos of one argument
