@@ -150,6 +150,7 @@ PREDICT_HOLD, PREDICT_CONSTANT_VELOCITY = 0, 1   # CILQR_PREDICT_* (include/cilq
 # cilqr_frenet_rows / cilqr_frenet_rows_batch: plain [K][2] x, y rows (CILQR_ROWS_POINTS; these two calls only), the doubles
 # of a centre-line row and of a result row (CILQR_FRENET_FIELDS), doubles per row of every layout they accept
 ROWS_POINTS = 4
+POLICY_MAX_SAMPLES = 256   # CILQR_POLICY_MAX_SAMPLES: starts per problem of one policy_rollout
 CENTER_FIELDS, FRENET_FIELDS = 7, 8
 FRENET_ROWS_FIELDS = {**ROWS_FIELDS, ROWS_POINTS: 2}
 # cilqr_clearance_rows / cilqr_clearance_rows_batch: the columns of a knot's row (CILQR_CLEARANCE_FIELDS)
@@ -199,6 +200,7 @@ EXPORTS = [
     "cilqr_clearance_rows", "cilqr_clearance_rows_batch",
     "cilqr_constraint_margins", "cilqr_constraint_margins_batch",
     "cilqr_track_rows", "cilqr_track_rows_batch",
+    "cilqr_policy_gains_batch", "cilqr_policy_rollout_batch",
     "cilqr_window_scene", "cilqr_window_scenes_batch", "cilqr_plan_scenes_batch_warm",
     "cilqr_predict_scene", "cilqr_predict_scenes_batch",
     "cilqr_carry_rows", "cilqr_carry_rows_batch", "cilqr_plan_scenes_batch_carry",
@@ -334,6 +336,11 @@ def lib():
                                        C.c_int32, C.c_void_p]
         L.cilqr_track_rows_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                              C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
+        L.cilqr_policy_gains_batch.argtypes = [C.c_void_p, C.POINTER(ProblemBatch), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cilqr_policy_rollout_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_double, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_int32]
         L.cilqr_default_tracker_config.argtypes = [C.POINTER(TrackerConfig)]
         L.cilqr_default_tracker_config.restype = None
         L.cilqr_set_tracker_config.argtypes = [C.c_void_p, C.POINTER(TrackerConfig)]
@@ -1229,6 +1236,90 @@ class BatchIlqrOptimizer:
         rc = self.L.cilqr_track_rows_batch(self.h, batch, layout, rows_ptr, n_knots, start6_ptr, n_drive, driven_ptr, ok_ptr,
                                            C.byref(n), memory)
         return rc, int(n.value)
+
+    def policy_gains(self, scene_or_problem, rows, layout: int, lam=None):
+        """The feedback law of one iLQR iteration about a batch of trajectories (cilqr_policy_gains_batch), host arrays: the
+        stage chain load -> rows as the iterate -> quadratize -> backward(lam) -> read, bit for bit.  scene_or_problem: the dict
+        a plan() takes; rows [B,K,F] in ROWS_TRAJ / ROWS_PLAN with K = n_steps + 1; lam: None (0), a number or [B].  Returns
+        dict(Kfb [B,N,2,6], kff [B,N,2], dV [B,2], ok [B] int32 -- 0: a knot without corridor, the problem's outputs are
+        zeros).  Afterwards the handle is in that chain's staged state (read() works)."""
+        rows = _f64(rows)
+        if rows.ndim != 3 or rows.shape[2] != ROWS_FIELDS.get(layout, rows.shape[2]):
+            raise ValueError(f"rows must be [B, K, {ROWS_FIELDS.get(layout)}]")
+        prob, keep = self._host_problem(scene_or_problem)
+        B, N = prob.batch, self.N
+        if rows.shape[0] != B:
+            raise ValueError(f"rows must be [{B}, K, F]")
+        if lam is not None:
+            lam = _f64(np.broadcast_to(lam, (B,)))
+        out = dict(Kfb=np.zeros((B, N, 2, 6)), kff=np.zeros((B, N, 2)), dV=np.zeros((B, 2)), ok=np.zeros(B, np.int32))
+        rc = self.policy_gains_raw(prob, layout, _ptr(rows), _ptr(lam), _ptr(out["Kfb"]), _ptr(out["kff"]), _ptr(out["dV"]),
+                                   _ptr(out["ok"]))
+        self._chk(rc, "policy_gains")
+        self.B = B
+        self.nl, self.nr = prob.n_left, prob.n_right
+        return out
+
+    def policy_gains_raw(self, prob: ProblemBatch, layout, rows_ptr, lambda_ptr, kfb_ptr, kff_ptr, dv_ptr=None, ok_ptr=None) -> int:
+        """Pointer-level form: rows, lambda and the outputs in device or host memory as prob.memory says (a solve's traj is
+        linearised where it lies; lambda_ptr, dv_ptr and ok_ptr may be None); returns the code."""
+        return self.L.cilqr_policy_gains_batch(self.h, C.byref(prob) if prob is not None else None, layout, rows_ptr, lambda_ptr,
+                                               kfb_ptr, kff_ptr, dv_ptr, ok_ptr)
+
+    def policy_rollout(self, rows, layout: int, Kfb, start6, kff=None, alpha: float = 0.0, clamp: bool = False,
+                       n_out: "int | None" = None, rows_out: bool = True):
+        """Closed-loop rollouts of a batch of plans under their feedback gains from starts of the caller's choosing, on the
+        GPU (cilqr_policy_rollout_batch; the rule: cilqr_amd/policy.py).  rows [B,K,F] nominal in ROWS_TRAJ / ROWS_PLAN, Kfb
+        [B,K-1,2,6], kff [B,K-1,2] or None (then alpha is not read), start6 [S,B,6] (or [B,6]: one sample); clamp: controls
+        limited to the handle's jerk and steering-rate bounds; n_out (None: K) rows are recorded.  NumPy arrays, or contiguous
+        float64 device tensors (all of the same kind).  Returns dict(rows [S,B,n_out,10] in ROWS_TRAJ layout (None with
+        rows_out=False: summaries only), max_dev [S,B], end_dev [S,B], n_clamped [S,B] int32) of that kind; slice s of rows is a
+        batch the audits, the margins, resample and a warm start take as it is."""
+        given = [a for a in (rows, Kfb, start6, kff) if a is not None]
+        on_device = _is_device_tensor(rows)
+        if any(_is_device_tensor(a) != on_device for a in given):
+            raise ValueError("rows, Kfb, kff and start6 must all be NumPy arrays or all device tensors")
+        if on_device:
+            for t in given:
+                if not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64":
+                    raise ValueError("rows / Kfb / kff / start6 on the device: contiguous float64 tensors")
+        else:
+            rows, Kfb, start6 = _f64(rows), _f64(Kfb), _f64(start6)
+            kff = None if kff is None else _f64(kff)
+        if rows.ndim != 3 or rows.shape[2] != ROWS_FIELDS.get(layout, rows.shape[2]):
+            raise ValueError(f"rows must be [B, K, {ROWS_FIELDS.get(layout)}]")
+        B, K = int(rows.shape[0]), int(rows.shape[1])
+        if start6.ndim == 2:
+            start6 = start6.reshape(1, *start6.shape)
+        if start6.ndim != 3 or tuple(start6.shape[1:]) != (B, 6):
+            raise ValueError(f"start6 must be [S, {B}, 6]")
+        S = int(start6.shape[0])
+        if tuple(Kfb.shape) != (B, K - 1, 2, 6) or (kff is not None and tuple(kff.shape) != (B, K - 1, 2)):
+            raise ValueError(f"Kfb must be [{B}, {K - 1}, 2, 6] and kff [{B}, {K - 1}, 2]")
+        D = K if n_out is None else int(n_out)
+        if on_device:
+            import torch
+            kw = dict(device=rows.device)
+            out = torch.empty((S, B, max(D, 0), 10), dtype=torch.float64, **kw) if rows_out else None
+            mx, en = torch.empty((S, B), dtype=torch.float64, **kw), torch.empty((S, B), dtype=torch.float64, **kw)
+            nc = torch.empty((S, B), dtype=torch.int32, **kw)
+            p = lambda a: None if a is None else a.data_ptr()   # noqa: E731
+        else:
+            out = np.empty((S, B, max(D, 0), 10)) if rows_out else None
+            mx, en, nc = np.empty((S, B)), np.empty((S, B)), np.empty((S, B), np.int32)
+            p = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+        rc = self.policy_rollout_raw(B, layout, p(rows), K, p(Kfb), p(kff), alpha, S, p(start6), clamp, D, p(out), p(mx), p(en),
+                                     p(nc), MEM_DEVICE if on_device else MEM_HOST)
+        self._chk(rc, "policy_rollout")
+        return dict(rows=out, max_dev=mx, end_dev=en, n_clamped=nc)
+
+    def policy_rollout_raw(self, batch, layout, rows_ptr, n_knots, kfb_ptr, kff_ptr, alpha, n_samples, start6_ptr, clamp, n_out,
+                           out_rows_ptr, max_dev_ptr, end_dev_ptr, n_clamped_ptr, memory) -> int:
+        """Pointer-level form (every array in device or host memory as `memory` says; each output pointer may be None, not all
+        of them); returns the code."""
+        return self.L.cilqr_policy_rollout_batch(self.h, batch, layout, rows_ptr, n_knots, kfb_ptr, kff_ptr, C.c_double(alpha),
+                                                 n_samples, start6_ptr, 1 if clamp else 0, n_out, out_rows_ptr, max_dev_ptr,
+                                                 end_dev_ptr, n_clamped_ptr, memory)
 
     def frenet(self, center, rows, layout: int = ROWS_POINTS):
         """DiscretizedTrajectory::GetProjection of every row of a batch of trajectories onto the centre line, on the GPU

@@ -263,6 +263,7 @@ struct cilqr_solver {
   cilqr::call_blocks mg;
   cilqr::call_blocks tk;          // cilqr_track_rows_batch (track_batch.hip)
   cilqr::dev_mem tk_work;         // ... and the follow table of the call (track.hpp)
+  cilqr::call_blocks po;          // cilqr_policy_gains_batch / cilqr_policy_rollout_batch (policy_batch.hip)
   cilqr::call_blocks sw;          // cilqr_window_scenes_batch (scene_window_batch.hip)
   cilqr::call_blocks pr;          // cilqr_predict_scenes_batch (scene_predict_batch.hip)
   // cilqr_carry_rows_batch (carry_batch.hip); cilqr_plan_scenes_batch_carry (carry_pipeline.hip): the intermediates of its

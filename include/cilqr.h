@@ -980,6 +980,66 @@ int cilqr_track_rows_batch(cilqr_handle h, int32_t batch, int32_t layout, const 
                            double* driven /* [B][n_drive][CILQR_TRAJ_FIELDS] */, int32_t* ok /* [B] */,
                            int32_t* n_failed /* HOST, optional */, int32_t memory);
 
+/* ---- policy: the closed-loop law of a solve -- its feedback gains, and rollouts under them from starts the caller chooses
+ * (additive, ABI 7) ----
+ * Every iteration of a solve computes the gains K_i (2 x 6), k_i of the Riccati pass and applies them in Forward (cc:392-415)
+ * as u_i = u*_i + K_i (x_i - x*_i) + alpha k_i.  Their curvature includes the corridor, lane and bound barriers.  The two calls
+ * give that law to the caller: the gains about any batch of trajectories, and what the vehicle does under them when it does not
+ * start where the plan assumed.
+ *
+ * cilqr_policy_gains_batch is the stage chain, bit for bit: cilqr_stage_load(in); the current iterate set to the state
+ * columns of all K rows and the control columns of the first N rows of `rows` (the bits copied, on the device, wherever the
+ * rows lie; every other column is not read); cilqr_stage_quadratize; cilqr_stage_backward(lambda); CILQR_T_KFB, CILQR_T_KFF
+ * and CILQR_T_DV written problem-major as cilqr_stage_read writes them.  rows [B][K][fields], lambda [B] (NULL: 0 for every
+ * problem), Kfb [B][N][2][6], kff [B][N][2], dV [B][2] (optional) and ok [B] (optional) lie in in->memory.  layout:
+ * CILQR_ROWS_TRAJ or CILQR_ROWS_PLAN -- every other layout lacks the controls or the states: CILQR_ERR_ARG.  A problem with a
+ * negative corridor_count at some knot (CILQR_ST_NO_CORRIDOR) gets ok = 0 and zeros in its K, k and dV; every other gets ok =
+ * 1.  Backward has no failure exit in the reference (cc:363-371), so there is none here; a non-finite row poisons its own
+ * problem only.  The checks are those of cilqr_stage_load -- among them CILQR_ERR_KNOTS unless in->n_knots is the handle's K,
+ * CILQR_ERR_ARG for a batch with more than one lane group (solve such groups one call each), CILQR_ERR_STATE while solves
+ * are submitted on the handle -- and CILQR_ERR_NULL for h, in, rows, Kfb, kff.  Afterwards the handle is in the staged state of
+ * that chain: cilqr_stage_read and cilqr_stage_forward work on it. */
+int cilqr_policy_gains_batch(cilqr_handle h, const cilqr_problem_batch* in, int32_t layout, const double* rows,
+                             const double* lambda /* [B] or NULL = 0 for every problem */,
+                             double* Kfb /* [B][N][2][6] */, double* kff /* [B][N][2] */, double* dV /* [B][2], optional */,
+                             int32_t* ok /* [B], optional */);
+/* cilqr_policy_rollout_batch (kernels_policy.hip): Forward from start6[s][b], for n_samples starts of every problem.
+ * For sample s of problem b: x_0 = start6[s][b]; for every step i < n_out - 1
+ *   difference  dx = x_i - x*_i component by component, x* the state columns of nominal row i.  theta is NOT wrapped, as at
+ *               cc:407: a start on the other side of the +-pi cut from the nominal heading is the caller's business.
+ *   control     for r = 0, 1: acc = K_i[r][0] dx_0; acc += K_i[r][1] dx_1; ... acc += K_i[r][5] dx_5;
+ *               u_r = (u*_r + acc) + alpha k_i[r], u* the control columns of nominal row i; with kff == NULL u_r = u*_r + acc
+ *               and alpha is not read.
+ *   clamp       if clamp != 0: u_0 limited to [jerk_min, jerk_max], u_1 to [delta_rate_min, delta_rate_max] of the handle's
+ *               configuration, as u < lo ? lo : (u > hi ? hi : u) -- a NaN passes.  n_clamped counts the steps at which a
+ *               limit was applied to either control.
+ *   step        u_1 = NormalizeAngle(u_1), x_{i+1} = Dynamics(x_i, u) (cc:408-410), the solve's own step.
+ * Recorded row i (CILQR_ROWS_TRAJ): time i dt, the six states x_i, kappa = tan(delta) / wheel_base, the two controls applied
+ * at step i; the last recorded row carries controls (0, 0), as the solver's export has them at its last knot.  max_dev =
+ * sqrt(max_i ((x_i - x*_i)^2 + (y_i - y*_i)^2)) over the recorded rows (a NaN stays), end_dev the same at the last recorded
+ * row.  dt, wheel_base and the bounds are the handle's; batch and n_knots are NOT tied to it (as for the margins), and no
+ * problem needs to be loaded.
+ *   rows [B][n_knots][fields] in CILQR_ROWS_TRAJ / _PLAN, Kfb [B][n_knots - 1][2][6], kff [B][n_knots - 1][2] or NULL,
+ *   start6 [S][B][6], out_rows [S][B][n_out][CILQR_TRAJ_FIELDS], max_dev, end_dev, n_clamped [S][B]: all in `memory`; each
+ *   output is optional, with out_rows == NULL only the summaries are produced (the cheap Monte-Carlo form).
+ * Outputs are sample-major on purpose: slice s of out_rows is an ordinary batch of B CILQR_ROWS_TRAJ trajectories, which
+ * cilqr_check_collisions_batch, cilqr_clearance_rows_batch, cilqr_constraint_margins_batch, cilqr_resample_rows_batch and a
+ * warm start take where it lies, with the scenes or the problem batch of the nominal plans.  A chain's bits do not depend on
+ * the batch, the samples or the chains around it.  Runs on the handle's stream and waits for that stream only; it touches
+ * neither the staged nor the solver state.  Checked before anything is launched, the handle staying usable: CILQR_ERR_NULL
+ * (h, rows, Kfb, start6; every output NULL); CILQR_ERR_ARG for an unknown memory flag, a layout other than _TRAJ / _PLAN,
+ * batch < 1, n_knots < 2, n_out outside 1 ... n_knots, n_samples outside 1 ... CILQR_POLICY_MAX_SAMPLES, a non-finite alpha
+ * with kff != NULL; CILQR_ERR_STATE while solves are submitted on the handle.  Process noise and random numbers are the
+ * caller's: it supplies the starts. */
+#define CILQR_POLICY_MAX_SAMPLES 256
+int cilqr_policy_rollout_batch(cilqr_handle h, int32_t batch, int32_t layout, const double* rows /* nominal [B][K][F] */,
+                               int32_t n_knots, const double* Kfb /* [B][N][2][6] */, const double* kff /* [B][N][2] or NULL */,
+                               double alpha, int32_t n_samples, const double* start6 /* [S][B][6] */, int32_t clamp,
+                               int32_t n_out /* 1..K rows recorded; n_out - 1 steps are simulated */,
+                               double* out_rows /* [S][B][n_out][CILQR_TRAJ_FIELDS] or NULL */,
+                               double* max_dev /* [S][B] or NULL */, double* end_dev /* [S][B] or NULL */,
+                               int32_t* n_clamped /* [S][B] or NULL */, int32_t memory);
+
 /* ---- TrajectoryPlanner::Plan for B scenes per call (trajectory_planner.cpp:28-162) ----
  * scene batch -> cilqr_dp_plan_batch -> cilqr_scene_points_batch (at the time column the planner produced, with
  * corridor_cfg->is_multiple_sample and the worst-case max_points) -> cilqr_build_corridors (the cmax of the handle's
