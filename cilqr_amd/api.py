@@ -146,6 +146,9 @@ KEY_TIME, KEY_STATION = 0, 1
 # cilqr_carry_rows / cilqr_carry_rows_batch: the state of a trajectory, and what cilqr_plan_scenes_batch_carry adds to it
 # in `source` (CILQR_CARRY_*)
 CARRY_KEPT, CARRY_NOT_ASKED, CARRY_REFUSED, CARRY_OFF_START, CARRY_HIT = 0, 1, 2, 3, 4
+# cilqr_stop_rows / cilqr_stop_rows_batch: the status of a chain (CILQR_STOP_*) and the profiles of one call
+STOP_STOPPED, STOP_MOVING, STOP_OVERRUN, STOP_REFUSED = 0, 1, 2, 3
+STOP_MAX_PROFILES = 8
 PREDICT_HOLD, PREDICT_CONSTANT_VELOCITY = 0, 1   # CILQR_PREDICT_* (include/cilqr.h, "scene prediction")
 # cilqr_frenet_rows / cilqr_frenet_rows_batch: plain [K][2] x, y rows (CILQR_ROWS_POINTS; these two calls only), the doubles
 # of a centre-line row and of a result row (CILQR_FRENET_FIELDS), doubles per row of every layout they accept
@@ -204,6 +207,7 @@ EXPORTS = [
     "cilqr_window_scene", "cilqr_window_scenes_batch", "cilqr_plan_scenes_batch_warm",
     "cilqr_predict_scene", "cilqr_predict_scenes_batch",
     "cilqr_carry_rows", "cilqr_carry_rows_batch", "cilqr_plan_scenes_batch_carry",
+    "cilqr_stop_rows", "cilqr_stop_rows_batch", "cilqr_stop_scenes_batch",
     "cilqr_road_barriers", "cilqr_default_tracker_config",
     "cilqr_set_tracker_config",
     "cilqr_solve_batch_warm", "cilqr_submit_warm", "cilqr_stage_load_warm", "cilqr_pool_submit_warm", "cilqr_multi_solve_warm",
@@ -298,6 +302,15 @@ def lib():
         L.cilqr_carry_rows_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double,
                                              C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
+        L.cilqr_stop_rows.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cilqr_stop_rows_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int32]
+        L.cilqr_stop_scenes_batch.argtypes = [C.c_void_p, C.POINTER(DpConfig), C.POINTER(SceneBatchStruct), C.c_int32,
+                                              C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32,
+                                              C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_int32)]
         L.cilqr_window_scene.argtypes = [C.POINTER(SceneStruct), C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_int32)]
         L.cilqr_window_scenes_batch.argtypes = [C.c_void_p, C.POINTER(SceneBatchStruct), C.c_void_p, C.c_double, C.c_int32,
@@ -1194,6 +1207,118 @@ class BatchIlqrOptimizer:
                                            state_ptr, C.byref(n), memory)
         return rc, int(n.value)
 
+    def _stop_inputs(self, rows, layout, profiles, start_va):
+        """rows [B,K,F] and start_va [B,2] or None of one kind (NumPy arrays or contiguous float64 device tensors), profiles
+        [M,2] as a host array"""
+        on_device = _is_device_tensor(rows)
+        if start_va is not None and on_device != _is_device_tensor(start_va):
+            raise ValueError("rows and start_va must both be NumPy arrays or both device tensors")
+        if on_device:
+            for t in (rows, start_va):
+                if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64"):
+                    raise ValueError("rows / start_va on the device: contiguous float64 tensors")
+        else:
+            rows, start_va = _f64(rows), (None if start_va is None else _f64(start_va))
+        if rows.ndim != 3 or rows.shape[2] != ROWS_FIELDS.get(layout, rows.shape[2]):
+            raise ValueError(f"rows must be [B, K, {ROWS_FIELDS.get(layout)}]")
+        if start_va is not None and tuple(start_va.shape) != (int(rows.shape[0]), 2):
+            raise ValueError(f"start_va must be [{int(rows.shape[0])}, 2]")
+        profiles = _f64(profiles)
+        if profiles.ndim != 2 or profiles.shape[1] != 2:
+            raise ValueError("profiles must be [M, 2] = a_target, jerk")
+        return on_device, rows, profiles, start_va
+
+    def stop_rows(self, rows, layout: int, profiles, delta_t: "float | None" = None, n_out: "int | None" = None, start_va=None,
+                  with_rows: bool = True):
+        """Brake along every trajectory of a batch at every one of M braking profiles, on the GPU (cilqr_stop_rows_batch):
+        rows [B,K,F] in `layout` (ROWS_TRAJ / ROWS_PLAN / ROWS_COARSE), profiles [M,2] = a_target <= 0, jerk < 0 (host),
+        n_out (None: K) rows delta_t (None: the handle's dt) apart, start_va [B,2] = v0, a0 (None: row 0's).  NumPy arrays,
+        or contiguous float64 device tensors (both of the same kind).  Returns dict(rows [M,B,n_out,11] in ROWS_PLAN layout
+        (with_rows), status [M,B] int32 (STOP_*), stop_knot [M,B] int32, travel [M,B]) of that kind: profile-major, so
+        that rows[m] is an ordinary batch for check_collisions, clearance, constraint_margins, resample and track."""
+        on_device, rows, profiles, start_va = self._stop_inputs(rows, layout, profiles, start_va)
+        B, K, M = int(rows.shape[0]), int(rows.shape[1]), int(profiles.shape[0])
+        N = K if n_out is None else int(n_out)
+        dt = self.cfg.dt if delta_t is None else float(delta_t)
+        if on_device:
+            import torch
+            make = lambda shape, dtype: torch.empty(shape, dtype=getattr(torch, dtype), device=rows.device)
+            ptr = lambda t: None if t is None else t.data_ptr()
+        else:
+            make = lambda shape, dtype: np.empty(shape, dtype=dtype)
+            ptr = lambda a: None if a is None else a.ctypes.data
+        out = dict(status=make((M, B), "int32"), stop_knot=make((M, B), "int32"), travel=make((M, B), "float64"))
+        if with_rows:
+            out["rows"] = make((M, B, max(N, 0), PLAN_FIELDS), "float64")
+        rc = self.stop_rows_raw(B, layout, ptr(rows), K, profiles, ptr(start_va), dt, N, ptr(out.get("rows")),
+                                ptr(out["status"]), ptr(out["stop_knot"]), ptr(out["travel"]),
+                                MEM_DEVICE if on_device else MEM_HOST)
+        self._chk(rc, "stop_rows")
+        return out
+
+    def stop_rows_raw(self, batch, layout, rows_ptr, n_knots, profiles, start_va_ptr, delta_t, n_out, out_rows_ptr, status_ptr,
+                      stop_knot_ptr, travel_ptr, memory) -> int:
+        """Pointer-level form (rows / start_va and the four outputs in device or host memory as `memory` says, each output
+        optional; profiles a host array [M,2]: slice m of out_rows feeds check_collisions_raw, clearance_raw,
+        constraint_margins_raw, resample_raw and track_raw where it lies); returns the code."""
+        profiles = _f64(profiles)
+        return self.L.cilqr_stop_rows_batch(self.h, batch, layout, rows_ptr, n_knots, profiles.shape[0] if profiles.ndim == 2 else 0,
+                                            profiles.ctypes.data, start_va_ptr, C.c_double(delta_t), n_out, out_rows_ptr,
+                                            status_ptr, stop_knot_ptr, travel_ptr, memory)
+
+    def stop_scenes(self, packed: dict, rows, layout: int, profiles, delta_t: "float | None" = None,
+                    n_out: "int | None" = None, start_va=None, cfg: "DpConfig | None" = None, buffer: float = 0.0):
+        """For every scene of a batch the gentlest braking profile that comes to rest clear of the obstacles, on the GPU
+        (cilqr_stop_scenes_batch): `packed` = scene_io.pack_scene_batch(center, scenes), rows [B,K,F] in `layout`, profiles
+        [M,2] ordered gentlest first, the rest as stop_rows; buffer = collision_buffer of the audit.  NumPy arrays, or
+        contiguous float64 device tensors for rows and start_va: the call then runs on DEVICE arrays -- the six per-scene
+        arrays of `packed` may be device tensors already (kept resident over the cycles), NumPy ones are uploaded -- and the
+        results are device tensors.  Returns dict(rows [B,n_out,11] in ROWS_PLAN layout = the rows of profile choice[b], of
+        the last profile where choice is -1; choice [B] int32; status, first_hit [M,B] int32; n_none = the scenes with
+        choice -1)."""
+        cfg = cfg or default_dp_config()
+        on_device, rows, profiles, start_va = self._stop_inputs(rows, layout, profiles, start_va)
+        B, K, M = int(packed["batch"]), int(rows.shape[1]), int(profiles.shape[0])
+        if rows.shape[0] != B:
+            raise ValueError(f"rows must be [{B}, K, {ROWS_FIELDS.get(layout)}]")
+        N = K if n_out is None else int(n_out)
+        dt = self.cfg.dt if delta_t is None else float(delta_t)
+        shapes = dict(rows=((B, max(N, 0), PLAN_FIELDS), "float64"), choice=((B,), "int32"), status=((M, B), "int32"),
+                      first_hit=((M, B), "int32"))
+        if on_device:
+            import torch
+            keep = {}
+            for k in _SCENE_BATCH_ARRAYS:
+                v = packed[k]
+                keep[k] = v if _is_device_tensor(v) else torch.from_numpy(np.ascontiguousarray(v)).to(rows.device)
+                if not keep[k].is_cuda or not keep[k].is_contiguous():
+                    raise ValueError(f"packed[{k!r}] on the device: a contiguous tensor")
+            sb = scene_batch_struct(packed, MEM_DEVICE, **{k: keep[k].data_ptr() for k in _SCENE_BATCH_ARRAYS})
+            out = {k: torch.empty(shape, dtype=getattr(torch, dtype), device=rows.device) for k, (shape, dtype) in shapes.items()}
+            ptr = lambda t: None if t is None else t.data_ptr()
+        else:
+            keep = {k: np.ascontiguousarray(v) for k, v in packed.items() if isinstance(v, np.ndarray)}
+            sb = scene_batch_struct(packed, MEM_HOST, **{k: _ptr(keep[k]) for k in _SCENE_BATCH_ARRAYS})
+            out = {k: np.empty(shape, dtype=dtype) for k, (shape, dtype) in shapes.items()}
+            ptr = _ptr
+        rc, n = self.stop_scenes_raw(cfg, sb, layout, ptr(rows), K, profiles, ptr(start_va), dt, N, buffer, ptr(out["rows"]),
+                                     ptr(out["choice"]), ptr(out["status"]), ptr(out["first_hit"]))
+        self._chk(rc, "stop_scenes")
+        del keep
+        return dict(out, n_none=n)
+
+    def stop_scenes_raw(self, cfg, scene_batch, layout, rows_ptr, n_knots, profiles, start_va_ptr, delta_t, n_out, buffer,
+                        out_rows_ptr, choice_ptr, status_ptr=None, first_hit_ptr=None):
+        """Pointer-level form (rows / start_va / out_rows / choice / status / first_hit in device or host memory as
+        scene_batch.memory says; profiles a host array [M,2]); returns (rc, n_none)."""
+        profiles = _f64(profiles)
+        n = C.c_int32(0)
+        rc = self.L.cilqr_stop_scenes_batch(self.h, C.byref(cfg) if cfg is not None else None, C.byref(scene_batch), layout,
+                                            rows_ptr, n_knots, profiles.shape[0] if profiles.ndim == 2 else 0,
+                                            profiles.ctypes.data, start_va_ptr, C.c_double(delta_t), n_out, C.c_double(buffer),
+                                            out_rows_ptr, choice_ptr, status_ptr, first_hit_ptr, C.byref(n))
+        return rc, int(n.value)
+
     def track(self, rows, layout: int, start6=None, n_drive: int | None = None):
         """Drive a vehicle along every trajectory of a batch with the closed-loop Tracker, on the GPU
         (cilqr_track_rows_batch): rows [B,K,F] in `layout` (ROWS_TRAJ / ROWS_PLAN / ROWS_COARSE), each with its own time
@@ -1589,6 +1714,24 @@ def carry_rows(rows, layout: int, advance: float, max_advance: float, n_knots: i
     if rc != OK:
         raise CilqrError(rc, "in cilqr_carry_rows")
     out["state"] = int(state.value)
+    return out
+
+
+def stop_rows(rows, layout: int, profiles, delta_t: float, n_out: int, start_va=None, with_rows: bool = True) -> dict:
+    """The stop rule for one trajectory and M braking profiles through the C-ABI (cilqr_stop_rows, host, no GPU): rows [K,F]
+    in `layout`, profiles [M,2] = a_target, jerk, start_va = (v0, a0) or None -> dict(rows [M,n_out,11] in ROWS_PLAN layout
+    (with_rows), status [M] int32 (STOP_*), stop_knot [M] int32, travel [M])."""
+    rows, profiles = _f64(rows), _f64(profiles)
+    start_va = None if start_va is None else _f64(start_va).ravel()
+    M, N = (profiles.shape[0] if profiles.ndim == 2 else 0), max(int(n_out), 0)
+    out = dict(status=np.empty(M, np.int32), stop_knot=np.empty(M, np.int32), travel=np.empty(M))
+    if with_rows:
+        out["rows"] = np.empty((M, N, PLAN_FIELDS))
+    rc = lib().cilqr_stop_rows(layout, rows.ctypes.data, rows.shape[0] if rows.ndim == 2 else 0, M, profiles.ctypes.data,
+                               _ptr(start_va), C.c_double(delta_t), int(n_out), _ptr(out.get("rows")), _ptr(out["status"]),
+                               _ptr(out["stop_knot"]), _ptr(out["travel"]))
+    if rc != OK:
+        raise CilqrError(rc, "in cilqr_stop_rows")
     return out
 
 

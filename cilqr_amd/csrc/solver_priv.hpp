@@ -272,6 +272,10 @@ struct cilqr_solver {
   cilqr::call_blocks cy;
   cilqr::pinned_mem cy_sel_host;
   cilqr::dev_mem cy_work, cy_chunk;
+  // cilqr_stop_rows_batch (stop_batch.hip); cilqr_stop_scenes_batch (stop_pipeline.hip): its HOST arrays and the count, and
+  // the slices of all profiles with their statuses and hits
+  cilqr::call_blocks sr, ss;
+  cilqr::dev_mem ss_work;
 };
 
 namespace cilqr {

@@ -1297,6 +1297,92 @@ int cilqr_plan_scenes_batch_carry(cilqr_handle h, const cilqr_dp_config* dp_cfg,
                                   double* plan, double* coarse9, int32_t* outcome, int32_t* source /* [B], optional */,
                                   int32_t* n_dp_failed, int32_t* n_corridor_failed, int32_t* n_kept);
 
+/* ---- stop: brake along a path that is already trusted (additive, ABI 7) ----
+ * Where a cycle's plan is refused -- the audit calls it hit, the carried plan no longer clears, the planner found no path --
+ * a caller keeps the path it has and takes the speed off it: the vehicle brakes along the path and comes to rest.  The stop
+ * rule makes such rows for one trajectory and one braking profile; a caller orders its profiles gentlest first and takes the
+ * first that stops clear (cilqr_stop_scenes_batch below).  Every operation is rounded once (no fused multiply-add).
+ *   inputs      n_knots >= 2 rows in CILQR_ROWS_TRAJ / _PLAN / _COARSE; a profile (a_target, jerk), a_target <= 0, jerk < 0,
+ *               both finite; delta_t > 0; n_out in 1 ... CILQR_DP_MAX_KNOTS; optionally start_va = (v0, a0), which replaces
+ *               the velocity and a columns of row 0 (else v0, a0 are those columns).
+ *   station key   _PLAN and _COARSE: the layout's station column.  _TRAJ (which has none): key_0 = 0, key_i = key_{i-1} +
+ *               hypot(x_i - x_{i-1}, y_i - y_{i-1}) in knot order (the hypot of the `plan` rows and of "carry").
+ *               s_end = key[n_knots-1].
+ *   speed chain   (s_0, v_0, a_0) = (key_0, v0, a0); with jd = jerk * delta_t and hd = 0.5 * delta_t, step k -> k + 1:
+ *               if v == 0:           s, v stay, a' = 0;
+ *               otherwise            a' = max(a + jd, a_target) if a > a_target,  min(a - jd, a_target) if a < a_target,
+ *                                    a_target else;      vn = v + hd * (a + a');
+ *                   if !(vn > 0)     (the stop lies inside the step)  f = v / (v - vn);  s = s + (0.5 * v) * (f * delta_t);
+ *                                    v = 0;  a = 0;
+ *                   otherwise        s = s + hd * (v + vn);  v = vn;  a = a'.
+ *   row k       always CILQR_ROWS_PLAN (11 columns), k = 0 ... n_out - 1:
+ *               time       time[0] + delta_t * k;
+ *               s          q_k = s_end if s_k > s_end, else s_k;
+ *               x y theta kappa delta    the resample rule above with CILQR_KEY_STATION at q_k on the station key -- its
+ *                          bracket, its degenerate pair (p0's bits) and its slerp included; delta is interpolated, never
+ *                          recomputed from kappa, so no transcendental enters the rule;
+ *               velocity, a    v_k, a_k;
+ *               jerk       (a_{k+1} - a_k) / delta_t,   delta_rate  (delta_{k+1} - delta_k) / delta_t;  both 0 in the last row.
+ *   status      first match wins:
+ *               CILQR_STOP_REFUSED   v0 or a0 is not finite, v0 < 0, or any column of any row produced is not finite.  Every
+ *                                    row is zero, stop_knot = -1, travel = 0.
+ *               CILQR_STOP_OVERRUN   some s_k > s_end (the path is shorter than the stop).
+ *               CILQR_STOP_MOVING    v_{n_out-1} > 0.
+ *               CILQR_STOP_STOPPED   otherwise.
+ *   stop_knot   the first k with v_k == 0, -1 if there is none;  travel = s_{n_out-1} - key_0, not clamped.
+ * The rows are kinematic, like the DP planner's: the jump of a to 0 at the stop shows in jerk.  cilqr_track_rows_batch makes
+ * them drivable, cilqr_constraint_margins_batch measures how far they overshoot the bounds.
+ * cilqr_stop_rows: one trajectory and n_profiles profiles on the host, no handle (C++ callers use
+ * include/cilqr/trajectory_queries.hpp: stop_rows).
+ *   profiles [n_profiles][2] a_target, jerk;  start_va [2] or NULL;  out_rows [n_profiles][n_out][CILQR_PLAN_FIELDS],
+ *   status / stop_knot / travel [n_profiles]: each output optional, not all of them
+ * CILQR_ERR_NULL (rows, profiles); CILQR_ERR_ARG for an unknown layout, n_knots < 2, n_out < 1, n_profiles outside 1 ...
+ * CILQR_STOP_MAX_PROFILES, a profile outside its domain, a delta_t that is not positive, every output NULL;
+ * CILQR_ERR_CAPACITY for n_knots or n_out > CILQR_DP_MAX_KNOTS. */
+#define CILQR_STOP_STOPPED 0
+#define CILQR_STOP_MOVING 1
+#define CILQR_STOP_OVERRUN 2
+#define CILQR_STOP_REFUSED 3
+#define CILQR_STOP_MAX_PROFILES 8
+int cilqr_stop_rows(int32_t layout, const double* rows, int32_t n_knots, int32_t n_profiles, const double* profiles,
+                    const double* start_va, double delta_t, int32_t n_out, double* out_rows, int32_t* status,
+                    int32_t* stop_knot, double* travel);
+/* ---- the same for B trajectories per call, on the GPU (kernels_stop.hip) ----
+ *   rows [B][n_knots][fields], start_va [B][2] or NULL, in `memory`; profiles [n_profiles][2], HOST memory;
+ *   out_rows [n_profiles][B][n_out][CILQR_PLAN_FIELDS], status / stop_knot / travel [n_profiles][B], in `memory`: each
+ *   optional, not all of them
+ * The outputs are profile-major on purpose: slice m is an ordinary batch of B CILQR_ROWS_PLAN trajectories and feeds
+ * cilqr_check_collisions_batch, cilqr_clearance_rows_batch, cilqr_constraint_margins_batch, cilqr_resample_rows_batch,
+ * cilqr_track_rows_batch and a warm start where it lies.  A workgroup takes a run of whole trajectories: their rows and
+ * station keys are staged in LDS once and shared by all profiles, one lane per (trajectory, profile) runs the speed chain
+ * into an LDS image of the rows, the (profile, knot) pairs are spread over the lanes, which bracket and interpolate there,
+ * the controls are differenced from the neighbouring row of the image, the test for a non-finite value is one ballot per
+ * wavefront, and the rows leave as consecutive doubles; an image that does not fit the workgroup's LDS is produced in chunks
+ * of knots.  Every element is the host call's bit for bit (the kernel is built without contraction, wraps angles with the
+ * routine of cilqr_device_math fn 6 and takes the hypot of fn 9); a chain's bits depend neither on the batch nor on the
+ * profiles around it; nothing beyond the alignment of a double is assumed.  Runs on the handle's stream and waits for that
+ * stream only; DEVICE arrays need no work space, HOST arrays are staged in blocks that belong to the handle and grow to the
+ * largest call.  Checked before anything is launched, the handle staying usable: CILQR_ERR_NULL (handle, rows, profiles);
+ * CILQR_ERR_ARG for batch < 1, an unknown memory flag and what the host call refuses; CILQR_ERR_CAPACITY as there;
+ * CILQR_ERR_STATE while solves are submitted on the handle. */
+int cilqr_stop_rows_batch(cilqr_handle h, int32_t batch, int32_t layout, const double* rows, int32_t n_knots,
+                          int32_t n_profiles, const double* profiles, const double* start_va, double delta_t, int32_t n_out,
+                          double* out_rows, int32_t* status, int32_t* stop_knot, double* travel, int32_t memory);
+/* ---- the pipeline: for every scene the gentlest profile that stops clear ----
+ *   1. stop     cilqr_stop_rows_batch for all n_profiles profiles, into the handle's work space;
+ *   2. audit    cilqr_check_collisions_batch (CILQR_ROWS_PLAN, collision_buffer) on each slice;
+ *   3. choose   choice[b] = the smallest m with status[m][b] == CILQR_STOP_STOPPED and first_hit[m][b] == -1; -1 if there is
+ *               none (the caller orders the profiles gentlest first);
+ *   4. gather   out_rows[b] = slice choice[b], or slice n_profiles - 1 where choice[b] is -1 (a small kernel, no atomics).
+ * The results are, bit for bit, those of the public calls made one after the other.
+ *   rows, start_va (optional), out_rows [B][n_out][CILQR_PLAN_FIELDS], choice [B], status / first_hit [n_profiles][B]
+ *   (optional): memory as scenes->memory;  profiles: HOST memory;  *n_none (HOST, optional): the scenes with choice -1
+ * The checks are those of the two calls, all made before anything is launched (out_rows and choice may not be NULL). */
+int cilqr_stop_scenes_batch(cilqr_handle h, const cilqr_dp_config* dp_cfg, const cilqr_scene_batch* scenes, int32_t layout,
+                            const double* rows, int32_t n_knots, int32_t n_profiles, const double* profiles,
+                            const double* start_va, double delta_t, int32_t n_out, double collision_buffer,
+                            double* out_rows, int32_t* choice, int32_t* status, int32_t* first_hit, int32_t* n_none);
+
 /* ---- several GPUs from ONE host process (the reference's caller is one process:
  * algorithm/planning_node.cc:9-31) ----
  * A multi handle owns one solver handle per listed device.  cilqr_multi_solve cuts the batch into contiguous shards

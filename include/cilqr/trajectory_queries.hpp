@@ -2,7 +2,8 @@
 // (algorithm/utils/discretized_trajectory.cpp:50-136, math::slerp math_utils.h:208-225) on rows in the layouts of
 // include/cilqr.h: the host statement of cilqr_resample_rows, which cilqr_resample_rows_batch is held to bit for bit.
 // Further down, GetProjection / GetCartesian (cpp:138-196) on a centre line: the host statement of cilqr_frenet_rows and
-// cilqr_cartesian_points.  Between the two, the carry rule on top of EvaluateTime: the host statement of cilqr_carry_rows.
+// cilqr_cartesian_points.  Between the two, the carry rule on top of EvaluateTime: the host statement of cilqr_carry_rows; and
+// the stop rule on top of EvaluateStation: the host statement of cilqr_stop_rows.
 // Header-only, C++14, no HIP.  The rules are stated once, in include/cilqr.h ("resample", "frenet"); this file follows
 // them step by step.
 #ifndef CILQR_TRAJECTORY_QUERIES_HPP_
@@ -158,6 +159,112 @@ inline int carry_rows(int layout, const double* rows, int n_rows, double advance
     if (station != nullptr) station[k] = o[1];
   }
   return state;
+}
+
+// ---- stop: brake along the path: the host statement of cilqr_stop_rows and cilqr_stop_rows_batch.  The rule is stated in
+// include/cilqr.h ("stop").
+constexpr int kStopStopped = 0, kStopMoving = 1, kStopOverrun = 2, kStopRefused = 3;
+
+// one state of the speed chain, and its step k -> k + 1 with jd = jerk * delta_t, hd = 0.5 * delta_t (constexpr: the kernel
+// of cilqr_stop_rows_batch runs this very function)
+struct StopState {
+  double s, v, a;
+};
+constexpr StopState stop_step(const StopState& c, double a_target, double jd, double hd, double delta_t) {
+  if (c.v == 0.0) return StopState{c.s, c.v, 0.0};
+  double an = a_target;
+  if (c.a > a_target) {
+    an = c.a + jd;
+    if (!(an > a_target)) an = a_target;   // max(a + jd, a_target)
+  } else if (c.a < a_target) {
+    an = c.a - jd;
+    if (!(an < a_target)) an = a_target;   // min(a - jd, a_target)
+  }
+  const double vn = c.v + hd * (c.a + an);
+  if (!(vn > 0.0)) {   // the stop lies inside the step
+    const double f = c.v / (c.v - vn);
+    return StopState{c.s + (0.5 * c.v) * (f * delta_t), 0.0, 0.0};
+  }
+  return StopState{c.s + hd * (c.v + vn), vn, an};
+}
+
+// rows [n_knots][fields] of `layout` as plan rows [n_knots][11] with the station key of the rule in the station column; a
+// column the layout lacks is 0
+inline void stop_plan_rows(int layout, const double* rows, int n_knots, double* plan) {
+  const Columns c = columns_of(layout), P = columns_of(1);
+  const ColumnMap from = column_map(P, c);
+  double key = 0.0;
+  for (int i = 0; i < n_knots; ++i) {
+    const double* r = rows + (size_t)i * c.fields;
+    double* o = plan + (size_t)i * P.fields;
+    for (int f = 0; f < P.fields; ++f) {
+      o[f] = 0.0;
+      if (from.col[f] >= 0) std::memcpy(o + f, r + from.col[f], sizeof(double));
+    }
+    if (c.station < 0) {
+      if (i > 0) key = key + std::hypot(r[c.x] - r[c.x - c.fields], r[c.y] - r[c.y - c.fields]);
+      o[P.station] = key;
+    }
+  }
+}
+
+// rows [n_knots][fields] and ONE profile -> out_rows [n_out][11] (may be null); returns the status.  start_va: null, or
+// (v0, a0).  The arguments are taken as checked (cilqr_stop_rows).
+inline int stop_rows(int layout, const double* rows, int n_knots, double a_target, double jerk, const double* start_va,
+                     double delta_t, int n_out, double* out_rows, int* stop_knot, double* travel) {
+  const Columns P = columns_of(1);
+  double plan[256 * 11], img[256 * 11];   // CILQR_DP_MAX_KNOTS rows
+  stop_plan_rows(layout, rows, n_knots, plan);
+  const double v0 = start_va ? start_va[0] : plan[P.v], a0 = start_va ? start_va[1] : plan[P.a];
+  const double key0 = plan[P.station], s_end = plan[(size_t)(n_knots - 1) * P.fields + P.station];
+  int status = kStopStopped, knot = -1;
+  double went = 0.0;
+  if (!std::isfinite(v0) || !std::isfinite(a0) || v0 < 0.0) {
+    status = kStopRefused;
+  } else {
+    const double jd = jerk * delta_t, hd = 0.5 * delta_t;
+    StopState c{key0, v0, a0};
+    bool overrun = false, finite = true;
+    double r[11];
+    for (int k = 0; k < n_out; ++k) {
+      if (k > 0) c = stop_step(c, a_target, jd, hd, delta_t);
+      if (c.s > s_end) overrun = true;
+      if (knot < 0 && c.v == 0.0) knot = k;
+      const double q = c.s > s_end ? s_end : c.s;
+      const int i = bracket(plan, P.fields, P.station, n_knots, q);
+      interpolate(P, P.station, plan + (size_t)(i - 1) * P.fields, plan + (size_t)i * P.fields, q, r);
+      double* o = img + (size_t)k * P.fields;
+      o[P.time] = plan[P.time] + delta_t * k;
+      o[P.station] = q;
+      std::memcpy(o + P.x, r + P.x, sizeof(double));
+      std::memcpy(o + P.y, r + P.y, sizeof(double));
+      std::memcpy(o + P.theta, r + P.theta, sizeof(double));
+      std::memcpy(o + P.kappa, r + P.kappa, sizeof(double));
+      std::memcpy(o + P.delta, r + P.delta, sizeof(double));
+      o[P.v] = c.v;
+      o[P.a] = c.a;
+      o[P.jerk] = 0.0;
+      o[P.rate] = 0.0;
+      if (k > 0) {
+        o[P.jerk - P.fields] = (o[P.a] - o[P.a - P.fields]) / delta_t;
+        o[P.rate - P.fields] = (o[P.delta] - o[P.delta - P.fields]) / delta_t;
+      }
+    }
+    for (int e = 0; e < n_out * P.fields; ++e) finite = finite && std::isfinite(img[e]);
+    went = c.s - key0;
+    if (!finite) status = kStopRefused;
+    else if (overrun) status = kStopOverrun;
+    else if (c.v > 0.0) status = kStopMoving;
+  }
+  if (status == kStopRefused) {
+    std::memset(img, 0, sizeof(double) * (size_t)n_out * P.fields);
+    knot = -1;
+    went = 0.0;
+  }
+  if (out_rows != nullptr) std::memcpy(out_rows, img, sizeof(double) * (size_t)n_out * P.fields);
+  if (stop_knot != nullptr) *stop_knot = knot;
+  if (travel != nullptr) *travel = went;
+  return status;
 }
 
 // ---- the Frenet frame of a centre line (DiscretizedTrajectory::GetProjection / GetCartesian, cpp:138-196): the host
