@@ -15,15 +15,14 @@
 #include <float.h>
 #include <math.h>
 
-#include "../../include/cilqr/row_layouts.hpp"
 #include "state.hpp"
 
 namespace cilqr {
 
 #define CILQR_DEV __device__ __forceinline__
 
-constexpr double kPi = 3.14159265358979323846;
-constexpr double kTwoPi = 2.0 * kPi;
+// (kPi, kTwoPi and the complete NormalizeAngle -- normalize_angle -- are include/cilqr/row_math.hpp's, as are slerp, bracket,
+// bracket_pair, the pair step and the libm-identical hypot_ref: the functions the host statements run)
 
 // ---- how the six products of a coefficient of `X.transpose() * Y` are added ----
 // Every such product of the path -- A^T Vx, B^T Vx, A^T Vxx, B^T Vxx (Backward, cc:348-353) and B^T P, A^T P (iqr,
@@ -63,56 +62,7 @@ CILQR_DEV Acc acc_sum6_xty(const Acc (&t)[6]) {
 #endif
 }
 
-// fmod(a + pi, 2 pi) with the IEEE-exact fast paths (fmod is always exact, so the short
-// branches return bit-identical values to the library call).
-CILQR_DEV double normalize_angle(double angle) {
-  const double t = angle + kPi;
-  double r;
-  if (t >= 0.0 && t < kTwoPi) {
-    r = t;
-  } else if (t >= kTwoPi && t < 2.0 * kTwoPi) {
-    r = t - kTwoPi;  // exact (Sterbenz)
-  } else if (t < 0.0 && t > -kTwoPi) {
-    r = t;
-  } else {
-    r = fmod(t, kTwoPi);
-  }
-  if (r < 0.0) r += kTwoPi;
-  return r - kPi;
-}
-
-// ---- the steps every query on rows shares (include/cilqr.h, "resample"; the host statement is trajectory_queries.hpp)
-// math::slerp (math_utils.h:208-225)
-CILQR_DEV double slerp(double a0, double t0, double a1, double t1, double t) {
-  if (fabs(t1 - t0) <= kMathEps) return normalize_angle(a0);
-  const double a0_n = normalize_angle(a0), a1_n = normalize_angle(a1);
-  double d = a1_n - a0_n;
-  if (d > kPi) d = d - kTwoPi;
-  else if (d < -kPi) d = d + kTwoPi;
-  const double r = (t - t0) / (t1 - t0);
-  const double a = a0_n + d * r;
-  return normalize_angle(a);
-}
-
-// bracket: n - 1 for q >= key(n - 1), 0 for q < key(0), else std::lower_bound's halving written out -- the first row whose
-// key is not below q.  The caller applies its own `i == 0 -> 1` and upper clamp.  key: int -> double, n >= 2
-template <class Key>
-CILQR_DEV int bracket(int n, double q, Key key) {
-  if (q >= key(n - 1)) return n - 1;
-  if (q < key(0)) return 0;
-  int first = 0, len = n;
-  while (len > 0) {
-    const int half = len >> 1;
-    if (key(first + half) < q) {
-      first += half + 1;
-      len -= half + 1;
-    } else {
-      len = half;
-    }
-  }
-  return first;
-}
-
+// ---- what the queries on rows share on the device alone (include/cilqr.h, "resample")
 // n doubles from global `g` to LDS `s` by the Lanes lanes of a workgroup, 16 bytes per lane and load where `g` allows:
 // the caller's arrays are only known to be aligned as doubles, so a piece that starts on an odd double moves its first
 // (and, as it comes, last) double alone
@@ -507,30 +457,8 @@ CILQR_DEV double segment_dist2_code(const double* __restrict__ r, int seg, doubl
 // alternatives (k_cost_knots at full batch, 481 us as is): comparing the roots inside a 4-ulp window, inline +34 %,
 // out of line +18 %; a plain 2-ulp margin costs nothing but only moves the disagreement to the fuzzy edge of the
 // strip.  The parity tests recognise the case (an exact tie of the oracle's own distances) and say so.
-// hypot as the reference's libm evaluates it.  glibc 2.35 (sysdeps/ieee754/dbl-64/e_hypot.c, the build without FMA
-// that x86-64 -O2 binaries get): h = sqrt(ax^2 + ay^2) with ax >= ay, corrected by one Newton step whose residual is
-// evaluated in two exact-ish parts.  The device library's hypot differs from it in the last bit on ~0.6 % of
-// arguments (measured against numpy on 200 000 pairs; this routine on none) -- enough to turn the reference's exact
-// ties into non-ties.  Arguments here are lengths in metres: the scaling branches for huge / tiny values are not needed.
-CILQR_DEV double hypot_ref(double x, double y) {
-  x = fabs(x);
-  y = fabs(y);
-  const double ax = x < y ? y : x, ay = x < y ? x : y;
-  if (ax >= ay * 0x1p54) return ax + ay;
-  double h = sqrt(ax * ax + ay * ay);
-  double t1, t2;
-  if (h <= 2.0 * ay) {
-    const double delta = h - ay;
-    t1 = ax * (2.0 * delta - ax);
-    t2 = (delta - 2.0 * (ax - ay)) * delta;
-  } else {
-    const double delta = h - ax;
-    t1 = 2.0 * delta * (ax - 2.0 * ay);
-    t2 = (4.0 * delta - ay) * ay + delta * delta;
-  }
-  h -= (t1 + t2) / (2.0 * h);
-  return h;
-}
+// hypot as the reference's libm evaluates it is row_math.hpp's hypot_ref: the device library's hypot differs from it in the
+// last bit on ~0.6 % of arguments -- enough to turn the reference's exact ties into non-ties.
 
 // LineSegment2d::DistanceTo as the reference evaluates it (line_segment2d.cpp:61-75): hypot to an end point, |cross| to
 // the foot.  Only the exact-tie rule below calls it.

@@ -54,6 +54,10 @@ CILQR_DEV DpRef dp_center_point(const DpParams& P, int i) {
   return DpRef{c[0], c[1], c[2], c[3], c[4], c[5], c[6]};
 }
 
+// The three functions below keep copies of their own of row_math.hpp's pair step (on a struct) and bracket_pair (the same
+// halving written with lo / hi, without the upper clamp); slerp and the epsilon are the shared ones.  As calls of the shared
+// functions they changed the code of k_dp_plan and k_cartesian, and each fell outside what the parent's own runs spread over
+// in one of two sessions (profiles/row_math_parent_vs_branch.json).
 CILQR_DEV DpRef dp_interpolate(const DpRef& p0, const DpRef& p1, double s) {   // discretized_trajectory.cpp:66-89
   const double s0 = p0.s, s1 = p1.s;
   if (fabs(s1 - s0) < kMathEps) return p0;

@@ -1,6 +1,8 @@
 // cilqr_carry_rows_batch and what cilqr_plan_scenes_batch_carry puts between its stages (include/cilqr.h, "carry").  The
-// host statement is include/cilqr/trajectory_queries.hpp: carry_rows; k_carry follows it operation by operation
-// (-ffp-contract=off, IEEE division, the exact normalize_angle, the libm-identical hypot_ref), so the rows are its bits.
+// host statement is include/cilqr/trajectory_queries.hpp: carry_rows.  The bracket and the pair step are ONE function for
+// both (include/cilqr/row_math.hpp: bracket_pair, pair_step over pair_carry); the checks of the advance, the chord
+// lengths (row_math.hpp's hypot_ref where the host statement takes std::hypot) and their sum in knot order k_carry follows
+// operation by operation (-ffp-contract=off, IEEE division), so the rows are its bits.
 //
 // k_carry moves memory: per trajectory it reads n_rows F doubles and writes 19 n_knots.  A workgroup of 256 lanes takes a
 // run of whole trajectories -- as many as fit 48 KiB of LDS, at most 16: five for 51 plan rows and 51 knots -- so that the
@@ -39,7 +41,7 @@ __global__ __launch_bounds__(kCyLanes) void k_carry(CarryParams P, int run, cons
                                                     int* __restrict__ n_kept) {
   constexpr RowColumns C = columns_of_fields(F);
   constexpr int TC = C.time;
-  constexpr trajectory_queries::CarryColumns kFrom = trajectory_queries::carry_columns(C);
+  constexpr PairColumns kSeven = trajectory_queries::pair_carry(C);   // x y theta kappa v a delta -> v[0 ... 6]
   extern __shared__ double s_mem[];
   __shared__ int s_state[kCyMaxRun];
   const int R = P.n_rows, K = P.n_knots, L = P.n_live;
@@ -72,26 +74,12 @@ __global__ __launch_bounds__(kCyLanes) void k_carry(CarryParams P, int run, cons
     if (e < np * L && s_state[p] == 0) {
       const double* T = s_rows + p * R * F;
       const double q = (T[TC] + advance[b0 + p]) + k * P.delta_t;
-      int i = bracket(R, q, [&](int r) { return T[r * F + TC]; });
-      if (i == 0) i = 1;
-      if (i > R - 1) i = R - 1;
+      const int i = bracket_pair(R, q, [&](int r) { return T[r * F + TC]; });
       const double* p0 = T + (i - 1) * F;
       const double* p1 = p0 + F;
       double* o = s_out + (size_t)e * CILQR_COARSE_FIELDS;
-      const double k0 = p0[TC], k1 = p1[TC];
       double v[7];
-      if (fabs(k1 - k0) < kMathEps) {
-#pragma unroll
-        for (int c = 0; c < 7; ++c) v[c] = p0[kFrom.col[c]];   // the degenerate pair: p0 as it is
-      } else {
-        const double w = (q - k0) / (k1 - k0);
-        const double w1 = 1 - w;
-#pragma unroll
-        for (int c = 0; c < 7; ++c) {
-          const double a = p0[kFrom.col[c]], z = p1[kFrom.col[c]];
-          v[c] = c == 2 ? slerp(a, k0, z, k1, q) : w1 * a + w * z;
-        }
-      }
+      pair_step(kSeven, TC, p0[TC], p1[TC], q, p0, p1, v);
       o[0] = P.delta_t * k;
 #pragma unroll
       for (int c = 0; c < 7; ++c) o[2 + c] = v[c];

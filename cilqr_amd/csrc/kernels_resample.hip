@@ -1,6 +1,8 @@
 // cilqr_resample_rows_batch (include/cilqr.h, "resample"): DiscretizedTrajectory::EvaluateTime / EvaluateStation for
-// every (trajectory, query) pair of a batch.  The host statement is include/cilqr/trajectory_queries.hpp; this file follows
-// it operation by operation (-ffp-contract=off, IEEE division, the exact normalize_angle), so the rows are its bits.
+// every (trajectory, query) pair of a batch.  The host statement is include/cilqr/trajectory_queries.hpp: resample_rows.
+// The bracket and the pair step are ONE function for both (include/cilqr/row_math.hpp: bracket_pair, pair_step over
+// pair_all, built with -ffp-contract=off and IEEE division here as there), so the rows are its bits; what this file adds
+// is where the rows lie while that runs.
 //
 // The kernel moves memory: it reads B K F doubles once and writes B M F.  A lane per query working on global memory would
 // store F-double rows at an F-double stride and bisect through HBM behind dependent loads.  Instead the work items are the
@@ -25,16 +27,13 @@ constexpr int kRsRowDoubles = 3072;   // >= CILQR_DP_MAX_KNOTS * CILQR_PLAN_FIEL
 constexpr int kRsItems = 2048;        // items a workgroup aims for (8 tiles): what its staged rows are shared among
 static_assert(kRsRowDoubles >= CILQR_DP_MAX_KNOTS * CILQR_PLAN_FIELDS, "one problem must fit the row image");
 
-// F: doubles per row (9 coarse, 10 traj, 11 plan); the two controls are the last columns, where there are any
+// F: doubles per row (9 coarse, 10 traj, 11 plan)
 template <int F>
 __global__ __launch_bounds__(kRsLanes) void k_resample(ResampleParams P, int probs_per_wg, unsigned chunk,
                                                        const double* __restrict__ rows, const double* __restrict__ queries,
                                                        double* __restrict__ out) {
-  constexpr RowColumns C = columns_of_fields(F);
+  constexpr PairColumns kAll = pair_all(columns_of_fields(F));   // every column in place
   constexpr int FS = F | 1;
-  constexpr int TH = C.theta;
-  constexpr int CTRL = C.jerk < 0 ? F : C.jerk;   // first control column; F: none
-  static_assert(C.time < 2 && C.station < 2 && CTRL >= F - 2, "a key is one of the first two columns, the controls the last two");
   __shared__ double s_rows[kRsRowDoubles];
   __shared__ double s_out[kRsLanes * FS];
   const int tid = threadIdx.x;
@@ -58,32 +57,10 @@ __global__ __launch_bounds__(kRsLanes) void k_resample(ResampleParams P, int pro
       const unsigned p = e / M, m = e - p * M;
       const double q = P.per_problem ? queries[(size_t)(b0 + p) * M + m] : queries[m];
       const double* R = s_rows + (int)p * K * F;
-      int i = bracket(K, q, [&](int r) { return R[r * F + kc]; });
-      if (i == 0) i = 1;
-      if (i > K - 1) i = K - 1;
+      const int i = bracket_pair(K, q, [&](int r) { return R[r * F + kc]; });
       const double* p0 = R + (i - 1) * F;
       const double* p1 = p0 + F;
-      double* o = s_out + tid * FS;
-      const double k0 = p0[kc], k1 = p1[kc];
-      if (fabs(k1 - k0) < kMathEps) {
-#pragma unroll
-        for (int c = 0; c < F; ++c) o[c] = p0[c];   // loads and stores: the bits travel untouched
-      } else {
-        const double w = (q - k0) / (k1 - k0);
-        const double w1 = 1 - w;
-#pragma unroll
-        for (int c = 0; c < F; ++c) {
-          const double a = p0[c];
-          double v;
-          if (c == TH) v = slerp(a, k0, p1[c], k1, q);
-          else if (c >= CTRL) v = a;
-          else {
-            v = w1 * a + w * p1[c];
-            if (c < 2) v = (c == kc) ? q : v;
-          }
-          o[c] = v;
-        }
-      }
+      pair_step(kAll, kc, p0[kc], p1[kc], q, p0, p1, s_out + tid * FS);
     }
     __syncthreads();
     // ---- the tile leaves: n * F consecutive doubles of `out`

@@ -1,7 +1,8 @@
 // cilqr_stop_rows_batch and what cilqr_stop_scenes_batch puts behind its audits (include/cilqr.h, "stop").  The host
-// statement is include/cilqr/trajectory_queries.hpp: stop_rows; k_stop follows it operation by operation (-ffp-contract=off,
-// IEEE division, the exact normalize_angle, the libm-identical hypot_ref) and runs its stop_step itself, so the rows are its
-// bits.
+// statement is include/cilqr/trajectory_queries.hpp: stop_rows.  Its stop_step, and the bracket and the pair step of
+// include/cilqr/row_math.hpp (bracket_pair, pair_step over pair_stop), are ONE function for both; the station keys
+// (row_math.hpp's hypot_ref where the host statement takes std::hypot), the differenced controls and the statuses k_stop
+// follows operation by operation (-ffp-contract=off, IEEE division), so the rows are its bits.
 //
 // k_stop moves memory: per trajectory it reads n_knots F doubles and writes 11 n_out per profile.  A workgroup of 256 lanes
 // takes a run of whole trajectories -- as many as fit 32 KiB of LDS, at most 16 -- and
@@ -58,6 +59,8 @@ __global__ __launch_bounds__(kStLanes) void k_stop(StopParams P, int run, int nc
                                                    double* __restrict__ travel) {
   constexpr RowColumns C = columns_of_fields(F);
   constexpr RowColumns O = row_columns(CILQR_ROWS_PLAN);
+  constexpr PairColumns kFive = trajectory_queries::pair_stop(C, O);   // x y theta kappa delta, to where a plan row keeps them
+  constexpr PairColumns kFiveV = pair_packed(kFive);                   // ... and to v[0 ... 4]
   extern __shared__ double s_mem[];
   __shared__ int s_refused0[kStMaxChains];   // by the start values: nothing is produced
   __shared__ int s_bad[kStMaxChains];        // a non-finite value was produced
@@ -143,31 +146,15 @@ __global__ __launch_bounds__(kStLanes) void k_stop(StopParams P, int run, int nc
         const double* key = s_key + p * K;
         double* o = s_img + ((size_t)pm * ni + j) * kPF;
         const double q = o[O.station];
-        int i = bracket(K, q, [&](int r) { return key[r]; });
-        if (i == 0) i = 1;
-        if (i > K - 1) i = K - 1;
+        const int i = bracket_pair(K, q, [&](int r) { return key[r]; });
         const double* p0 = T + (i - 1) * F;
         const double* p1 = p0 + F;
-        const double q0 = key[i - 1], q1 = key[i];
-        constexpr int from[5] = {C.x, C.y, C.theta, C.kappa, C.delta};
-        constexpr int to[5] = {O.x, O.y, O.theta, O.kappa, O.delta};
         double v[5];
-        if (fabs(q1 - q0) < kMathEps) {
-#pragma unroll
-          for (int f = 0; f < 5; ++f) v[f] = p0[from[f]];   // the degenerate pair: p0 as it is
-        } else {
-          const double w = (q - q0) / (q1 - q0);
-          const double w1 = 1 - w;
-#pragma unroll
-          for (int f = 0; f < 5; ++f) {
-            const double a = p0[from[f]], z = p1[from[f]];
-            v[f] = f == 2 ? slerp(a, q0, z, q1, q) : w1 * a + w * z;
-          }
-        }
+        pair_step(kFiveV, -1,key[i - 1], key[i], q, p0, p1, v);
         const double t = T[C.time] + P.delta_t * (k0 + j);
         o[O.time] = t;
 #pragma unroll
-        for (int f = 0; f < 5; ++f) o[to[f]] = v[f];
+        for (int f = 0; f < 5; ++f) o[kFive.to[f]] = v[f];
         bad = !(isfinite(t) && isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]) && isfinite(v[3]) && isfinite(v[4]));
       }
       mark_bad(bad, e0 + (tid & ~63), ne, s_bad);

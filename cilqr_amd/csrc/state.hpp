@@ -27,6 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/cilqr/row_math.hpp"   // kMathEps and the rest of the arithmetic shared with the host statements
+
 namespace cilqr {
 
 constexpr int kNX = 6;
@@ -37,7 +39,6 @@ constexpr int kGainPairs = 7;   // 14 doubles
 constexpr int kPartPairs = 3;
 constexpr int kNumAlpha = 11;
 constexpr int kMaxDiscs = 16;
-constexpr double kMathEps = 1e-10;  // algorithm/math/vec2d.h:33
 constexpr int kLaneFields = 11;  // a b c | sx sy | ux uy | len | ex ey | pad (an odd row stride: rows of different segments start in different LDS banks)
 constexpr int kGridCellBytes = 16;
 #ifndef CILQR_GRID_CELLS_LOG2

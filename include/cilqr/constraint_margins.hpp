@@ -13,7 +13,7 @@
 #include <limits>
 #include <vector>
 
-#include "row_layouts.hpp"
+#include "row_math.hpp"
 
 namespace cilqr {
 namespace constraint_margins {
@@ -22,35 +22,13 @@ constexpr int kFields = 8;        // corridor, left lane, right lane, velocity, 
 constexpr int kWhichFields = 6;   // corridor disc, corridor plane, left disc, left segment, right disc, right segment
 constexpr int kLaneRowFields = 7; // a b c start_x start_y end_x end_y
 constexpr int kMaxDiscs = 16;
-constexpr double kMathEpsilon = 1e-10;   // algorithm/math/vec2d.h:33
 constexpr double kInf = std::numeric_limits<double>::infinity();
 
 // what the rule reads of a row (row_layouts.hpp); fields = 0: no such layout, jerk = -1: the layout has no control columns
 using Columns = StateColumns;
 constexpr Columns columns_of(int layout) { return state_columns(layout); }
 
-// hypot as the reference's C library evaluates it for lengths in metres (glibc's e_hypot.c without FMA): the square root
-// of the sum of squares, corrected by one Newton step.  Written out so that the value does not depend on the C library
-// the caller links.
-inline double hypot_ref(double x, double y) {
-  x = std::fabs(x);
-  y = std::fabs(y);
-  const double ax = x < y ? y : x, ay = x < y ? x : y;
-  if (ax >= ay * 0x1p54) return ax + ay;
-  double h = std::sqrt(ax * ax + ay * ay);
-  double t1, t2;
-  if (h <= 2.0 * ay) {
-    const double delta = h - ay;
-    t1 = ax * (2.0 * delta - ax);
-    t2 = (delta - 2.0 * (ax - ay)) * delta;
-  } else {
-    const double delta = h - ax;
-    t1 = 2.0 * delta * (ax - 2.0 * ay);
-    t2 = (4.0 * delta - ay) * ay + delta * delta;
-  }
-  h -= (t1 + t2) / (2.0 * h);
-  return h;
-}
+// (hypot is row_math.hpp's hypot_ref: the value does not depend on the C library the caller links)
 
 // what the rule takes from the configuration (any struct with cilqr_config's field names)
 struct Vehicle {
@@ -109,14 +87,14 @@ inline void prepare_lane(const double* rows7, int n, double shrink, std::vector<
     s.sx = r[3]; s.sy = r[4]; s.ex = r[5]; s.ey = r[6];
     const double dx = s.ex - s.sx, dy = s.ey - s.sy;
     s.len = hypot_ref(dx, dy);
-    s.ux = (s.len <= kMathEpsilon) ? 0.0 : dx / s.len;
-    s.uy = (s.len <= kMathEpsilon) ? 0.0 : dy / s.len;
+    s.ux = (s.len <= kMathEps) ? 0.0 : dx / s.len;
+    s.uy = (s.len <= kMathEps) ? 0.0 : dy / s.len;
   }
 }
 // LineSegment2d::DistanceTo (line_segment2d.cpp:61-75)
 inline double segment_distance(const Segment& s, double px, double py) {
   const double x0 = px - s.sx, y0 = py - s.sy;
-  if (s.len <= kMathEpsilon) return hypot_ref(x0, y0);
+  if (s.len <= kMathEps) return hypot_ref(x0, y0);
   const double proj = x0 * s.ux + y0 * s.uy;
   if (proj <= 0.0) return hypot_ref(x0, y0);
   if (proj >= s.len) return hypot_ref(px - s.ex, py - s.ey);
@@ -131,7 +109,7 @@ inline double segment_distance2(const Segment& s, double px, double py) {
   const double d_end = x1 * x1 + y1 * y1;
   const double c = x0 * s.uy - y0 * s.ux;
   const double d_perp = c * c;
-  return (s.len <= kMathEpsilon || proj <= 0.0) ? d_start : (proj >= s.len ? d_end : d_perp);
+  return (s.len <= kMathEps || proj <= 0.0) ? d_start : (proj >= s.len ? d_end : d_perp);
 }
 // FindNeastLaneSegment (cc:605-618): strict `<`, the first index wins; 0 when no distance is below DBL_MAX
 inline int nearest_segment(const std::vector<Segment>& tab, double px, double py, bool exact_ties) {

@@ -37,6 +37,8 @@
 #include <utility>
 #include <vector>
 
+#include "row_math.hpp"
+
 namespace cilqr {
 
 constexpr int kDpNT = 5;    // dp_planner.h:27-29
@@ -72,26 +74,11 @@ struct CoarsePoint {
 
 namespace dp_detail {
 
-constexpr double kGeomEps = 1e-10;   // math::kMathEpsilon, vec2d.h:33
-constexpr double kDpEps = 1e-3;      // dp_planner.cpp:25
+constexpr double kGeomEps = kMathEps;   // math::kMathEpsilon, vec2d.h:33 (row_math.hpp)
+constexpr double kDpEps = 1e-3;         // dp_planner.cpp:25
 
-inline double NormalizeAngle(double angle) {   // math_utils.cpp:53-59
-  double a = std::fmod(angle + M_PI, 2.0 * M_PI);
-  if (a < 0.0) a += 2.0 * M_PI;
-  return a - M_PI;
-}
-
-inline double Slerp(double a0, double t0, double a1, double t1, double t) {   // math_utils.h:208-225
-  if (std::abs(t1 - t0) <= kGeomEps) return NormalizeAngle(a0);
-  const double a0_n = NormalizeAngle(a0);
-  const double a1_n = NormalizeAngle(a1);
-  double d = a1_n - a0_n;
-  if (d > M_PI) d = d - 2 * M_PI;
-  else if (d < -M_PI) d = d + 2 * M_PI;
-  const double r = (t - t0) / (t1 - t0);
-  const double a = a0_n + d * r;
-  return NormalizeAngle(a);
-}
+inline double NormalizeAngle(double angle) { return normalize_angle(angle); }   // math_utils.cpp:53-59
+inline double Slerp(double a0, double t0, double a1, double t1, double t) { return slerp(a0, t0, a1, t1, t); }   // math_utils.h:208-225
 
 template <int N>
 inline std::array<double, N> LinSpaced(double start, double end) {   // math_utils.h:245-254

@@ -52,28 +52,6 @@ inline bool config_valid(const Config& c, int max_iterations = 1000) {
 inline double max_of(double a, double b) { return (a >= b || b != b) ? a : b; }
 inline double min_of(double a, double b) { return (a <= b || b != b) ? a : b; }
 
-// hypot as glibc 2.35 evaluates it in the build without fused multiply-add (sysdeps/ieee754/dbl-64/e_hypot.c): the scaling
-// branches for huge and tiny arguments are left out, lengths here are metres
-inline double hypot_ref(double x, double y) {
-  x = std::fabs(x);
-  y = std::fabs(y);
-  const double ax = x < y ? y : x, ay = x < y ? x : y;
-  if (ax >= ay * 0x1p54) return ax + ay;
-  double h = std::sqrt(ax * ax + ay * ay);
-  double t1, t2;
-  if (h <= 2.0 * ay) {
-    const double delta = h - ay;
-    t1 = ax * (2.0 * delta - ax);
-    t2 = (delta - 2.0 * (ax - ay)) * delta;
-  } else {
-    const double delta = h - ax;
-    t1 = 2.0 * delta * (ax - 2.0 * ay);
-    t2 = (4.0 * delta - ay) * ay + delta * delta;
-  }
-  h -= (t1 + t2) / (2.0 * h);
-  return h;
-}
-
 // row-major 3x3 products, every element accumulated k = 0, 1, 2
 inline void mul33(const double* a, const double* b, double* r) {
   for (int i = 0; i < 3; ++i)
@@ -143,7 +121,6 @@ constexpr FollowColumns follow_columns(int layout) { return trajectory_columns(l
 inline bool track_rows(const Config& cfg, const Vehicle& veh, int layout, const double* rows, int n_knots, const double* start6,
                        int n_drive, double* driven, int max_steps = kMaxSimSteps) {
   namespace tq = trajectory_queries;
-  constexpr double kEps = tq::kMathEpsilon;
   const FollowColumns c = follow_columns(layout);
   const int K = n_knots, F = c.fields;
   // the follow table: time, station, x, y, theta, v per knot
@@ -189,7 +166,7 @@ inline bool track_rows(const Config& cfg, const Vehicle& veh, int layout, const 
   record(0, start_time);
   double ctime = start_time;
   int i = 1, steps = 0;
-  for (double t = start_time; t < end_time + kEps && i < n_drive && steps < max_steps; t += cfg.sumulation_dt, ++steps) {
+  for (double t = start_time; t < end_time + kMathEps && i < n_drive && steps < max_steps; t += cfg.sumulation_dt, ++steps) {
     // ---- preview and projection
     double sn, cs;
     tq::sin_cos(cth, &sn, &cs);
@@ -216,7 +193,7 @@ inline bool track_rows(const Config& cfg, const Vehicle& veh, int layout, const 
         const double v1_norm = std::sqrt(v1x * v1x + v1y * v1y);
         const double dot = v0x * v1x + v0y * v1y;
         const double st = fs[i0] + dot / v1_norm;
-        if (std::fabs(fs[i1] - fs[i0]) < kEps) {
+        if (std::fabs(fs[i1] - fs[i0]) < kMathEps) {
           ps = fs[i0]; px = fx[i0]; py = fy[i0]; pth = fth[i0];
         } else {
           const double w = (st - fs[i0]) / (fs[i1] - fs[i0]);
@@ -237,7 +214,7 @@ inline bool track_rows(const Config& cfg, const Vehicle& veh, int layout, const 
       const double time = ctime + 0.0;
       const int it = tq::bracket(ft, 1, 0, K, time);
       const double t0 = ft[it - 1], t1 = ft[it];
-      if (std::fabs(t1 - t0) < kEps) {
+      if (std::fabs(t1 - t0) < kMathEps) {
         match_s = fs[it - 1];
         match_v = fv[it - 1];
       } else {
@@ -282,7 +259,7 @@ inline bool track_rows(const Config& cfg, const Vehicle& veh, int layout, const 
       cx = nx; cy = ny; cth = nth; cv = nv; cdl = ndl; ca = na;
     }
     ctime = t;
-    if (i < K && ctime > ft[i] - kEps) {
+    if (i < K && ctime > ft[i] - kMathEps) {
       double* prev = driven + (size_t)(i - 1) * kDrivenFields;
       prev[8] = jerk;
       prev[9] = delta_rate;

@@ -5,7 +5,8 @@
 // cilqr_cartesian_points.  Between the two, the carry rule on top of EvaluateTime: the host statement of cilqr_carry_rows; and
 // the stop rule on top of EvaluateStation: the host statement of cilqr_stop_rows.
 // Header-only, C++14, no HIP.  The rules are stated once, in include/cilqr.h ("resample", "frenet"); this file follows
-// them step by step.
+// them step by step.  NormalizeAngle, slerp, the bracket and the pair step are the functions of row_math.hpp, and
+// stop_step is stated here: those the kernels RUN; the order of the steps around them a kernel follows on its own.
 #ifndef CILQR_TRAJECTORY_QUERIES_HPP_
 #define CILQR_TRAJECTORY_QUERIES_HPP_
 
@@ -14,13 +15,10 @@
 #include <cstdint>
 #include <cstring>
 
-#include "row_layouts.hpp"
+#include "row_math.hpp"
 
 namespace cilqr {
 namespace trajectory_queries {
-
-constexpr double kPi = 3.14159265358979323846;   // M_PI
-constexpr double kMathEpsilon = 1e-10;            // algorithm/math/vec2d.h:33
 
 // the columns of a trajectory layout (CILQR_ROWS_TRAJ 0 / _PLAN 1 / _COARSE 2, row_layouts.hpp); fields = 0: no such layout
 using Columns = RowColumns;
@@ -34,68 +32,17 @@ inline int key_column(int layout, int key) {
   return -1;
 }
 
-inline double NormalizeAngle(double angle) {   // math_utils.cpp:53-59
-  double a = std::fmod(angle + kPi, 2.0 * kPi);
-  if (a < 0.0) a += 2.0 * kPi;
-  return a - kPi;
-}
-
-inline double slerp(double a0, double t0, double a1, double t1, double t) {   // math_utils.h:208-225
-  if (std::fabs(t1 - t0) <= kMathEpsilon) return NormalizeAngle(a0);
-  const double a0_n = NormalizeAngle(a0);
-  const double a1_n = NormalizeAngle(a1);
-  double d = a1_n - a0_n;
-  if (d > kPi) d = d - 2 * kPi;
-  else if (d < -kPi) d = d + 2 * kPi;
-  const double r = (t - t0) / (t1 - t0);
-  const double a = a0_n + d * r;
-  return NormalizeAngle(a);
-}
+inline double NormalizeAngle(double angle) { return normalize_angle(angle); }
+using cilqr::slerp;
 
 // the row index i (1 <= i <= n_knots - 1) of p1; p0 is row i - 1.  rows [n_knots][fields], n_knots >= 2.
 inline int bracket(const double* rows, int fields, int key_col, int n_knots, double q) {
-  int i;
-  if (q >= rows[(size_t)(n_knots - 1) * fields + key_col]) {
-    i = n_knots - 1;
-  } else if (q < rows[key_col]) {
-    i = 0;
-  } else {   // std::lower_bound's halving, written out: defined for any input
-    int first = 0, len = n_knots;
-    while (len > 0) {
-      const int half = len >> 1;
-      if (rows[(size_t)(first + half) * fields + key_col] < q) {
-        first += half + 1;
-        len -= half + 1;
-      } else {
-        len = half;
-      }
-    }
-    i = first;
-  }
-  if (i == 0) i = 1;
-  if (i > n_knots - 1) i = n_knots - 1;   // not reached: q < key[K-1] here, so the halving stops at or before K - 1
-  return i;
+  return bracket_pair(n_knots, q, [=](int r) { return rows[(size_t)r * fields + key_col]; });
 }
 
 // one output row from the pair (p0, p1) of a layout
 inline void interpolate(const Columns& c, int key_col, const double* p0, const double* p1, double q, double* out) {
-  const double k0 = p0[key_col], k1 = p1[key_col];
-  if (std::fabs(k1 - k0) < kMathEpsilon) {
-    std::memcpy(out, p0, sizeof(double) * (size_t)c.fields);   // p0, its key column included, as bits
-    return;
-  }
-  const double w = (q - k0) / (k1 - k0);
-  for (int f = 0; f < c.fields; ++f) {
-    if (f == key_col) {
-      out[f] = q;
-    } else if (f == c.theta) {
-      out[f] = slerp(p0[f], k0, p1[f], k1, q);
-    } else if (f == c.jerk || f == c.rate) {
-      std::memcpy(out + f, p0 + f, sizeof(double));   // a control holds over its step
-    } else {
-      out[f] = (1 - w) * p0[f] + w * p1[f];
-    }
-  }
+  pair_step(pair_all(c), key_col, p0[key_col], p1[key_col], q, p0, p1, out);
 }
 
 // rows [n_knots][fields] -> out [n_queries][fields]; the arguments are taken as checked (cilqr_resample_rows)
@@ -118,13 +65,19 @@ struct CarryColumns {
   int col[7];
 };
 constexpr CarryColumns carry_columns(const RowColumns& c) { return CarryColumns{{c.x, c.y, c.theta, c.kappa, c.v, c.a, c.delta}}; }
+// ... as an instance of the pair step: out[0 ... 6]
+constexpr PairColumns pair_carry(const RowColumns& c) {
+  PairColumns L{};
+  for (int e = 0; e < 7; ++e) L = pair_with(L, carry_columns(c).col[e], e, e == 2 ? kPairSlerp : kPairLerp);
+  return L;
+}
 
 // rows [n_rows][fields] -> coarse9 [n_knots][9], coarse6 [n_knots][6], knots3 [n_knots][3], station [n_knots] (each may be
 // null); returns the state (0 kept, 1 not asked, 2 refused).  The arguments are taken as checked (cilqr_carry_rows).
 inline int carry_rows(int layout, const double* rows, int n_rows, double advance, double max_advance, int n_knots,
                       double delta_t, double* coarse9, double* coarse6, double* knots3, double* station) {
   const Columns c = columns_of(layout);
-  const CarryColumns from = carry_columns(c);
+  const PairColumns seven = pair_carry(c);
   int state = 0;
   if (advance < 0.0) state = 1;
   else if (!(advance <= max_advance)) state = 2;                                          // a NaN, or above the limit
@@ -132,15 +85,15 @@ inline int carry_rows(int layout, const double* rows, int n_rows, double advance
   double nine[256 * kCoarseFields];   // CILQR_DP_MAX_KNOTS rows
   if (state == 0) {
     const double first = rows[c.time] + advance;
-    double r[11], s = 0.0;
+    double s = 0.0;
     bool finite = true;
     for (int k = 0; k < n_knots; ++k) {
       const double q = first + k * delta_t;
       const int i = bracket(rows, c.fields, c.time, n_rows, q);
-      interpolate(c, c.time, rows + (size_t)(i - 1) * c.fields, rows + (size_t)i * c.fields, q, r);
+      const double *p0 = rows + (size_t)(i - 1) * c.fields, *p1 = p0 + c.fields;
       double* o = nine + (size_t)k * kCoarseFields;
       o[0] = delta_t * k;
-      for (int e = 0; e < 7; ++e) std::memcpy(o + 2 + e, r + from.col[e], sizeof(double));
+      pair_step(seven, c.time, p0[c.time], p1[c.time], q, p0, p1, o + 2);
       if (k > 0) s = s + std::hypot(o[2] - o[2 - kCoarseFields], o[3] - o[3 - kCoarseFields]);
       o[1] = s;
       finite = finite && std::isfinite(o[2]) && std::isfinite(o[3]) && std::isfinite(o[4]) && std::isfinite(o[6]) &&
@@ -188,6 +141,14 @@ constexpr StopState stop_step(const StopState& c, double a_target, double jd, do
   return StopState{c.s + hd * (c.v + vn), vn, an};
 }
 
+// what a stop row takes from the path, as an instance of the pair step: x y theta kappa delta of `from` to where `to` keeps them
+constexpr PairColumns pair_stop(const RowColumns& from, const RowColumns& to) {
+  const int f[5] = {from.x, from.y, from.theta, from.kappa, from.delta}, t[5] = {to.x, to.y, to.theta, to.kappa, to.delta};
+  PairColumns L{};
+  for (int e = 0; e < 5; ++e) L = pair_with(L, f[e], t[e], e == 2 ? kPairSlerp : kPairLerp);
+  return L;
+}
+
 // rows [n_knots][fields] of `layout` as plan rows [n_knots][11] with the station key of the rule in the station column; a
 // column the layout lacks is 0
 inline void stop_plan_rows(int layout, const double* rows, int n_knots, double* plan) {
@@ -225,22 +186,18 @@ inline int stop_rows(int layout, const double* rows, int n_knots, double a_targe
     const double jd = jerk * delta_t, hd = 0.5 * delta_t;
     StopState c{key0, v0, a0};
     bool overrun = false, finite = true;
-    double r[11];
+    const PairColumns five = pair_stop(P, P);
     for (int k = 0; k < n_out; ++k) {
       if (k > 0) c = stop_step(c, a_target, jd, hd, delta_t);
       if (c.s > s_end) overrun = true;
       if (knot < 0 && c.v == 0.0) knot = k;
       const double q = c.s > s_end ? s_end : c.s;
       const int i = bracket(plan, P.fields, P.station, n_knots, q);
-      interpolate(P, P.station, plan + (size_t)(i - 1) * P.fields, plan + (size_t)i * P.fields, q, r);
+      const double *p0 = plan + (size_t)(i - 1) * P.fields, *p1 = p0 + P.fields;
       double* o = img + (size_t)k * P.fields;
       o[P.time] = plan[P.time] + delta_t * k;
       o[P.station] = q;
-      std::memcpy(o + P.x, r + P.x, sizeof(double));
-      std::memcpy(o + P.y, r + P.y, sizeof(double));
-      std::memcpy(o + P.theta, r + P.theta, sizeof(double));
-      std::memcpy(o + P.kappa, r + P.kappa, sizeof(double));
-      std::memcpy(o + P.delta, r + P.delta, sizeof(double));
+      pair_step(five, P.station, p0[P.station], p1[P.station], q, p0, p1, o);
       o[P.v] = c.v;
       o[P.a] = c.a;
       o[P.jerk] = 0.0;
@@ -295,19 +252,7 @@ inline void sin_cos(double angle, double* sn, double* cs) {
 
 // LinearInterpolateTrajectory (cpp:66-87) on centre rows: out[7]
 inline void interpolate_center(const double* p0, const double* p1, double s, double* out) {
-  const double s0 = p0[0], s1 = p1[0];
-  if (std::fabs(s1 - s0) < kMathEpsilon) {
-    std::memcpy(out, p0, sizeof(double) * kCenterFields);
-    return;
-  }
-  const double w = (s - s0) / (s1 - s0);
-  out[0] = s;
-  out[1] = (1 - w) * p0[1] + w * p1[1];
-  out[2] = (1 - w) * p0[2] + w * p1[2];
-  out[3] = slerp(p0[3], s0, p1[3], s1, s);
-  out[4] = (1 - w) * p0[4] + w * p1[4];
-  out[5] = (1 - w) * p0[5] + w * p1[5];
-  out[6] = (1 - w) * p0[6] + w * p1[6];
+  pair_step(pair_center(), 0, p0[0], p1[0], s, p0, p1, out);
 }
 
 // QueryNearestPoint (cpp:138-157): the first index with the smallest squared distance; 0 when none is below DBL_MAX

@@ -76,6 +76,15 @@ def crafted_cases():
     add("fifty-one knots over fifty-one rows", np.arange(51) * DT, 0.5, carry.KEPT, ("search", "past_end"), n_knots=51, max_advance=2.0)
     add("the limit of rows and knots", np.arange(256) * 0.02 + 1.0, 0.011, carry.KEPT, ("search", "past_end"), n_knots=256,
         delta_t=0.03, max_advance=2.0)
+    # (added last: the cases above keep their draws)  1e-10 - 0.0 is 1e-10 exactly: the pair is interpolated (`<`), its
+    # heading that of its first row (slerp's own `<=`); the first knot lies inside the pair, or on its second key
+    add("times exactly 1e-10 apart, a knot inside", [0.0, 1e-10, 1.0], 5e-11, carry.KEPT, ("search",), n_knots=3,
+        delta_t=0.25, theta=[1.0, 2.5, 2.75])
+    add("times exactly 1e-10 apart, a knot on the second", [0.0, 1e-10, 1.0], 1e-10, carry.KEPT, ("search",), n_knots=3,
+        delta_t=0.25, theta=[1.0, 2.5, 2.75])
+    # more than 2 pi outside [-pi, pi): the library call of NormalizeAngle
+    add("headings far outside [-pi, pi)", grid, 0.13, carry.KEPT, ("search",),
+        theta=np.pi * np.array([7.5, -9.25, 7.75, -9.0, 40.5, 7.5, 7.6, -9.25, -9.3, 7.5, -7.5]))
     return cases
 
 

@@ -59,7 +59,7 @@ static void check_table() {
 static void check_rules() {
   // resample (trajectory_queries.hpp: Columns / columns_of): fields, time, station, theta, first control
   const int resample[3][5] = {{10, 0, -1, 3, 8}, {11, 0, 1, 4, 9}, {9, 0, 1, 4, -1}};
-  // carry (carry_columns, k_carry's kFrom): x y theta kappa v a delta
+  // carry (carry_columns, which pair_carry and so k_carry take): x y theta kappa v a delta
   const int carry[3][7] = {{1, 2, 3, 7, 4, 5, 6}, {2, 3, 4, 5, 6, 7, 8}, {2, 3, 4, 5, 6, 7, 8}};
   // track (tracker.hpp: FollowColumns): fields, time, station, x, theta, v, a, delta; y follows x
   const int follow[3][8] = {{10, 0, -1, 1, 3, 4, 5, 6}, {11, 0, 1, 2, 4, 6, 7, 8}, {9, 0, 1, 2, 4, 6, 7, 8}};
@@ -114,9 +114,9 @@ static void check_rules() {
     CHECK(c.x == (traj ? 1 : 2) && c.y == (traj ? 2 : 3) && c.theta == (traj ? 3 : 4) && c.v == (traj ? 4 : 6) &&
           c.a == (traj ? 5 : 7) && c.delta == (traj ? 6 : 8));                         // k_track_gather: XC TH VC AC DC
     CHECK(c.station == (traj ? -1 : 1));                                               // ... kChord, r[1]
-    CHECK((c.jerk < 0 ? F : c.jerk) == (F == 9 ? F : F - 2));                          // k_resample: CTRL
+    CHECK((c.jerk < 0 ? F : c.jerk) == (F == 9 ? F : F - 2));                          // pair_all: the held columns
     const int from[7] = {traj ? 1 : 2, traj ? 2 : 3, traj ? 3 : 4, traj ? 7 : 5, traj ? 4 : 6, traj ? 5 : 7, traj ? 6 : 8};
-    const tq::CarryColumns k = tq::carry_columns(c);                                   // k_carry: kFrom
+    const tq::CarryColumns k = tq::carry_columns(c);                                   // k_carry: pair_carry
     for (int e = 0; e < 7; ++e) CHECK(k.col[e] == from[e]);
   }
   for (int F : {2, 9, 10, 11}) CHECK(columns_of_fields(F).x == (F == 10 ? 1 : F == 2 ? 0 : 2));   // k_frenet: XC

@@ -95,6 +95,9 @@ def crafted_cases():
     add("NaN values under finite keys", grid, grid[0] + np.array([0.15, 0.25, 0.35, 0.55, 0.65]), ["search"], edit=nan_values)
     add("non-monotone keys", [0.0, 0.4, 0.2, 0.6, 0.5, 0.1, 0.9], [0.05, 0.2, 0.3, 0.45, 0.55, 0.7, 0.9, -1.0, 2.0],
         ["search", "past_end", "before_start"], monotone=False)
+    # (added last: the cases above keep their draws)  more than 2 pi outside [-pi, pi): the library call of NormalizeAngle
+    add("headings far outside [-pi, pi)", grid[:5], grid[0] + np.array([-0.2, 0.0, 0.04, 0.1, 0.17, 0.25, 0.31, 0.4, 0.6]),
+        ["before_start", "first_pair", "search", "past_end"], theta=np.pi * np.array([7.5, -9.25, 7.75, -9.0, 40.5]))
     return cases
 
 

@@ -106,6 +106,25 @@ def cases():
     out.append(_case("knots_256_n_out_256", ROWS_TRAJ, arc(256, 0.2, 0.02, v=12.0, seed=5), [GENTLE, HARD], 0.05, 256))
     out.append(_case("accelerating_start", ROWS_PLAN, arc(51, 0.9, 0.02, v=4.0, a=2.0), [GENTLE, FIRM], 0.1, 80))
     out.append(_case("already_beyond_target", ROWS_PLAN, arc(51, 0.9, 0.02, v=9.0, a=-5.0), [GENTLE], 0.1, 80))
+    # ---- the first two stations exactly 1e-10 apart (1e-10 - 0.0 is 1e-10): the pair is interpolated (`<`), its heading that
+    # of its first row (slerp's own `<=`); knot 0 of every chain is answered by it, and every knot of a standing start
+    close = arc(51, 0.6, 0.05)
+    close[:, 1] -= 0.25
+    close[1, 1] = 1e-10
+    for layout in (ROWS_PLAN, ROWS_COARSE):
+        out.append(_case(f"stations_exactly_1e-10_apart_layout{layout}", layout, close, [GENTLE, FIRM], 0.1, 51))
+    out.append(_case("stations_exactly_1e-10_apart_standing", ROWS_PLAN, close, [FIRM], 0.1, 4, start_va=(0.0, 0.0)))
+    # ... and the LAST two (0.0 - -1e-10 is 1e-10): a chain that runs over the end is clamped onto the second key, w = 1, so
+    # its rows are the last knot's -- a degenerate pair would give the knot before it
+    short = arc(11, 0.6, 0.05)
+    short[:, 1] -= short[-1, 1]
+    short[-2, 1] = -1e-10
+    assert short[-1, 1] == 0.0 and short[-1, 1] - short[-2, 1] == 1e-10
+    for layout in (ROWS_PLAN, ROWS_COARSE):
+        out.append(_case(f"last_stations_exactly_1e-10_apart_layout{layout}", layout, short, [GENTLE, FIRM], 0.1, 51, expect=stop.OVERRUN))
+    # ---- headings more than 2 pi outside [-pi, pi): the library call of NormalizeAngle
+    out.append(_case("headings_near_7.5_pi", ROWS_TRAJ, arc(51, 0.7, 0.09, theta0=7.5 * np.pi), [GENTLE, FIRM], 0.1, 51))
+    out.append(_case("headings_near_-9.25_pi", ROWS_PLAN, arc(51, 0.7, -0.09, theta0=-9.25 * np.pi), [FIRM, HARD], 0.1, 51))
     return out
 
 

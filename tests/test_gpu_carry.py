@@ -93,7 +93,9 @@ def test_kernel_equals_the_host_call_bit_for_bit(opt, shape):
 
 
 def test_crafted_table_alone(opt):
-    """every crafted case as a batch of its own (its own row and knot counts, limit and step), every layout, HOST arrays"""
+    """every crafted case as a batch of its own (its own row and knot counts, limit and step), every layout, HOST arrays:
+    against the host call and -- kernel and host call run one pair step (include/cilqr/row_math.hpp), so a wrong one agrees
+    with itself -- against the NumPy statement"""
     for case in cc.crafted_cases():
         for layout in cc.LAYOUTS:
             rows = rc.rows_in_layout(layout, case.plan)[None]
@@ -101,6 +103,8 @@ def test_crafted_table_alone(opt):
             want = host_batch(rows, layout, adv, case.max_advance, case.n_knots, case.delta_t)
             got = opt.carry(rows, layout, adv, case.max_advance, case.n_knots, case.delta_t)
             check(got, want, (case.name, layout))
+            stated = carry.carry_rows(rows[0], layout, case.advance, case.max_advance, case.n_knots, case.delta_t)
+            check(got, {k: np.asarray(v)[None] for k, v in stated.items()}, (case.name, layout, "NumPy statement"))
             assert want["state"][0] == case.state, case.name
 
 

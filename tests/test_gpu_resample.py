@@ -140,7 +140,9 @@ def test_kernel_equals_the_host_call_bit_for_bit(opt, crafted, shape):
 
 
 def test_crafted_cases_alone(opt, crafted):
-    """every crafted case as a batch of its own (B = 1, its own K), every layout and key, HOST arrays"""
+    """every crafted case as a batch of its own (B = 1, its own K), every layout and key, HOST arrays: against the host call
+    and -- kernel and host call run one pair step (include/cilqr/row_math.hpp), so a wrong one agrees with itself --
+    against the NumPy statement"""
     for case in crafted:
         for layout in rc.LAYOUTS:
             rows = rc.rows_in_layout(layout, case.plan)[None]
@@ -148,6 +150,8 @@ def test_crafted_cases_alone(opt, crafted):
                 want = host_rows(rows, layout, case.queries, key)
                 got = opt.resample(rows, layout, case.queries, key)
                 check(got, want, rows, layout, case.queries, key, (case.name, layout, key))
+                stated = resample.resample_rows(rows[0], layout, case.queries, key)[None]
+                check(got, stated, rows, layout, case.queries, key, (case.name, layout, key, "NumPy statement"))
                 if "degenerate" in case.branches:    # a copied row: its bits
                     deg = [m for m, q in enumerate(case.queries) if resample.branch_of(rows[0], layout, q, key) == "degenerate"]
                     assert deg and np.array_equal(_bits(got[0, deg]), _bits(want[0, deg])), case.name

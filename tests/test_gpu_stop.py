@@ -102,12 +102,15 @@ def test_rows_do_not_depend_on_the_launch_plan(opt, plan, monkeypatch):
 
 
 def test_crafted_table_alone(opt):
-    """every case of the table as a batch of its own (its own counts, profiles and step), HOST arrays"""
+    """every case of the table as a batch of its own (its own counts, profiles and step), HOST arrays: against the host call
+    and -- kernel and host call run one pair step (include/cilqr/row_math.hpp), so a wrong one agrees with itself --
+    against the NumPy statement"""
     for case in sc.cases():
         va = None if case["start_va"] is None else case["start_va"][None]
         want = sc.host_batch(api, case["rows"][None], case["layout"], case["profiles"], case["delta_t"], case["n_out"], va)
         got = opt.stop_rows(case["rows"][None], case["layout"], case["profiles"], case["delta_t"], case["n_out"], va)
         check(got, want, case["name"])
+        check(got, {k: np.asarray(v)[:, None] for k, v in sc.reference(case).items()}, (case["name"], "NumPy statement"))
         if case["expect"] is not None:
             assert got["status"][0, 0] == case["expect"], case["name"]
 

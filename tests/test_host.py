@@ -40,7 +40,8 @@ def _check_library_fingerprint():
     files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp")), key=os.path.basename)
     files = sorted([os.path.basename(f) for f in files if os.path.basename(f) != "build_id.h"])
     h = hashlib.sha256()   # same order as the Makefile's $(sort ...): the ../../include paths sort first
-    for f in ("cilqr.h", os.path.join("cilqr", "dp_planner.hpp"), os.path.join("cilqr", "row_layouts.hpp")):
+    for f in ("cilqr.h", os.path.join("cilqr", "dp_planner.hpp"), os.path.join("cilqr", "row_layouts.hpp"),
+              os.path.join("cilqr", "row_math.hpp")):
         h.update(open(os.path.join(ROOT, "include", f), "rb").read())
     for f in files:
         h.update(open(os.path.join(csrc, f), "rb").read())
